@@ -8,12 +8,19 @@ ms per cost volume, on N MI355X of one node.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W             # ... or runs as one rank of an external launcher
 
-Prints ONE JSON line on rank 0.  Extra objects: `roofline` (dominant kernel, live HIP-event timing), `roofline_costvol`
-(the HBM-bound cost-volume build), `roofline_worst` (the kernels furthest below their roofline, live-timed in the same
-steps), `configs` (N=1 only: the other BASELINE.json configurations that fit one GPU -- eval forward of cfg 1, the KITTI
-frame and the 256x512 training crop of cfg 4, the cfg 5 cost-volume microbench -- each with its own steps / ms so the
-driver's clock can bound them), `cpu_baseline` (the oracle port on host cores; N=1 only).
-Synthetic data (N(0,1) images, U(0,191) ground truth), random-init weights (reference init rule).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times exactly --steps steps and prints the headline
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step, ...); nothing else
+runs on the GPU.  `--full` adds, after the timed steps: `ms_per_cost_volume` (the stand-alone cost-volume build), `roofline`
+(dominant kernel, HIP-event timing in a second pass of the same step), `roofline_costvol` (the HBM-bound cost-volume build),
+`roofline_worst` (the kernels furthest below their roofline, timed in the same second pass), `step_breakdown_ms`,
+`explicit_cost_volume` and `configs` (N=1 only: the other BASELINE.json configurations that fit one GPU -- eval forward of
+cfg 1, the KITTI frame and the 256x512 training crop of cfg 4, the cfg 5 cost-volume microbench -- each with its own steps /
+ms so the driver's clock can bound them; off with --no-extras), `cpu_baseline` (the oracle port on host cores; N=1 only;
+off with --no-cpu-baseline).
+`--dump-outputs DIR` writes what the last timed step computed -- what a caller of the step receives -- as DIR/<name>.npy
+(float32; see dump_outputs), so that two builds can be compared output for output.
+Synthetic data (N(0,1) images, U(0,191) ground truth, seeded), random-init weights (reference init rule, seeded): the same
+arguments give the same inputs in every run.
 """
 from __future__ import annotations
 
@@ -49,8 +56,18 @@ def parse():
                    help="run the reference's explicit op sequence (4-D concat volume + 64->32 Conv3d) instead of the collapsed 2-D form")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--trace-steps", action="store_true", help="diagnostic: synchronise and print the wall time of every timed step")
-    ap.add_argument("--launch-table", default="", help="write the second pass's per-(entry point, shape) device times to this JSON file")
-    return ap.parse_args()
+    ap.add_argument("--launch-table", default="", help="--full only: write the second pass's per-(entry point, shape) device times to this JSON file")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the second (per-launch timing) pass, the cost-volume build, the extras "
+                         "and the CPU baseline (see the module docstring); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (at most 64 MB in all)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.launch_table and not args.full:
+        ap.error("--launch-table is written from the second timing pass: it needs --full")
+    return args
 
 
 def _cpu_model():
@@ -147,6 +164,48 @@ def shard_feeder_rate(dev, B, n_frames=32):
             feeder.close()
         out["shard"] = {"frames": n_frames, "bytes": os.path.getsize(path), "disparity": "fp16"}
     return out
+
+
+DUMP_BYTES = 60 * 2**20          # --dump-outputs: array bytes in all (64 MB with room for the .npy headers)
+
+
+def dump_budget(sizes, budget):
+    """Bytes to write of each array (name -> bytes): an array that fits its share of `budget` is written whole, and what
+    those leave is split evenly over the others."""
+    caps, rest, left = {}, dict(sizes), budget
+    while rest:
+        share = left // len(rest)
+        small = {k: n for k, n in rest.items() if n <= share}
+        if not small:
+            caps.update({k: share for k in rest})
+            break
+        for k, n in small.items():
+            caps[k] = n
+            left -= n
+            del rest[k]
+    return caps
+
+
+def dump_outputs(outputs, dirname, budget_bytes=DUMP_BYTES):
+    """name -> tensor, written as DIR/<name>.npy in float32 (float64 stays float64).  An array over its share of the budget
+    (dump_budget) is written as a fixed sample: the elements at the sorted first `cap` indices of a permutation seeded with 0,
+    flattened -- the same indices in every run with the same arguments."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for k, t in outputs.items():
+        t = t.detach().cpu()
+        host[k] = t if t.dtype == torch.float64 else t.float()
+    caps = dump_budget({k: t.numel() * t.element_size() for k, t in host.items()}, budget_bytes)
+    written = {}
+    for k, t in host.items():
+        n = caps[k] // t.element_size()
+        if n < t.numel():
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:n].sort().values
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(dirname, k + ".npy"), t.numpy())
+        written[k] = t.numel()
+    return written
 
 
 def _timed(fn, steps, warmup, sync):
@@ -323,15 +382,21 @@ def main():
 
     def train_step(l, r, g):
         ddp.zero_grad()
-        loss, count = ecm_dist.masked_smooth_l1_x3_with_count(model(l, r), g, D)      # train.py:162-174
+        preds = model(l, r)
+        loss, count = ecm_dist.masked_smooth_l1_x3_with_count(preds, g, D)            # train.py:162-174
         ddp.global_mean_loss(loss, count).backward()                                  # one masked mean over the GLOBAL batch
         ddp.allreduce_gradients()
         opt.step()
-        return loss
+        return loss, preds
 
+    # step() -> (the tensor that must be finite, what a caller of the step receives: name -> tensor for --dump-outputs).
+    # Training: the loss, the three disparity maps, the gradient bucket (every parameter's .grad, FlatBucketDDP order) and the
+    # parameters after the optimizer step; the eval forward: the three disparity maps.
     if args.mode == "train":
         def step():
-            return train_step(left, right, gt)
+            loss, preds = train_step(left, right, gt)
+            return loss, lambda: {"loss": loss, **{f"disp{i + 1}": p for i, p in enumerate(preds)}, "grads": ddp.flat,
+                                  "params": torch.cat([p.detach().reshape(-1) for p in ddp.params])}
     else:
         model.eval()
         if not args.graph:
@@ -340,11 +405,13 @@ def main():
             graphed = ecm_dist.GraphedForward(model, left, right, cluster_groupnorm=True)    # one graph, replayed alone
 
             def step():
-                return graphed(left, right)[2]
+                preds = graphed(left, right)
+                return preds[2], lambda: {f"disp{i + 1}": p for i, p in enumerate(preds)}
         else:
             def step():
                 with torch.no_grad():
-                    return model(left, right)[2]
+                    preds = model(left, right)
+                return preds[2], lambda: {f"disp{i + 1}": p for i, p in enumerate(preds)}
 
     def barrier():
         torch.cuda.synchronize()
@@ -356,8 +423,12 @@ def main():
         if rank == 0:
             print(f"[bench] {msg}", file=sys.stderr, flush=True)
 
+    # `last = None` before each step releases the previous step's outputs before the next one starts, as a discarded
+    # result would be: the allocator sees the same pattern with and without --dump-outputs
+    last = None
     for i in range(args.warmup):
-        step()
+        last = None
+        last = step()
         torch.cuda.synchronize()
         note(f"warmup step {i + 1}/{args.warmup} done")
     # time EXACTLY K steps, un-instrumented
@@ -367,61 +438,71 @@ def main():
     if args.trace_steps:                                   # diagnostic mode (a sync per step; not the headline protocol)
         for i in range(args.steps):
             ts = time.perf_counter()
-            step()
+            last = None
+            last = step()
             torch.cuda.synchronize()
             note(f"step {i}: {(time.perf_counter() - ts) * 1e3:.1f} ms  (allocator: {torch.cuda.memory_reserved() / 2**30:.1f} GiB reserved)")
     else:
         for _ in range(args.steps):
-            step()
+            last = None
+            last = step()
     barrier()
     dt = time.perf_counter() - t0
     ms1 = torch.cuda.memory_stats()
     device_allocs_timed = int(ms1.get("num_device_alloc", 0) - ms0.get("num_device_alloc", 0))
     note(f"timed region: {device_allocs_timed} device allocations by the caching allocator, reserved "
          f"{ms0.get('reserved_bytes.all.current', 0) / 2**30:.1f} -> {ms1.get('reserved_bytes.all.current', 0) / 2**30:.1f} GiB")
-    # second pass, outside the timed region: the dominant kernel and the kernels furthest below their roofline are
-    # event-timed per launch on the launch stream (torch's current stream, the one every kernel of the step is launched on)
-    TIMED = ("ecm_conv_wino_fwd", "ecm_conv3d_k3_fwd", "ecm_conv3d_k3_wgrad", "ecm_conv3d_c1_fwd", "ecm_conv3d_c1_gn_fwd", "ecm_weights9_fwd",
-             "ecm_weights9_bwd", "ecm_deconv3d_k3s2_fwd")
-    # The timed steps run the weight gradients on a second stream, under the data-gradient / GroupNorm chain (ops._on_side):
-    # a launch then shares the device and its duration says nothing about the kernel.  For this pass they go back onto the
-    # main stream, so every timed launch has the device to itself (profiles/: the kernel stats of a run with
-    # ECM_WGRAD_OVERLAP=0 are the ones these averages agree with).
-    overlap_was = ops.enable_wgrad_overlap(False)
-    for name in TIMED:
-        lib.enable_timer(name)
-    lib.enable_all_timers()                                # ... and every other entry point, for step_breakdown_ms
-    n_pass2 = min(args.steps, 5)
-    for _ in range(n_pass2):                               # every rank: the training step holds a collective
-        step()
-    torch.cuda.synchronize()
-    timers = lib.disable_timers()
-    breakdown = step_breakdown(timers, n_pass2)
-    if args.launch_table and rank == 0:
-        rows = {}
-        for name, evs in timers.items():
-            for s_, e_, a in evs:
-                r = rows.setdefault((name, tuple(a), tuple(getattr(a, "longs", ()))), [0, 0.0])
-                r[0] += 1
-                r[1] += s_.elapsed_time(e_)
-        table = [{"entry": k[0], "family": _family(k[0], k[1]), "int_args": list(k[1]), "size_args": list(k[2]),
-                  "launches_per_step": v[0] / n_pass2, "ms_per_step": v[1] / n_pass2, "avg_launch_ms": v[1] / v[0]}
-                 for k, v in rows.items()]
-        table.sort(key=lambda r: -r["ms_per_step"])
-        with open(args.launch_table, "w") as f:
-            json.dump({"note": "per (C-ABI entry point, integer arguments) device time of one training step; HIP events, "
-                               "weight gradients on the main stream", "steps": n_pass2, "rows": table}, f, indent=0)
-    ops.enable_wgrad_overlap(overlap_was)
     ops.check_async_errors()                               # a GroupNorm cluster time-out during the timed steps is fatal
-    last = step()                                          # outside the timed region: the result must be finite
-    assert bool(torch.isfinite(last).all()), "non-finite loss / disparity after the timed steps"
+    assert bool(torch.isfinite(last[0]).all()), "non-finite loss / disparity in the last timed step"
+    if args.dump_outputs and rank == 0:
+        written = dump_outputs(last[1](), args.dump_outputs)
+        note(f"outputs of the last timed step -> {args.dump_outputs}: " + ", ".join(f"{k} [{n}]" for k, n in written.items()))
+    last = None
+    if args.full:
+        # second pass, outside the timed region: the dominant kernel and the kernels furthest below their roofline are
+        # event-timed per launch on the launch stream (torch's current stream, the one every kernel of the step is launched on)
+        TIMED = ("ecm_conv_wino_fwd", "ecm_conv3d_k3_fwd", "ecm_conv3d_k3_wgrad", "ecm_conv3d_c1_fwd", "ecm_conv3d_c1_gn_fwd",
+                 "ecm_weights9_fwd", "ecm_weights9_bwd", "ecm_deconv3d_k3s2_fwd")
+        # The timed steps run the weight gradients on a second stream, under the data-gradient / GroupNorm chain (ops._on_side):
+        # a launch then shares the device and its duration says nothing about the kernel.  For this pass they go back onto the
+        # main stream, so every timed launch has the device to itself (profiles/: the kernel stats of a run with
+        # ECM_WGRAD_OVERLAP=0 are the ones these averages agree with).
+        overlap_was = ops.enable_wgrad_overlap(False)
+        for name in TIMED:
+            lib.enable_timer(name)
+        lib.enable_all_timers()                            # ... and every other entry point, for step_breakdown_ms
+        n_pass2 = min(args.steps, 5)
+        for _ in range(n_pass2):                           # every rank: the training step holds a collective
+            step()
+        torch.cuda.synchronize()
+        timers = lib.disable_timers()
+        breakdown = step_breakdown(timers, n_pass2)
+        if args.launch_table and rank == 0:
+            rows = {}
+            for name, evs in timers.items():
+                for s_, e_, a in evs:
+                    r = rows.setdefault((name, tuple(a), tuple(getattr(a, "longs", ()))), [0, 0.0])
+                    r[0] += 1
+                    r[1] += s_.elapsed_time(e_)
+            table = [{"entry": k[0], "family": _family(k[0], k[1]), "int_args": list(k[1]), "size_args": list(k[2]),
+                      "launches_per_step": v[0] / n_pass2, "ms_per_step": v[1] / n_pass2, "avg_launch_ms": v[1] / v[0]}
+                     for k, v in rows.items()]
+            table.sort(key=lambda r: -r["ms_per_step"])
+            with open(args.launch_table, "w") as f:
+                json.dump({"note": "per (C-ABI entry point, integer arguments) device time of one training step; HIP events, "
+                                   "weight gradients on the main stream", "steps": n_pass2, "rows": table}, f, indent=0)
+        ops.enable_wgrad_overlap(overlap_was)
+        ops.check_async_errors()
+        last = step()[0]                                   # outside the timed region: the result must be finite
+        assert bool(torch.isfinite(last).all()), "non-finite loss / disparity after the second pass"
+        last = None
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
     note(f"timed {args.steps} steps in {dt:.3f} s")
 
-    extras = world == 1 and not args.no_extras and args.mode == "train" and not args.explicit_cost_volume
+    extras = args.full and world == 1 and not args.no_extras and args.mode == "train" and not args.explicit_cost_volume
     sync = torch.cuda.synchronize
     # second reading (1 GPU only): the same step with the reference's explicit op sequence -- 4-D concat volume built by
     # the cost-volume kernel + 64->32 Conv3d on it -- so both forms are on record in the same JSON line
@@ -532,7 +613,8 @@ def main():
         except OSError as e:                       # no scratch space on this box: report, do not fail the bench line
             configs["n4_shard_feeder"] = {"error": str(e)}
 
-    if rank == 0:
+    full = {}                                              # the --full keys of the JSON line
+    if rank == 0 and args.full:
         h, w, Dl = H // 4, W // 4, D // 4
         # "ms per cost-volume build" (BASELINE.json's second metric) is the stand-alone build of the reference's full
         # [B,2C,D',h,w] concat volume (ops.cost_volume = cmfsm.py:667-682), timed here on features of the bench's shape;
@@ -572,7 +654,6 @@ def main():
         cv_ms = ms_of(cv)
         cv_bytes = (2 * 32 * Dl * h * w + 2 * 32 * h * w) * 4.0 * B
         cv_gbs = cv_bytes / (cv_ms * 1e-3) / 1e9 if cv else 0.0
-        pairs = B * world * args.steps
 
         # kernels furthest below their roofline, live-timed in the same steps
         worst = {}
@@ -685,8 +766,6 @@ def main():
                                       "bound": "mfma", "achieved": tf, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
                                       "frac": tf / PEAK_F32_MFMA_TFLOPS, "launches_timed": len(dc), "avg_launch_ms": tot / len(dc)}
 
-        shape_name = {(576, 960): "SceneFlow 960x540 (padded to 576)",
-                      (384, 1248): "KITTI-2015 1242x375 (padded to 1248x384)"}.get((H, W), f"synthetic {W}x{H}")
         # roofline.traffic: HBM bytes per launch from rocprofv3 PMC passes of THIS round (profiles/r02_pmc_traffic.json, written
         # by tools/pmc_traffic.py with the calibration of tools/micro/fetch_calib.hip applied); null until that file exists --
         # round 1's figure used an uncalibrated FETCH_SIZE for 4-byte-per-lane buffer loads and read below the algorithmic bytes.
@@ -705,21 +784,7 @@ def main():
                 traffic_source = "profiles/" + os.path.basename(pmc_file) + " (a committed rocprofv3 --pmc run, NOT measured in this run)"
         except (OSError, KeyError, ValueError, IndexError):
             pass
-        out = {
-            "metric": "stereo-pairs/sec (cmfsm train step fwd+bwd+Adam)" if args.mode == "train"
-                      else "stereo-pairs/sec (cmfsm eval forward)",
-            "value": pairs / dt, "unit": "pairs/s", "n_gpus": devices, "ranks": world, "devices": devices,
-            "backend": backend if world > 1 else "none (single process)", "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            # the timed region must not go to the driver for memory (ops: host run-ahead bound); both figures are of rank 0
-            "device_allocations_in_timed_region": device_allocs_timed,
-            "allocator_reserved_gib": round(ms1.get("reserved_bytes.all.current", 0) / 2**30, 1),
-            "config": {"workload": f"{shape_name} D={D} batch={B}/GPU "
-                                   f"{'fwd+bwd+Adam (train.py path)' if args.mode == 'train' else 'eval forward (test.py path)'}",
-                       "arch": "cmfsm", "global_batch": B * world, "parallelism": f"dp{world}",
-                       "cost_volume": "explicit 4-D tensor" if args.explicit_cost_volume else "collapsed into class-indexed 2-D convolutions",
-                       "launch": "hip graph replay" if (args.mode == "infer" and args.graph) else "eager"},
+        full = {
             "ms_per_cost_volume": cv_ms / B,
             # frac is on EXECUTED matrix-core work: the Winograd kernel issues 12/27 of the direct convolution's multiplies
             # (16 per 2x2 outputs per (kd,ci,co) instead of 36), so executed FLOPs = algorithmic x 12/27 -- the number
@@ -749,16 +814,37 @@ def main():
         }
         if explicit is not None:
             # the reading with north_star's cost-volume kernel ON the step's path, as top-level scalars
-            out["explicit_ms_per_step"] = explicit["ms_per_step"]
-            out["explicit_pairs_per_s"] = explicit["value"]
-            out["explicit_cost_volume"] = explicit
+            full["explicit_ms_per_step"] = explicit["ms_per_step"]
+            full["explicit_pairs_per_s"] = explicit["value"]
+            full["explicit_cost_volume"] = explicit
         if configs:
-            out["configs"] = configs
+            full["configs"] = configs
         if world == 1 and not args.no_cpu_baseline:
             note("cpu baseline (oracle port: 1 pair at the bench resolution; 4 eval forwards + 1 fwd+bwd) ...")
             cb = cpu_baseline(args.cpu_threads, H, W)
             note(f"cpu baseline done: fwd+bwd {cb['seconds']:.1f} s, eval forward {1.0 / cb['eval_forward']['pairs_per_s']:.2f} s")
-            out["cpu_baseline"] = cb
+            full["cpu_baseline"] = cb
+    if rank == 0:
+        shape_name = {(576, 960): "SceneFlow 960x540 (padded to 576)",
+                      (384, 1248): "KITTI-2015 1242x375 (padded to 1248x384)"}.get((H, W), f"synthetic {W}x{H}")
+        out = {
+            "metric": "stereo-pairs/sec (cmfsm train step fwd+bwd+Adam)" if args.mode == "train"
+                      else "stereo-pairs/sec (cmfsm eval forward)",
+            "value": B * world * args.steps / dt, "unit": "pairs/s", "n_gpus": devices, "ranks": world, "devices": devices,
+            "backend": backend if world > 1 else "none (single process)", "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            # the timed region must not go to the driver for memory (ops: host run-ahead bound); both figures are of rank 0
+            "device_allocations_in_timed_region": device_allocs_timed,
+            "allocator_reserved_gib": round(ms1.get("reserved_bytes.all.current", 0) / 2**30, 1),
+            "config": {"workload": f"{shape_name} D={D} batch={B}/GPU "
+                                   f"{'fwd+bwd+Adam (train.py path)' if args.mode == 'train' else 'eval forward (test.py path)'}",
+                       "arch": "cmfsm", "global_batch": B * world, "parallelism": f"dp{world}",
+                       "cost_volume": "explicit 4-D tensor" if args.explicit_cost_volume else "collapsed into class-indexed 2-D convolutions",
+                       "launch": "hip graph replay" if (args.mode == "infer" and args.graph) else "eager"},
+            "full": args.full,
+            **full,
+        }
         print(json.dumps(out), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

@@ -43,3 +43,41 @@ def test_default_arguments_are_the_single_gpu_headline(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "50", "--warmup", "10"])
     a = b.parse()
     assert (a.gpus, a.steps, a.warmup) == (8, 50, 10)
+
+
+def test_plain_run_and_full_options(monkeypatch):
+    """A plain run measures the headline only; --full turns the rest on; --steps really is the number of timed steps."""
+    import pytest
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7"])
+    a = b.parse()
+    assert a.steps == 7 and not a.full and a.dump_outputs == ""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out", "--launch-table", "t.json"])
+    a = b.parse()
+    assert a.full and a.dump_outputs == "out" and a.launch_table == "t.json"
+    for argv in (["bench.py", "--steps", "0"], ["bench.py", "--launch-table", "t.json"]):
+        monkeypatch.setattr(sys, "argv", argv)
+        with pytest.raises(SystemExit):
+            b.parse()
+
+
+def test_dump_outputs_fit_the_budget_and_repeat(tmp_path):
+    """--dump-outputs at the default geometry: the small arrays whole, the gradient and parameter vectors as a fixed sample,
+    float32, at most 64 MB in all, and the same elements in every run."""
+    import numpy as np
+    import torch
+    b = _bench()
+    g = torch.Generator().manual_seed(3)
+    outs = {"loss": torch.tensor(0.25), **{f"disp{i}": torch.rand(4, 576, 960, generator=g) for i in (1, 2, 3)},
+            "grads": torch.randn(5255368, generator=g), "params": torch.randn(5255368, generator=g)}
+    written = b.dump_outputs(outs, str(tmp_path / "a"))
+    b.dump_outputs(outs, str(tmp_path / "b"))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64e6
+    for k, t in outs.items():
+        x, y = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
+        assert x.dtype == np.float32 and np.array_equal(x, y) and x.size == written[k]
+        if k.startswith("disp") or k == "loss":
+            assert np.array_equal(x, t.numpy())
+        else:
+            assert 0 < x.size < t.numel() and np.isin(x, t.numpy()).all()
+    assert b.dump_budget({"a": 10, "b": 100, "c": 100}, 110) == {"a": 10, "b": 50, "c": 50}

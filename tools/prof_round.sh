@@ -6,10 +6,10 @@ cd /tmp && export TMPDIR=/tmp
 RT=${1:-r4}
 O=$R/gpurun_out/prof_$RT
 rm -rf $O; mkdir -p $O
-echo stats; rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-extras > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
+echo stats; rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-extras > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
 # the same run with the weight gradients on the main stream: every launch has the device to itself (what bench.py's roofline times)
 export ECM_WGRAD_OVERLAP=0
-echo stats unshared; rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_unshared -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-extras > $O/bench_under_rocprof_unshared.json 2> $O/bench_under_rocprof_unshared.err
+echo stats unshared; rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_unshared -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-extras > $O/bench_under_rocprof_unshared.json 2> $O/bench_under_rocprof_unshared.err
 unset ECM_WGRAD_OVERLAP
 P="rocprofv3 --kernel-trace --output-format csv"
 echo calib; $P --pmc FETCH_SIZE -d $O/calib_fetch -- $R/tools/micro/fetch_calib > /dev/null 2>&1

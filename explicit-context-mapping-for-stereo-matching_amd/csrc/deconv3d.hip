@@ -32,11 +32,12 @@ struct DeconvCfg {
     static constexpr int LDS_BYTES = (XS_FLOATS + 2 * WS_FLOATS) * 4;
 };
 
-template <int CO_TILES, int CIC, int KD = 3>
+// BIAS: y[b,co,...] += bias[co] in the epilogue (ConvTranspose2d(bias=True) of the cmf decoder, cmf.py:236-239).
+template <int CO_TILES, int CIC, int KD = 3, bool BIAS = false>
 __global__ __launch_bounds__(256 * CO_TILES) void deconv3d_k3s2_mfma(const float* __restrict__ x, const float* __restrict__ wp,
                                                                      float* __restrict__ y, int Ci, int Co, int D, int H,
                                                                      int W, int Do, int Ho, int Wo, int tiles_d, int tiles_h,
-                                                                     int tiles_w) {
+                                                                     int tiles_w, const float* __restrict__ bias) {
     using Cfg = DeconvCfg<CO_TILES, CIC, KD>;
     constexpr int TD = Cfg::TD, TH = Cfg::TH, ID = Cfg::ID, IH = Cfg::IH, IW = Cfg::IW, RS = Cfg::RS, COP = Cfg::COP,
                   NTHR = Cfg::THREADS, NTAPS = Cfg::NTAPS;
@@ -148,6 +149,15 @@ __global__ __launch_bounds__(256 * CO_TILES) void deconv3d_k3s2_mfma(const float
     const size_t HWo = (size_t)Ho * Wo, DHWo = (size_t)Do * HWo;
     float* yb = y + (size_t)b * Co * DHWo;
     const int md = md0, mh = mh0 + row, mw = mw0 + l31;
+    if constexpr (BIAS) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int co = ct * 32 + (i & 3) + 8 * (i >> 2) + 4 * half;
+            const float bv = co < Co ? bias[co] : 0.f;
+#pragma unroll
+            for (int cls = 0; cls < 8; ++cls) acc[cls][i] += bv;
+        }
+    }
     if (md < D && mh < H && mw < W) {
         // The two width-parity classes of a (depth, height) parity pair are the neighbouring outputs ow = 2 mw, 2 mw + 1: one
         // 8-byte store instead of two stride-2 4-byte ones (32 lanes then write 256 contiguous bytes per instruction) whenever
@@ -191,20 +201,20 @@ __global__ void pack_deconv_weight(const float* __restrict__ w, float* __restric
     packed[i] = o < Bc ? w[((size_t)k * Bc + o) * taps + tap] : 0.f;
 }
 
-template <int CO_TILES, int CIC, int KD = 3>
+template <int CO_TILES, int CIC, int KD = 3, bool BIAS = false>
 int launch_deconv(const float* x, const float* wp, float* y, int B, int Ci, int Co, int D, int H, int W, int Do, int Ho,
-                  int Wo, hipStream_t st) {
+                  int Wo, hipStream_t st, const float* bias = nullptr) {
     using Cfg = DeconvCfg<CO_TILES, CIC, KD>;
     const int tiles_d = (D + Cfg::TD - 1) / Cfg::TD, tiles_h = (H + Cfg::TH - 1) / Cfg::TH, tiles_w = (W + TW - 1) / TW;
     const long long nblk = (long long)B * tiles_d * tiles_h * tiles_w;
     if (nblk > 0x7fffffffLL || (long long)D * H * W * 4 >= 0x80000000LL) return ECM_EUNSUP;
-    auto kern = deconv3d_k3s2_mfma<CO_TILES, CIC, KD>;
+    auto kern = deconv3d_k3s2_mfma<CO_TILES, CIC, KD, BIAS>;
     {
         const hipError_t e = ecm_allow_lds(reinterpret_cast<const void*>(kern), Cfg::LDS_BYTES);
         if (e != hipSuccess) return (int)e;
     }
     hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(Cfg::THREADS), Cfg::LDS_BYTES, st, x, wp, y, Ci, Co, D, H, W, Do, Ho,
-                       Wo, tiles_d, tiles_h, tiles_w);
+                       Wo, tiles_d, tiles_h, tiles_w, bias);
     return ECM_LAUNCH_RESULT();
 }
 
@@ -248,4 +258,16 @@ extern "C" int ecm_deconv2d_k3s2_fwd(const float* x, const float* wpacked, float
     hipStream_t st = ecm_stream(stream);
     if (Co > 32) return launch_deconv<2, 4, 1>(x, wpacked, y, B, Ci, Co, 1, H, W, 1, Ho, Wo, st);
     return launch_deconv<1, 4, 1>(x, wpacked, y, B, Ci, Co, 1, H, W, 1, Ho, Wo, st);
+}
+
+// ---- 2-D with bias: nn.ConvTranspose2d(Ci, Co, 3, 2, 1, 1, bias=True) (cmf decoder's deconv_module_list, cmf.py:236-239);
+// the bias is added to the accumulators before the stores (no second pass over the full-resolution map)
+extern "C" int ecm_deconv2d_k3s2_bias_fwd(const float* x, const float* wpacked, const float* bias, float* y, int B, int Ci,
+                                          int Co, int H, int W, int Ho, int Wo, void* stream) {
+    ECM_CHECK_ARG(x && wpacked && bias && y && B > 0 && H > 0 && W > 0);
+    if (Ci % 4 != 0 || Co < 1 || Co > 64) return ECM_EUNSUP;
+    if (Ho > 2 * H || Ho < 2 * H - 1 || Wo > 2 * W || Wo < 2 * W - 1) return ECM_EUNSUP;
+    hipStream_t st = ecm_stream(stream);
+    if (Co > 32) return launch_deconv<2, 4, 1, true>(x, wpacked, y, B, Ci, Co, 1, H, W, 1, Ho, Wo, st, bias);
+    return launch_deconv<1, 4, 1, true>(x, wpacked, y, B, Ci, Co, 1, H, W, 1, Ho, Wo, st, bias);
 }

@@ -258,6 +258,8 @@ _ENCODERS = {
     "sub4": dict(first_tail="conv", layers=((1, 1), (2, 1), (1, 2), (1, 4)), pools=(64, 32, 16, 8), raw="layer2"),
     "sub8": dict(first_tail="convbn", layers=((2, 1), (2, 1), (1, 2), (1, 4)), pools=(4, 32, 16, 8), raw="layer2"),
     "sub16": dict(first_tail="convbn", layers=((2, 1), (2, 1), (2, 1), (1, 4)), pools=(4, 2, 16, 8), raw="layer3"),
+    # cmf.py:126-225: stride-2 stem of three convbn+ReLU, no secondconv; layer1's output (1/2 resolution) is the decoder's `half`
+    "cmf": dict(first_tail="none", stem_stride=2, layers=((1, 1), (2, 1), (1, 1), (1, 2)), pools=(64, 32, 16, 8), raw="layer2"),
 }
 
 
@@ -276,17 +278,21 @@ def _pyramid_pools(x, pools):
 
 class feature_extraction(nn.Module):
     """Returns (low-res 32-ch feature, layer1 output, full-res 32-ch firstconv output)  (cmfsm.py:126-236 and the
-    per-architecture copies: cmfsm_sub_8.py:126-236, cmfsm_sub_16.py:127-239, cm_sub_4.py:126-236)."""
+    per-architecture copies: cmfsm_sub_8.py:126-236, cmfsm_sub_16.py:127-239, cm_sub_4.py:126-236).  Variant "cmf"
+    (cmf.py:126-225, no full-resolution map): the third result is layer1's output (1/2 resolution) again, or with `head`
+    its first `head` samples."""
 
     def __init__(self, variant="cmfsm"):
         super().__init__()
         cfg = _ENCODERS[variant]
         self.variant = variant
         self.inplanes = 32
-        head = [convbn(3, 32, 3, 1, 1, 1), nn.ReLU(inplace=True),
+        head = [convbn(3, 32, 3, cfg.get("stem_stride", 1), 1, 1), nn.ReLU(inplace=True),
                 convbn(32, 32, 3, 1, 1, 1), nn.ReLU(inplace=True),
                 convbn(32, 32, 3, 1, 1, 1), nn.ReLU(inplace=True)]
-        if cfg["first_tail"] == "conv":
+        if cfg["first_tail"] == "none":
+            self.firstconv = nn.Sequential(*head)
+        elif cfg["first_tail"] == "conv":
             self.firstconv = nn.Sequential(*head, EncConv2d(32, 32, kernel_size=3, padding=1, stride=1, bias=False))
             self.secondconv = nn.Sequential(
                 HipGroupNorm(NUM_GROUPS, 32), nn.ReLU(inplace=True),
@@ -344,7 +350,12 @@ class feature_extraction(nn.Module):
         gradient is then folded into the map's gradient in place (ops.fork_head) instead of through a zero-padded copy."""
         output_all = _seq_fused(self.firstconv, x)
         output_head = None
-        if head is not None and isinstance(self.secondconv[0], HipGroupNorm):
+        if not hasattr(self, "secondconv"):           # cmf.py:197-198: firstconv -> layer1 directly
+            output_rt = self.layer1(output_all)
+            output_all = output_rt
+            if head is not None:
+                output_rt, output_head = ops.fork_head(output_rt, head)
+        elif head is not None and isinstance(self.secondconv[0], HipGroupNorm):
             # the map's whole-batch consumer is secondconv's GroupNorm + ReLU: that node hands the head slice out and folds
             # its gradient into its own data gradient (ops.GroupNormAct `head`)
             y, output_head = self.secondconv[0].fused(output_all, None, True, head=head)
@@ -670,9 +681,146 @@ class bilinear_cmf_sub_16(_ECMNet):
     ENCODER, HOURGLASSES, HEAD = "sub16", 3, "trilinear"
 
 
+# ------------------------------------------------------------------------------------------------
+# cmf: super-resolution refinement decoder (cmf.py:227-264)
+# ------------------------------------------------------------------------------------------------
+class HipConvTranspose2d(nn.ConvTranspose2d):
+    """nn.ConvTranspose2d(Ci, Co, 3, stride 2, pad 1, output_padding 1, bias=True) of the decoder (cmf.py:236-239) on the
+    bias-taking 2-D transposed-convolution kernel (ops.deconv2d_k3s2_bias); any other configuration raises unless
+    ECM_ALLOW_FALLBACK=1 (like EncConv2d)."""
+
+    def _native(self):
+        return (self.kernel_size == (3, 3) and self.stride == (2, 2) and self.padding == (1, 1)
+                and self.output_padding == (1, 1) and self.dilation == (1, 1) and self.groups == 1 and self.bias is not None
+                and self.padding_mode == "zeros" and self.out_channels <= 64 and self.in_channels % 4 == 0)
+
+    def forward(self, x, output_size=None):
+        if self._native() and output_size is None:
+            return ops.deconv2d_k3s2_bias(x, self.weight, self.bias)
+        if not ALLOW_FALLBACK:
+            raise RuntimeError(f"HipConvTranspose2d({self.in_channels}->{self.out_channels}, k={self.kernel_size}, s={self.stride}, "
+                               f"p={self.padding}, op={self.output_padding}, bias={self.bias is not None}) is outside the native "
+                               "kernels; set ECM_ALLOW_FALLBACK=1 to run it on PyTorch-ROCm's own convolution instead")
+        SLOW_PATH_EVENTS.append(("miopen_conv_transpose2d", self.in_channels, self.out_channels, self.kernel_size))
+        return super().forward(x, output_size)
+
+
+class HipConv2dC1(nn.Conv2d):
+    """conv_out, nn.Conv2d(96, 1, 3, 1, 1, bias=True) (cmf.py:259), with the ReLU that follows it (`crap`, cmf.py:260,264)
+    fused: forward() returns relu(conv(x)) on the one-output-channel kernels (ops.conv2d_c1_relu)."""
+
+    def _native(self):
+        return (self.out_channels == 1 and self.kernel_size == (3, 3) and self.stride == (1, 1) and self.padding == (1, 1)
+                and self.dilation == (1, 1) and self.groups == 1 and self.bias is not None and self.padding_mode == "zeros")
+
+    def forward(self, x):
+        if self._native():
+            return ops.conv2d_c1_relu(x, self.weight, self.bias)
+        if not ALLOW_FALLBACK:
+            raise RuntimeError(f"HipConv2dC1({self.in_channels}->{self.out_channels}, k={self.kernel_size}) is outside the native "
+                               "kernels; set ECM_ALLOW_FALLBACK=1 to run it on PyTorch-ROCm's own convolution instead")
+        SLOW_PATH_EVENTS.append(("miopen_conv2d", self.in_channels, self.out_channels, self.kernel_size))
+        return F.relu(super().forward(x))
+
+
+def _cat_shared(x, shared, nh):
+    """cat([x, shared repeated over the nh heads], 1) for x [nh*B,C,h,w] and shared [B,C',h,w]: the shared map enters as an
+    expanded view (the cat writes those channels anyway); autograd sums its nh gradients in a fixed order."""
+    B = shared.shape[0]
+    x5 = x.view(nh, B, *x.shape[1:])
+    return torch.cat([x5, shared.unsqueeze(0).expand(nh, *shared.shape)], 2).view(nh * B, -1, *x.shape[-2:])
+
+
+class super_resolution_refinement(nn.Module):
+    """cmf.py:227-264.  forward(preds [NH,B,h,w], rgb [B,3,4h,4w], refimg_fea [B,32,h,w], half [B,32,2h,2w]) ->
+    [NH,B,1,4h,4w].  The reference calls the module once per head with the same rgb / features (cmf.py:437,442,447); here the
+    NH heads are ONE pass over an NH*B batch (shared weights, per-sample GroupNorm: the same result), rgb_fea(rgb) is
+    computed once, and the shared maps join the concatenations as expanded views."""
+
+    def __init__(self, dis_planes=32, twice_times=2):
+        super().__init__()
+        self.twice_times = twice_times
+        self.conv1 = nn.Sequential(convbn(1, dis_planes * 2, 3, 1, 1, 1), nn.ReLU(inplace=True))
+        self.deconv_module_list = nn.ModuleList([nn.Sequential(
+            HipConvTranspose2d(dis_planes * 3, dis_planes * 2, 3, 2, 1, 1),
+            HipGroupNorm(NUM_GROUPS, dis_planes * 2), nn.ReLU(inplace=True)) for _ in range(twice_times)])
+        self.rgb_fea = nn.Sequential(
+            convbn(3, dis_planes, 3, 1, 1, 1), nn.ReLU(inplace=True),
+            convbn(dis_planes, dis_planes, 3, 1, 1, 1), nn.ReLU(inplace=True),
+            convbn(dis_planes, dis_planes, 3, 1, 1, 1), nn.ReLU(inplace=True))
+        self.conv2 = nn.Sequential(convbn(dis_planes * 3, dis_planes * 3, 3, 1, 1, 1), nn.ReLU(inplace=True))
+        self.conv_out = HipConv2dC1(dis_planes * 3, 1, 3, 1, 1)
+        self.crap = HipReLU(inplace=True)                  # fused into conv_out
+
+    def forward(self, preds, rgb, *rgb_zoom_feature):
+        if len(rgb_zoom_feature) != self.twice_times:
+            raise ValueError(f"super_resolution_refinement: {self.twice_times} zoom features expected, got {len(rgb_zoom_feature)}")
+        NH, B, h, w = preds.shape
+        f = 2 ** self.twice_times
+        want = [(B, h * 2 ** i, w * 2 ** i) for i in range(self.twice_times)]
+        got = [(t.shape[0], t.shape[-2], t.shape[-1]) for t in rgb_zoom_feature]
+        if got != want or rgb.shape[0] != B or tuple(rgb.shape[-2:]) != (h * f, w * f):
+            raise ValueError(f"super_resolution_refinement: preds {tuple(preds.shape)}, rgb {tuple(rgb.shape)}, zoom features "
+                             f"{[tuple(t.shape) for t in rgb_zoom_feature]}: each map must be twice the size of the previous one")
+        x = _seq_fused(self.conv1, preds.reshape(NH * B, 1, h, w))                 # cmf.py:258
+        for dec, skip in zip(self.deconv_module_list, rgb_zoom_feature):            # cmf.py:259-260
+            x = dec[1].fused(dec[0](_cat_shared(x, skip, NH)), None, True)
+        x = _cat_shared(x, _seq_fused(self.rgb_fea, rgb), NH)                      # cmf.py:262
+        x = self.conv_out(_seq_fused(self.conv2, x))                               # cmf.py:263-264 (+ crap)
+        return x.view(NH, B, 1, h * f, w * f)
+
+
+class cmf(_ECMNet):
+    """cmf.py:267-450.  forward(left, right) -> (pred1, pred2, pred3), each [B,1,H,W]: the cmfsm 3-D stack and accumulated
+    soft-argmin heads on the 1/4-resolution cost volume, each head's quarter-resolution disparity refined to full resolution by
+    the shared super_resolution_refinement decoder.  H and W must be multiples of 4 (the decoder doubles 1/4 -> 1/2 -> 1)."""
+    ENCODER, HOURGLASSES, HEAD = "cmf", 3, "srr"
+
+    def __init__(self, maxdisp=192):
+        super().__init__(maxdisp)
+        self.srr = super_resolution_refinement(32, 2)
+        for m in self.srr.modules():                                   # cmf.py:377-392 (ConvTranspose2d and biases: default)
+            if isinstance(m, nn.Conv2d):
+                m.weight.data.normal_(0, math.sqrt(2.0 / (m.kernel_size[0] * m.kernel_size[1] * m.out_channels)))
+
+    def hot_path(self, lr_l, lr_r, left, half):
+        """Cost volume -> dres0/1 -> three hourglasses -> accumulated heads (cmf.py:394-436) -> decoder (cmf.py:437-449)."""
+        cost0 = _costvol_dres0(self.dres0, lr_l, lr_r, self.maxdisp // 4)
+        cost0 = _cbn(self.dres0[2], cost0, relu=True)
+        y, cost0 = _cbn(self.dres1[0], cost0, relu=True, fork=True)
+        cost0 = _cbn(self.dres1[2], y, skip=cost0)
+        c_forks = ops.fork(cost0, 4)
+        heads, x, pre1, post = [], c_forks[0], None, None
+        for i in range(3):                                             # dres4(out2, pre1, post2): cmf.py:413
+            out, pre, post = getattr(self, f"dres{i + 2}")(x, pre1, post, residual=c_forks[i + 1])
+            if i == 0:
+                pre1 = pre
+            clf = getattr(self, f"classif{i + 1}")
+            if i < 2:
+                c_i, out = _classifier(clf, out, fork=True)
+            else:
+                c_i = _classifier(clf, out)
+            x = out
+            heads.append(c_i)
+        disp = ops.softargmin_heads(torch.stack(heads, 0))            # [3,B,h,w], quarter-resolution units
+        preds = self.srr(disp, left, lr_l, half)
+        return preds[0], preds[1], preds[2]
+
+    def forward(self, left, right):
+        H, W = left.shape[-2:]
+        if H % 4 or W % 4 or tuple(right.shape) != tuple(left.shape):
+            raise ValueError(f"cmf: left {tuple(left.shape)}, right {tuple(right.shape)}: H and W must be multiples of 4 (the "
+                             "decoder doubles 1/4 -> 1/2 -> 1) and both images the same size")
+        B = left.shape[0]
+        if torch.is_grad_enabled():
+            ops.pace_side_streams()
+        lr, _, half = self.feature_extraction(torch.cat([left, right], 0), head=B)   # one encoder pass for both images
+        return self.hot_path(lr[:B], lr[B:], left, half)
+
+
 _MODELS = {"cmfsm": cmfsm, "cmfsm_sub_8": cmfsm_sub_8, "cmfsm_sub_16": cmfsm_sub_16, "cm_sub_4": cm_sub_4,
            "cm_sub_8": cm_sub_8, "cm_sub_16": cm_sub_16, "bilinear_cmf": bilinear_cmf,
-           "bilinear_cmf_sub_8": bilinear_cmf_sub_8, "bilinear_cmf_sub_16": bilinear_cmf_sub_16}
+           "bilinear_cmf_sub_8": bilinear_cmf_sub_8, "bilinear_cmf_sub_16": bilinear_cmf_sub_16, "cmf": cmf}
 
 
 

@@ -887,7 +887,7 @@ def _cached_pack(w, kind, build):
 
 # (kh, kw, stride, dil) -> output-channel tilings (tiles of 32 per workgroup) the kernels are instantiated for; mirrors the
 # COTS masks of csrc/conv2d_case_*.hip and the tiling rule c2_plan() of csrc/conv2d_kernel.h
-_C2_CASES = {(3, 3, 1, 1): {1, 2, 3, 4}, (3, 3, 1, 2): {2, 4}, (3, 3, 1, 4): {4}, (3, 3, 2, 1): {1, 2, 4},
+_C2_CASES = {(3, 3, 1, 1): {1, 2, 3, 4}, (3, 3, 1, 2): {2, 4}, (3, 3, 1, 4): {4}, (3, 3, 2, 1): {1, 2, 3, 4},
              (3, 5, 1, 1): {1, 3}, (1, 1, 1, 1): {1, 2, 4}, (1, 1, 2, 1): {1, 2, 4}}
 
 
@@ -1111,6 +1111,113 @@ class Deconv3dK3S2(torch.autograd.Function):
 
 def deconv3d_k3s2(x, w):
     return Deconv3dK3S2.apply(x, w)
+
+
+# ---- cmf decoder (super_resolution_refinement, cmf.py:227-264) --------------------------------------------------------------
+def channel_sum(x):
+    """[B,C,...] -> [C]: sum over everything but the channel axis in a fixed order (the bias gradient of a layer; no atomics)."""
+    _chk(x)
+    x = _c(x)
+    B, Cc = x.shape[0], x.shape[1]
+    HW = x.numel() // max(B * Cc, 1)
+    out = torch.empty(Cc, device=x.device, dtype=x.dtype)
+    nb = _lib.query("ecm_channel_sum_scratch_bytes", B, Cc, C.c_longlong(HW))
+    scratch = _scratch(nb, x.device)
+    _lib.call("ecm_channel_sum", _p(x), _p(out), _p(scratch), C.c_longlong(nb), B, Cc, C.c_longlong(HW), _stream())
+    return out
+
+
+class Deconv2dK3S2Bias(torch.autograd.Function):
+    """nn.ConvTranspose2d(Ci, Co, 3, stride 2, pad 1, output_padding 1, bias=True) (cmf.py:236-239): forward with the bias in
+    the kernel's epilogue; data gradient = the stride-2 3x3 Conv2d of gy with the weight read as a Conv2d [Ci,Co,3,3] (COT-3
+    case for Ci = 96); weight gradient = the 2-D conv-wgrad with the roles of x and gy exchanged; bias gradient =
+    channel_sum(gy)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        _chk(x, w, b)
+        _need(x.dim() == 4 and w.dim() == 4 and tuple(w.shape[2:]) == (3, 3) and w.shape[0] == x.shape[1] and x.numel() > 0
+              and b.dim() == 1 and b.shape[0] == w.shape[1] and w.shape[1] <= 64 and x.shape[1] % 4 == 0,
+              lambda: f"deconv2d_k3s2_bias: x {tuple(x.shape)}, w {tuple(w.shape)}, b {tuple(b.shape)}: want [B,Ci,H,W], "
+                      "ConvTranspose2d's [Ci,Co<=64,3,3] with Ci % 4 == 0 and [Co]")
+        x, w, b = _c(x), _c(w), _c(b)
+        B, Ci, H, W = x.shape
+        Co = w.shape[1]
+
+        def build():
+            packed = torch.empty(9 * Ci * ((Co + 31) // 32) * 32, device=w.device, dtype=w.dtype)
+            _lib.call("ecm_deconv2d_pack_weight", _p(w), _p(packed), Ci, Co, _stream())
+            return packed
+        y = torch.empty(B, Co, 2 * H, 2 * W, device=x.device, dtype=x.dtype)
+        _lib.call("ecm_deconv2d_k3s2_bias_fwd", _p(x), _p(_cached_pack(w, "d2b", build)), _p(b), _p(y), B, Ci, Co, H, W, 2 * H,
+                  2 * W, _stream())
+        ctx.save_for_backward(x, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        gy = _c(gy)
+        B, Ci, H, W = x.shape
+        Co, Ho, Wo = w.shape[1], 2 * H, 2 * W
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            # gx[ci,i] = sum_{co,k} gy[co,2i+k-1] w[ci,co,k]: a Conv2d(Co -> Ci, stride 2, pad 1) with weight [Ci,Co,3,3]
+            gx = _conv2d_run(gy, _pack2d(w, False), Ci, 3, 3, 2, 1, 1, 1, H, W)
+        if ctx.needs_input_grad[1]:
+            # gw[ci,co,k] = sum x[ci,i] gy[co,2i+k-1]: the conv-wgrad with x := gy, gy := x, "Co" := Ci, "Ci" := Co
+            gw = _empty_like(w)
+            nb = _lib.query("ecm_conv2d_wgrad_ex_scratch_bytes", B, Co, Ci, H, W, 3, 3, 2)
+            scratch = _scratch(nb, x.device)
+            _lib.call("ecm_conv2d_wgrad_ex", _p(gy), _p(x), _p(gw), _p(scratch), C.c_longlong(nb), B, Co, Ci, Ho, Wo, 3, 3, 2, 1,
+                      1, 1, H, W, _stream())
+        if ctx.needs_input_grad[2]:
+            gb = channel_sum(gy)
+        return gx, gw, gb
+
+
+def deconv2d_k3s2_bias(x, w, b):
+    return Deconv2dK3S2Bias.apply(x, w, b)
+
+
+class Conv2dC1Relu(torch.autograd.Function):
+    """relu(nn.Conv2d(Ci, 1, 3, 1, 1, bias=True)(x)) (cmf.py:259-264, conv_out + crap) on csrc/conv2d_c1.hip: forward with
+    bias and ReLU fused, data gradient with the ReLU mask applied, weight and bias gradient in one deterministic pass."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        _chk(x, w, b)
+        _need(x.dim() == 4 and tuple(w.shape) == (1, x.shape[1], 3, 3) and b.numel() == 1 and x.numel() > 0,
+              lambda: f"conv2d_c1_relu: x {tuple(x.shape)}, w {tuple(w.shape)}, b {tuple(b.shape)}: want [B,Ci,H,W], "
+                      "[1,Ci,3,3] and [1]")
+        x, w, b = _c(x), _c(w), _c(b)
+        B, Ci, H, W = x.shape
+        y = torch.empty(B, 1, H, W, device=x.device, dtype=x.dtype)
+        _lib.call("ecm_conv2d_c1_fwd", _p(x), _p(w), _p(b), _p(y), B, Ci, H, W, _stream())
+        ctx.save_for_backward(x, w, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w, y = ctx.saved_tensors
+        gy = _c(gy)
+        B, Ci, H, W = x.shape
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            _lib.call("ecm_conv2d_c1_dgrad", _p(gy), _p(y), _p(w), _p(gx), B, Ci, H, W, _stream())
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            gw = _empty_like(w)
+            gb = torch.empty(1, device=x.device, dtype=x.dtype)
+            nb = _lib.query("ecm_conv2d_c1_wgrad_scratch_bytes", B, Ci, H, W)
+            scratch = _scratch(nb, x.device)
+            _lib.call("ecm_conv2d_c1_wgrad", _p(x), _p(gy), _p(y), _p(gw), _p(gb), _p(scratch), C.c_longlong(nb), B, Ci, H, W,
+                      _stream())
+        return gx, gw, gb
+
+
+def conv2d_c1_relu(x, w, b):
+    return Conv2dC1Relu.apply(x, w, b)
 
 
 # Exchange memory of the one-pass GroupNorm kernels (cluster slots, ticket counter, per-span counters): kept per (device,

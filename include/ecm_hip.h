@@ -223,6 +223,27 @@ int ecm_deconv2d_pack_weight(const float* w, float* packed, int Ci, int Co, void
 int ecm_deconv2d_k3s2_fwd(const float* x, const float* wpacked, float* y, int B, int Ci, int Co, int H, int W, int Ho, int Wo,
                           void* stream);
 
+/* ---- cmf decoder, super_resolution_refinement (cmf.py:227-264) ----------------------------------------------------------
+ * ConvTranspose2d(Ci, Co, 3, stride 2, pad 1, output_padding 1, bias=True) (deconv_module_list.i.0, cmf.py:236-239): the
+ * kernel of ecm_deconv2d_k3s2_fwd with bias[co] added in its epilogue.  w: the ConvTranspose2d weight [Ci,Co,3,3], packed by
+ * ecm_deconv2d_pack_weight(w, packed, Ci, Co); bias [Co].  Co <= 64, Ci % 4 == 0, Ho in {2H-1, 2H}. */
+int ecm_deconv2d_k3s2_bias_fwd(const float* x, const float* wpacked, const float* bias, float* y, int B, int Ci, int Co, int H,
+                               int W, int Ho, int Wo, void* stream);
+/* out[c] = sum_{b,p} x[b,c,p] over x [B,C,HW]: the bias gradient of a layer whose output gradient is x.  Fixed-order partial
+ * sums (no atomics): bit-reproducible.  scratch >= ecm_channel_sum_scratch_bytes(B, C, HW). */
+long long ecm_channel_sum_scratch_bytes(int B, int C, long long HW);
+int ecm_channel_sum(const float* x, float* out, void* scratch, long long scratch_bytes, int B, int C, long long HW, void* stream);
+/* conv_out + crap (cmf.py:259-264): y = relu(Conv2d(Ci -> 1, 3x3, pad 1, bias)(x)), x [B,Ci,H,W] -> y [B,1,H,W].
+ * w: the reference weight [1,Ci,3,3] as it stands (no packing), bias [1].
+ * dgrad: gx [B,Ci,H,W] from gy [B,1,H,W] masked by the forward output y (> 0).
+ * wgrad: gw [1,Ci,3,3] and gb [1] from x, gy and y; fixed-order reductions, bit-reproducible;
+ *        scratch >= ecm_conv2d_c1_wgrad_scratch_bytes(...). */
+int ecm_conv2d_c1_fwd(const float* x, const float* w, const float* bias, float* y, int B, int Ci, int H, int W, void* stream);
+int ecm_conv2d_c1_dgrad(const float* gy, const float* y, const float* w, float* gx, int B, int Ci, int H, int W, void* stream);
+long long ecm_conv2d_c1_wgrad_scratch_bytes(int B, int Ci, int H, int W);
+int ecm_conv2d_c1_wgrad(const float* x, const float* gy, const float* y, float* gw, float* gb, void* scratch,
+                        long long scratch_bytes, int B, int Ci, int H, int W, void* stream);
+
 /* GroupNorm(32 groups, eps) over [B,C,S] (S = D*H*W), cmfsm.py:58; deterministic fixed-order reductions.
  * scratch for every call: >= ecm_gn3d_scratch_bytes(B,C,S).
  * fwd: y = relu?( (x-mean)*rstd*gamma[c]+beta[c] (+ skip) ) (skip may be NULL) and mean_rstd [B,32,2] in ONE pass over x

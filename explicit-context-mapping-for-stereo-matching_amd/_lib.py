@@ -98,6 +98,14 @@ PROTOTYPES = {
     "ecm_gn3d_cluster_preset": (_I, [_P, _LL, _P]),
     "ecm_gn3d_fwd_p": (_I, [_P] * 7 + [_LL, _P, _LL, _I, _I, _LL, _I, _F, _P]),
     "ecm_gn3d_bwd_p": (_I, [_P] * 11 + [_LL, _P, _LL, _I, _I, _LL, _I, _P]),
+    "ecm_conv3d_bf16_packed_elems": (_LL, [_I, _I]),
+    "ecm_conv3d_bf16_pack_weight": (_I, [_P, _P, _I, _I, _I, _P]),
+    "ecm_conv3d_k3_bf16_fwd": (_I, [_P, _P, _P] + [_I] * 7 + [_P]),
+    "ecm_deconv3d_k3s2_bf16_fwd": (_I, [_P, _P, _P] + [_I] * 6 + [_P]),
+    "ecm_gn3d_stats_bf16": (_I, [_P, _P, _P, _LL, _I, _I, _LL, _F, _P]),
+    "ecm_gn3d_apply_bf16": (_I, [_P] * 6 + [_I, _I, _LL, _I, _P]),
+    "ecm_gn3d_apply_f32_bf16": (_I, [_P] * 6 + [_I, _I, _LL, _I, _P]),
+    "ecm_conv3d_c1_gn_fwd_bf16": (_I, [_P] * 6 + [_I, _I, _I, _I, _I, _P]),
 }
 
 _lib = None

@@ -43,8 +43,9 @@ __device__ __forceinline__ int v_slot(int dz, int hy, int wx) { return ((dz * VH
 // stand-alone GroupNorm kernel would have written -- and positions outside the volume stay 0 (the convolution pads h, not x).
 // The normalised tensor (849 MB per head at batch 4) is then never written or read: one read pass of x for the statistics
 // (ecm_gn3d_stats) replaces the GroupNorm kernel's read + write.  Ci == 32 only (one channel per group).
-template <bool GN>
-__global__ __launch_bounds__(256, 2) void conv3d_c1_fwd_v(const float* __restrict__ x, const float* __restrict__ w,
+// T = unsigned short: x is a bf16 volume (the bf16 inference path, ecm_conv3d_c1_gn_fwd_bf16), widened to fp32 as it is staged.
+template <bool GN, class T = float>
+__global__ __launch_bounds__(256, 2) void conv3d_c1_fwd_v(const T* __restrict__ x, const float* __restrict__ w,
                                                           float* __restrict__ y, int Ci, int D, int H, int W, int tiles_d,
                                                           int tiles_h, int tiles_w, const float* __restrict__ mean_rstd,
                                                           const float* __restrict__ gamma, const float* __restrict__ beta) {
@@ -78,20 +79,25 @@ __global__ __launch_bounds__(256, 2) void conv3d_c1_fwd_v(const float* __restric
         const int dz = p / (VH_H * VH_W), r = p - dz * (VH_H * VH_W), hy = r / VH_W, wx = r - hy * VH_W;
         const int gz = d0 - 1 + dz, gy = h0 - 1 + hy, gx = w0 - 1 + wx;
         const bool ok = p < VPOS && (unsigned)gz < (unsigned)D && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
-        goff[k] = ok ? (unsigned)(((size_t)gz * H + gy) * W + gx) * 4u : 0x80000000u;
+        goff[k] = ok ? (unsigned)(((size_t)gz * H + gy) * W + gx) * (unsigned)sizeof(T) : 0x80000000u;
         lslot[k] = p < VPOS ? v_slot(dz, hy, wx) * 4 : (V_X_FLOATS + V_W_FLOATS) * 4;   // bytes; past the end: a scratch slot nobody reads
         asm volatile("" : "+v"(goff[k]), "+v"(lslot[k]));   // keep them in registers: recomputing costs more than the pk_fmas
     }
-    const auto xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x) + (size_t)b * Ci * DHW, 0,
-                                                      (unsigned)((size_t)Ci * DHW * 4), 0x00020000);
-    const unsigned cstride = (unsigned)(DHW * 4);
+    const auto xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(x) + (size_t)b * Ci * DHW, 0,
+                                                      (unsigned)((size_t)Ci * DHW * sizeof(T)), 0x00020000);
+    const unsigned cstride = (unsigned)(DHW * sizeof(T));
     f32x2 rr[VSLOTS];                                        // (channel 2p, channel 2p+1) of a halo position: one ds_write_b64
     auto fetch = [&](int pair) {
         const unsigned s0 = (unsigned)(2 * pair) * cstride;
 #pragma unroll
         for (int k = 0; k < VSLOTS; ++k) {
-            rr[k].x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, goff[k], s0, 0));
-            rr[k].y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, goff[k], s0 + cstride, 0));
+            if constexpr (sizeof(T) == 4) {
+                rr[k].x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, goff[k], s0, 0));
+                rr[k].y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, goff[k], s0 + cstride, 0));
+            } else {                                         // bf16 bits -> the high half of an fp32
+                rr[k].x = __builtin_bit_cast(float, (unsigned)__builtin_amdgcn_raw_buffer_load_b16(xr, goff[k], s0, 0) << 16);
+                rr[k].y = __builtin_bit_cast(float, (unsigned)__builtin_amdgcn_raw_buffer_load_b16(xr, goff[k], s0 + cstride, 0) << 16);
+            }
         }
     };
     fetch(0);
@@ -531,15 +537,15 @@ inline long long c1_tiles(int B, int D, int H, int W) {
 }  // namespace
 
 namespace {
-template <bool GN>
-int launch_c1_fwd_v(const float* x, const float* w, float* y, int B, int Ci, int D, int H, int W, const float* mean_rstd,
+template <bool GN, class T = float>
+int launch_c1_fwd_v(const T* x, const float* w, float* y, int B, int Ci, int D, int H, int W, const float* mean_rstd,
                     const float* gamma, const float* beta, void* stream) {
     const int td = (D + VT_D - 1) / VT_D, th = (H + VT_H - 1) / VT_H, tw = (W + VT_W - 1) / VT_W;
     const long long nb = (long long)B * td * th * tw;
     if (nb > 0x7fffffffLL) return ECM_EUNSUP;
-    const hipError_t e = ecm_allow_lds(reinterpret_cast<const void*>(conv3d_c1_fwd_v<GN>), V_LDS_BYTES);
+    const hipError_t e = ecm_allow_lds(reinterpret_cast<const void*>(conv3d_c1_fwd_v<GN, T>), V_LDS_BYTES);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(conv3d_c1_fwd_v<GN>, dim3((unsigned)nb), dim3(256), V_LDS_BYTES, ecm_stream(stream), x, w, y, Ci, D, H, W, td,
+    hipLaunchKernelGGL((conv3d_c1_fwd_v<GN, T>), dim3((unsigned)nb), dim3(256), V_LDS_BYTES, ecm_stream(stream), x, w, y, Ci, D, H, W, td,
                        th, tw, mean_rstd, gamma, beta);
     return ECM_LAUNCH_RESULT();
 }
@@ -550,6 +556,13 @@ extern "C" int ecm_conv3d_c1_gn_fwd(const float* x, const float* mean_rstd, cons
     ECM_CHECK_ARG(x && mean_rstd && gamma && beta && w && y && B > 0 && D > 0 && H > 0 && W > 0);
     if (Ci != 32 || (long long)D * H * W * 4 * 32 >= 0x7fffffffLL) return ECM_EUNSUP;      // one channel per GroupNorm group
     return launch_c1_fwd_v<true>(x, w, y, B, Ci, D, H, W, mean_rstd, gamma, beta, stream);
+}
+
+extern "C" int ecm_conv3d_c1_gn_fwd_bf16(const unsigned short* x, const float* mean_rstd, const float* gamma, const float* beta,
+                                         const float* w, float* y, int B, int Ci, int D, int H, int W, void* stream) {
+    ECM_CHECK_ARG(x && mean_rstd && gamma && beta && w && y && B > 0 && D > 0 && H > 0 && W > 0);
+    if (Ci != 32 || (long long)D * H * W * 2 * 32 >= 0x7fffffffLL) return ECM_EUNSUP;
+    return launch_c1_fwd_v<true, unsigned short>(x, w, y, B, Ci, D, H, W, mean_rstd, gamma, beta, stream);
 }
 
 extern "C" int ecm_conv3d_c1_fwd(const float* x, const float* w, float* y, int B, int Ci, int D, int H, int W, void* stream) {

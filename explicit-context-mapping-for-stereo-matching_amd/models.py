@@ -69,7 +69,9 @@ class HipGroupNorm(nn.GroupNorm):
     def forward(self, x):
         return ops.group_norm_act(x, self.weight, self.bias, None, False)
 
-    def fused(self, x, skip=None, relu=False, head=0):
+    def fused(self, x, skip=None, relu=False, head=0, out_dtype=None):
+        if out_dtype is not None:                  # the boundary into the bf16 aggregation region (_costvol_dres0)
+            return ops.group_norm_act(x, self.weight, self.bias, skip, relu, head, out_dtype)
         return ops.group_norm_act(x, self.weight, self.bias, skip, relu, head)
 
 
@@ -155,11 +157,17 @@ def _costvol_dres0(dres0, lr_l, lr_r, ndisp):
     """Cost-volume build + dres0's first convbn_3d + ReLU (cmfsm.py:667-684) as one op: the reference-image half of the
     concat volume is constant along d, so its part of the convolution is a class-indexed set of 2-D convolutions of the
     feature map and only the shifted target-image half is materialised (ops.costvol_conv3d).  `ops.cost_volume` is the
-    stand-alone builder of the full [B,2C,D,h,w] tensor (kept for the drop-in boundary and the microbench)."""
+    stand-alone builder of the full [B,2C,D,h,w] tensor (kept for the drop-in boundary and the microbench).
+    Inside ops.aggregation_dtype(torch.bfloat16) the GroupNorm + ReLU writes bf16: the 3-D stack from here to the
+    classifiers' 32 -> 1 layers then runs on the bf16 kernels (the ops dispatch on the volume's dtype)."""
     conv, gn = dres0[0][0], dres0[0][1]
+    out_dtype = None
+    if ops.aggregation_bf16():
+        ops._agg_grad_guard("the bf16 aggregation stack")           # before the first 3-D launch
+        out_dtype = torch.bfloat16
     if EXPLICIT_COST_VOLUME:
-        return gn.fused(conv(ops.cost_volume(lr_l, lr_r, ndisp)), None, True)
-    return gn.fused(ops.costvol_conv3d(lr_l, lr_r, conv.weight, ndisp), None, True)
+        return gn.fused(conv(ops.cost_volume(lr_l, lr_r, ndisp)), None, True, out_dtype=out_dtype)
+    return gn.fused(ops.costvol_conv3d(lr_l, lr_r, conv.weight, ndisp), None, True, out_dtype=out_dtype)
 
 
 def _cbn(seq, x, skip=None, relu=False, fork=False):
@@ -184,7 +192,7 @@ def _classifier(clf, x, fork=False):
         y, xs = conv(x, fork=True)
     else:
         y, xs = conv(x), None
-    if C1_GN_FUSE and y.is_cuda and tuple(last.weight.shape) == (1, 32, 3, 3, 3):
+    if y.dtype == torch.bfloat16 or (C1_GN_FUSE and y.is_cuda and tuple(last.weight.shape) == (1, 32, 3, 3, 3)):   # bf16: the tail only
         out = ops.classifier_tail(y, gn.weight, gn.bias, last.weight).squeeze(1)
     else:
         out = last(gn.fused(y, None, True)).squeeze(1)

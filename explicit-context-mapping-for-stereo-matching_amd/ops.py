@@ -88,6 +88,7 @@ class CostVolumeConcat(torch.autograd.Function):
 
 
 def cost_volume(left, right, ndisp):
+    _agg_grad_guard("cost_volume")
     return CostVolumeConcat.apply(left, right, int(ndisp))
 
 
@@ -152,6 +153,7 @@ def costvol_conv3d(left, right, weight, ndisp):
     halves of the concat volume are constant along a line in (d, x), so the 3x3x3 convolution collapses to class-indexed
     2-D convolutions of the two feature maps (3x3 on `left`, sheared 3x5 on `right`) -- see csrc/costvol_conv.hip.
     weight: [Co, 2C, 3, 3, 3] (the reference's dres0[0][0].weight)."""
+    _agg_grad_guard("costvol_conv3d")
     _need(left.dim() == 4 and right.shape == left.shape and weight.dim() == 5,
           lambda: f"costvol_conv3d: left {tuple(left.shape)}, right {tuple(right.shape)}, weight {tuple(weight.shape)}")
     Cc = left.shape[1]
@@ -1077,7 +1079,11 @@ def conv2d_planes(x, w, fork=False):
 
 
 def conv3d_k3(x, w, stride=1, fork=False):
-    """fork=True: returns (y, x') with x' a view of x to be used as the skip operand (see _fork_out)."""
+    """fork=True: returns (y, x') with x' a view of x to be used as the skip operand (see _fork_out).
+    A bf16 x runs the bf16 inference kernel (see aggregation_dtype)."""
+    if x.dtype == torch.bfloat16:
+        return _conv3d_bf16(x, w, int(stride), bool(fork))
+    _agg_grad_guard("conv3d_k3")
     return Conv3dK3.apply(x, w, int(stride), bool(fork), torch.is_grad_enabled())
 
 
@@ -1110,6 +1116,9 @@ class Deconv3dK3S2(torch.autograd.Function):
 
 
 def deconv3d_k3s2(x, w):
+    if x.dtype == torch.bfloat16:
+        return _deconv3d_bf16(x, w)
+    _agg_grad_guard("deconv3d_k3s2")
     return Deconv3dK3S2.apply(x, w)
 
 
@@ -1387,7 +1396,10 @@ class ClassifierTail(torch.autograd.Function):
 
 
 def classifier_tail(x, gamma, beta, w):
-    """relu(GroupNorm32(x)) -> Conv3d(32 -> 1): see ClassifierTail."""
+    """relu(GroupNorm32(x)) -> Conv3d(32 -> 1): see ClassifierTail.  A bf16 x gives the same fp32 logits from the bf16 volume."""
+    if x.dtype == torch.bfloat16:
+        return _classifier_tail_bf16(x, gamma, beta, w)
+    _agg_grad_guard("classifier_tail")
     return ClassifierTail.apply(x, gamma, beta, w)
 
 
@@ -1527,8 +1539,13 @@ def stereo_loss3(preds, gt, maxdisp=192, weights=(0.5, 0.7, 1.0)):
     return StereoLoss3.apply(p1, p2, p3, gt, float(maxdisp), *map(float, weights))
 
 
-def group_norm_act(x, gamma, beta, skip=None, relu=False, head=0):
-    """head > 0: returns (y, x[:head]) -- see GroupNormAct.forward."""
+def group_norm_act(x, gamma, beta, skip=None, relu=False, head=0, out_dtype=None):
+    """head > 0: returns (y, x[:head]) -- see GroupNormAct.forward.  A bf16 x, or out_dtype=torch.bfloat16 (the boundary into
+    the bf16 region: fp32 x), runs the bf16 inference kernels and returns a bf16 y (see aggregation_dtype)."""
+    if x.dtype == torch.bfloat16 or out_dtype == torch.bfloat16:
+        _need(not head, "group_norm_act: the bf16 form takes no head fork")
+        return _group_norm_bf16(x, gamma, beta, skip, bool(relu))
+    _need(out_dtype in (None, torch.float32), lambda: f"group_norm_act: out_dtype {out_dtype}: float32 or bfloat16")
     _need(0 <= int(head) <= x.shape[0], lambda: f"group_norm_act: head {head} of a batch of {x.shape[0]}")
     if head and not (torch.is_grad_enabled() and x.requires_grad):
         return GroupNormAct.apply(x, gamma, beta, skip, bool(relu), 0), x[:head]
@@ -1550,3 +1567,143 @@ def check_async_errors(clear=True):
         _GN_CLUSTER.clear()                    # a timed-out cluster leaves the exchange memory in an unknown state
         msg = _lib.load().ecm_error_string(rc)
         raise RuntimeError(f"asynchronous device-side failure ({rc}): {msg.decode() if msg else '?'}")
+
+
+# ---- opt-in bf16 inference of the 3-D aggregation stack ----------------------------------------------------------------------
+# Inside `with aggregation_dtype(torch.bfloat16):` the models run dres0's second convolution through the classifiers' 32 -> 1
+# layers on bf16 volumes (csrc/bf16_infer.hip: bf16 operands on the matrix cores, fp32 accumulation, one rounding per output).
+# The setting is process-wide like WINOGRAD (nn.DataParallel replicas run in other threads), inference only (nothing here has
+# a backward: a 3-D op reached with grad enabled raises), and the fp32 path outside the block is untouched.  The ops below
+# dispatch on the dtype of the volume; weights stay fp32 parameters, packed to bf16 images per call (cached under
+# frozen_weights() beside the fp32 layouts, under their own keys).
+_AGG_DTYPE = torch.float32
+
+
+@_contextlib.contextmanager
+def aggregation_dtype(dtype):
+    """torch.float32 (the default; a no-op) or torch.bfloat16 for the 3-D aggregation stack inside the block; nests and
+    restores the previous setting on exit.  bf16 is inference only: run the model under torch.no_grad()."""
+    global _AGG_DTYPE
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"aggregation_dtype: {dtype} is not supported (torch.float32 or torch.bfloat16)")
+    prev, _AGG_DTYPE = _AGG_DTYPE, dtype
+    try:
+        yield
+    finally:
+        _AGG_DTYPE = prev
+
+
+def aggregation_bf16():
+    """True inside an aggregation_dtype(torch.bfloat16) block."""
+    return _AGG_DTYPE == torch.bfloat16
+
+
+def _bf16_no_grad(what):
+    if torch.is_grad_enabled():
+        raise RuntimeError(f"{what}: bf16 aggregation has no backward (inference only); run the model under torch.no_grad() "
+                           "or leave the aggregation_dtype(torch.bfloat16) block")
+
+
+def _agg_grad_guard(what):
+    """A 3-D op reached inside a bf16 block with grad enabled raises before it launches anything (no silent fp32 path)."""
+    if _AGG_DTYPE == torch.bfloat16:
+        _bf16_no_grad(what)
+
+
+def _chk_bf16(*ts):
+    for t in ts:
+        if t is not None and (not t.is_cuda or t.dtype != torch.bfloat16):
+            raise RuntimeError(f"ecm bf16 ops take bfloat16 CUDA volumes (got {t.dtype} on {t.device})")
+
+
+def _pack_bf16(w, transposed):
+    """bf16 weight image [Ci/8][28][Co][8] of a Conv3d weight [Co,Ci,3,3,3] or (transposed) a ConvTranspose3d one [Ci,Co,3,3,3]."""
+    Ci, Co = (w.shape[0], w.shape[1]) if transposed else (w.shape[1], w.shape[0])
+
+    def build():
+        wc = _c(w.detach())
+        packed = torch.empty(_lib.query("ecm_conv3d_bf16_packed_elems", Ci, Co), device=w.device, dtype=torch.bfloat16)
+        _lib.call("ecm_conv3d_bf16_pack_weight", _p(wc), _p(packed), Ci, Co, int(transposed), _stream())
+        return packed
+    return _cached_pack(w, "bf16_deconv" if transposed else "bf16_conv", build)
+
+
+def _conv3d_bf16(x, w, stride, fork):
+    _bf16_no_grad("conv3d_k3")
+    _chk_bf16(x)
+    _chk(w)
+    _need(x.dim() == 5 and w.dim() == 5 and tuple(w.shape[2:]) == (3, 3, 3) and w.shape[1] == x.shape[1] and stride in (1, 2)
+          and x.shape[1] in (32, 64) and w.shape[0] in (32, 64) and x.numel() > 0,
+          lambda: f"conv3d_k3 (bf16): x {tuple(x.shape)}, w {tuple(w.shape)}, stride {stride}: want [B,Ci,D,H,W], [Co,Ci,3,3,3] "
+                  "with Ci, Co in {32, 64}, stride 1|2")
+    x = _c(x)
+    B, Ci, D, H, W = x.shape
+    Co = w.shape[0]
+    y = torch.empty(B, Co, (D - 1) // stride + 1, (H - 1) // stride + 1, (W - 1) // stride + 1, device=x.device,
+                    dtype=torch.bfloat16)
+    _lib.call("ecm_conv3d_k3_bf16_fwd", _p(x), _p(_pack_bf16(w, False)), _p(y), B, Ci, Co, D, H, W, stride, _stream())
+    return (y, x) if fork else y
+
+
+def _deconv3d_bf16(x, w):
+    _bf16_no_grad("deconv3d_k3s2")
+    _chk_bf16(x)
+    _chk(w)
+    _need(x.dim() == 5 and w.dim() == 5 and tuple(w.shape[2:]) == (3, 3, 3) and w.shape[0] == x.shape[1]
+          and x.shape[1] in (32, 64) and w.shape[1] in (32, 64) and x.numel() > 0,
+          lambda: f"deconv3d_k3s2 (bf16): x {tuple(x.shape)}, w {tuple(w.shape)}: want [B,Ci,D,H,W] and ConvTranspose3d's "
+                  "[Ci,Co,3,3,3] with Ci, Co in {32, 64}")
+    x = _c(x)
+    B, Ci, D, H, W = x.shape
+    Co = w.shape[1]
+    y = torch.empty(B, Co, 2 * D, 2 * H, 2 * W, device=x.device, dtype=torch.bfloat16)
+    _lib.call("ecm_deconv3d_k3s2_bf16_fwd", _p(x), _p(_pack_bf16(w, True)), _p(y), B, Ci, Co, D, H, W, _stream())
+    return y
+
+
+def _gn_stats_any(x):
+    """GroupNorm(32) statistics [B,32,2] (mean, rstd) of an fp32 or bf16 volume (two-stage kernels)."""
+    B, Cc = x.shape[:2]
+    S = x.numel() // (B * Cc)
+    stats = torch.empty(B, GN_GROUPS, 2, device=x.device, dtype=torch.float32)
+    nb = _lib.query("ecm_gn3d_scratch_bytes", B, Cc, C.c_longlong(S))
+    scratch = _scratch(nb, x.device)
+    name = "ecm_gn3d_stats_bf16" if x.dtype == torch.bfloat16 else "ecm_gn3d_stats"
+    _lib.call(name, _p(x), _p(stats), _p(scratch), C.c_longlong(nb), B, Cc, C.c_longlong(S), C.c_float(GN_EPS), _stream())
+    return stats
+
+
+def _group_norm_bf16(x, gamma, beta, skip, relu):
+    _bf16_no_grad("group_norm_act")
+    if x.dtype != torch.bfloat16:
+        _chk(x)
+    _chk(gamma, beta)
+    _chk_bf16(x if x.dtype == torch.bfloat16 else None, skip)
+    _need(x.dim() >= 3 and x.numel() > 0 and x.shape[1] % GN_GROUPS == 0 and gamma.numel() == x.shape[1] == beta.numel()
+          and (skip is None or skip.shape == x.shape),
+          lambda: f"group_norm_act (bf16): x {tuple(x.shape)}, gamma {tuple(gamma.shape)}, skip "
+                  f"{None if skip is None else tuple(skip.shape)}: {GN_GROUPS} groups over C channels, bf16 skip of x's shape")
+    x, gamma, beta = _c(x), _c(gamma), _c(beta)
+    skip = _c(skip) if skip is not None else None
+    B, Cc = x.shape[:2]
+    S = x.numel() // (B * Cc)
+    stats = _gn_stats_any(x)
+    y = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16)
+    name = "ecm_gn3d_apply_bf16" if x.dtype == torch.bfloat16 else "ecm_gn3d_apply_f32_bf16"
+    _lib.call(name, _p(x), _p(stats), _p(gamma), _p(beta), _p(skip), _p(y), B, Cc, C.c_longlong(S), int(relu), _stream())
+    return y
+
+
+def _classifier_tail_bf16(x, gamma, beta, w):
+    _bf16_no_grad("classifier_tail")
+    _chk_bf16(x)
+    _chk(gamma, beta, w)
+    _need(x.dim() == 5 and x.numel() > 0 and x.shape[1] == 32 and gamma.numel() == 32 == beta.numel()
+          and tuple(w.shape) == (1, 32, 3, 3, 3),
+          lambda: f"classifier_tail (bf16): x {tuple(x.shape)}, gamma {tuple(gamma.shape)}, w {tuple(w.shape)}: 32 -> 1 only")
+    x, gamma, beta, w = _c(x), _c(gamma), _c(beta), _c(w)
+    B, Cc, D, H, W = x.shape
+    stats = _gn_stats_any(x)
+    y = torch.empty(B, 1, D, H, W, device=x.device, dtype=torch.float32)
+    _lib.call("ecm_conv3d_c1_gn_fwd_bf16", _p(x), _p(stats), _p(gamma), _p(beta), _p(w), _p(y), B, Cc, D, H, W, _stream())
+    return y

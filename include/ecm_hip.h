@@ -367,6 +367,35 @@ int ecm_stereo_loss_bwd(const float* p1, const float* p2, const float* p3, const
                         const float* gloss, float* g1, float* g2, float* g3, long long n, float maxdisp,
                         float w1, float w2, float w3, void* stream);
 
+/* ---- opt-in bf16 inference of the 3-D aggregation stack (ops.aggregation_dtype; bf16_infer.hip) ------------------------
+ * Forward only.  Volumes are contiguous bf16 NCDHW (unsigned short = the bf16 bit pattern), weights and GroupNorm
+ * parameters fp32; products accumulate in fp32 and every output is rounded once to bf16 (round to nearest even, NaN stays
+ * NaN).  No atomics: bit-reproducible.
+ * Weight image: [Ci/8][28 tap slots][Co][8] bf16 packed from the fp32 weight -- transposed = 0: Conv3d w [Co,Ci,3,3,3];
+ * transposed = 1: ConvTranspose3d w [Ci,Co,3,3,3] (taps grouped by output phase).  Ci % 8 == 0. */
+long long ecm_conv3d_bf16_packed_elems(int Ci, int Co);
+int ecm_conv3d_bf16_pack_weight(const float* w, unsigned short* packed, int Ci, int Co, int transposed, void* stream);
+/* Conv3d k3 pad 1 stride 1|2, no bias (cmfsm.py:49-58): y [B,Co,Do,Ho,Wo], Do = (D-1)/stride+1.  Ci, Co in {32, 64}. */
+int ecm_conv3d_k3_bf16_fwd(const unsigned short* x, const unsigned short* wpacked, unsigned short* y,
+                           int B, int Ci, int Co, int D, int H, int W, int stride, void* stream);
+/* ConvTranspose3d k3 stride 2 pad 1 output_padding 1, no bias (cmfsm.py:262-268): y [B,Co,2D,2H,2W].  Ci, Co in {32, 64}. */
+int ecm_deconv3d_k3s2_bf16_fwd(const unsigned short* x, const unsigned short* wpacked, unsigned short* y,
+                               int B, int Ci, int Co, int D, int H, int W, void* stream);
+/* GroupNorm(32) statistics of a bf16 volume: mean_rstd [B,32,2] fp32 as ecm_gn3d_stats (same variance formulation);
+ * scratch >= ecm_gn3d_scratch_bytes(B, C, S). */
+int ecm_gn3d_stats_bf16(const unsigned short* x, float* mean_rstd, void* scratch, long long scratch_bytes,
+                        int B, int C, long long S, float eps, void* stream);
+/* y = bf16( relu?( GroupNorm(x)*gamma + beta (+ skip) ) ), skip bf16 or NULL; _f32_bf16: x fp32 (its statistics from
+ * ecm_gn3d_stats) -- the boundary into the bf16 region. */
+int ecm_gn3d_apply_bf16(const unsigned short* x, const float* mean_rstd, const float* gamma, const float* beta,
+                        const unsigned short* skip, unsigned short* y, int B, int C, long long S, int relu, void* stream);
+int ecm_gn3d_apply_f32_bf16(const float* x, const float* mean_rstd, const float* gamma, const float* beta,
+                            const unsigned short* skip, unsigned short* y, int B, int C, long long S, int relu, void* stream);
+/* The classifier tail (ecm_conv3d_c1_gn_fwd) reading a bf16 x: relu(GroupNorm(x)) -> Conv3d(32 -> 1) with fp32 output
+ * y [B,1,D,H,W]; statistics from ecm_gn3d_stats_bf16. */
+int ecm_conv3d_c1_gn_fwd_bf16(const unsigned short* x, const float* mean_rstd, const float* gamma, const float* beta,
+                              const float* w, float* y, int B, int Ci, int D, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

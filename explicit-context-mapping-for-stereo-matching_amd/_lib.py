@@ -106,6 +106,10 @@ PROTOTYPES = {
     "ecm_gn3d_apply_bf16": (_I, [_P] * 6 + [_I, _I, _LL, _I, _P]),
     "ecm_gn3d_apply_f32_bf16": (_I, [_P] * 6 + [_I, _I, _LL, _I, _P]),
     "ecm_conv3d_c1_gn_fwd_bf16": (_I, [_P] * 6 + [_I, _I, _I, _I, _I, _P]),
+    "ecm_conv2d_bf16_packed_elems": (_LL, [_I, _I, _I]),
+    "ecm_conv2d_bf16_pack_weight": (_I, [_P, _P, _I, _I, _I, _P]),
+    "ecm_conv2d_bf16_fwd": (_I, [_P, _P, _P] + [_I] * 9 + [_P]),
+    "ecm_gn3d_apply_bf16_f32": (_I, [_P] * 7 + [_I, _I, _LL, _I, _P]),
 }
 
 _lib = None

@@ -93,8 +93,23 @@ class EncConv2d(nn.Conv2d):
                 and self.dilation[0] == self.dilation[1] and self.padding == (d * (kh - 1) // 2, d * (kw - 1) // 2)
                 and self.padding_mode == "zeros" and ops.conv2d_supported(self.in_channels, self.out_channels, kh, kw, s, d))
 
-    def forward(self, x, fork=False):
-        """fork=True: returns (y, x') -- x' is x for the skip connection (ops._fork_out)."""
+    def _native_bf16(self):
+        kh, kw = self.kernel_size
+        d = self.dilation[0]
+        return (self.groups == 1 and self.bias is None and kh == kw and self.stride[0] == self.stride[1]
+                and self.dilation[0] == self.dilation[1] and self.padding == (d * (kh - 1) // 2, d * (kw - 1) // 2)
+                and self.padding_mode == "zeros" and ops.conv2d_bf16_supported(self.in_channels, self.out_channels, kh, self.stride[0], d))
+
+    def forward(self, x, fork=False, out_dtype=None):
+        """fork=True: returns (y, x') -- x' is x for the skip connection (ops._fork_out).
+        A bf16 x (ops.encoder_dtype) runs the bf16 encoder kernel; out_dtype=torch.float32 writes its result in fp32."""
+        if x.dtype == torch.bfloat16:
+            if not self._native_bf16():
+                raise RuntimeError(
+                    f"EncConv2d({self.in_channels}->{self.out_channels}, k={self.kernel_size}, s={self.stride}, d={self.dilation}) "
+                    "is outside the bf16 encoder kernel (ops.conv2d_bf16_supported); leave the encoder_dtype(torch.bfloat16) block")
+            return ops.conv2d_bf16(x, self.weight, self.stride[0], self.dilation[0], fork,
+                                   torch.bfloat16 if out_dtype is None else out_dtype)
         if x.dim() == 5:       # [B,C,d*d,H/d,W/d]: the phase planes of a dilation-d layer (feature_extraction._run_layer)
             return ops.conv2d_planes(x, self.weight, fork)
         if self._native():     # raises on CPU tensors, like every op
@@ -212,7 +227,9 @@ class BasicBlock(nn.Module):
         self.downsample = downsample
         self.stride = stride
 
-    def forward(self, x):
+    def forward(self, x, dual=False):
+        """dual=True (bf16 encoder, the stage whose output leaves the encoder): returns (fp32 output, its bf16 copy) from one
+        GroupNorm pass."""
         if self.downsample is None:
             # x feeds conv1 AND the residual add: conv1 hands x back so that its data gradient absorbs the skip gradient
             y, x = self.conv1[0][0](x, fork=True)
@@ -220,6 +237,9 @@ class BasicBlock(nn.Module):
         else:
             out = _seq_fused(self.conv1, x)                                # conv + GN + ReLU
             x = _seq_fused(self.downsample, x)
+        if dual:
+            gn = self.conv2[1]
+            return ops.group_norm_act_bf16_f32(self.conv2[0](out), gn.weight, gn.bias, x, False, dual=True)
         return self.conv2[1].fused(self.conv2[0](out), x, False)            # conv + GN + residual add (cmfsm.py:76-85)
 
 
@@ -251,6 +271,8 @@ def bilinear_upsample(x, size):
     small matmuls with the separable interpolation matrices: same values, but the backward is a matmul instead of
     ATen's atomic scatter (2 ms per call at 144x240 from a 2x3 map)."""
     H, W = size
+    if x.dtype == torch.bfloat16:        # bf16 encoder: interpolate in fp32 (weights not rounded), round the result once
+        return bilinear_upsample(x.float(), size).to(torch.bfloat16)
     uy = _interp_matrix(x.shape[-2], H, x.device, x.dtype)
     ux = _interp_matrix(x.shape[-1], W, x.device, x.dtype)
     return torch.matmul(uy, torch.matmul(x, ux.t()))
@@ -324,6 +346,7 @@ class feature_extraction(nn.Module):
             EncConv2d(128, 32, kernel_size=1, padding=0, stride=1, bias=False))
         setattr(self, "lastconv" if cfg["raw"] == "layer2" else "lastconv_16", last)
         self._raw_is_layer3 = cfg["raw"] == "layer3"
+        self._first_tail = cfg["first_tail"]
 
     def _make_layer(self, block, planes, blocks, stride, pad, dilation):
         downsample = None
@@ -340,6 +363,8 @@ class feature_extraction(nn.Module):
     def _run_layer(layer, x):
         """One residual stage.  If every convolution in it is a 3x3 / stride 1 layer of the same dilation d > 1 (cmfsm's
         layer4, cmfsm.py:150), run it on d*d phase planes, where the convolutions are ordinary 3x3 ones (ops.phase_split)."""
+        if x.dtype == torch.bfloat16:     # bf16 encoder: the kernel runs the dilation natively, no phase planes
+            return layer(x)
         convs = [m for m in layer.modules() if isinstance(m, nn.Conv2d)]
         d = convs[0].dilation[0]
         ok = (ops.WINOGRAD and d > 1 and x.shape[-2] % d == 0 and x.shape[-1] % d == 0 and x.shape[-1] // d >= 2
@@ -355,7 +380,10 @@ class feature_extraction(nn.Module):
 
     def forward(self, x, head=None):
         """`head` (extension): the caller only needs the first `head` samples of the full-resolution map (third result); their
-        gradient is then folded into the map's gradient in place (ops.fork_head) instead of through a zero-padded copy."""
+        gradient is then folded into the map's gradient in place (ops.fork_head) instead of through a zero-padded copy.
+        Inside ops.encoder_dtype(torch.bfloat16): _forward_bf16."""
+        if ops.encoder_bf16():
+            return self._forward_bf16(x, head)
         output_all = _seq_fused(self.firstconv, x)
         output_head = None
         if not hasattr(self, "secondconv"):           # cmf.py:197-198: firstconv -> layer1 directly
@@ -384,6 +412,51 @@ class feature_extraction(nn.Module):
         last = self.lastconv_16 if self._raw_is_layer3 else self.lastconv
         feature = _seq_fused(last, torch.cat([output_raw, output_skip] + pyramid, 1))
         return feature, output_rt, (output_all if output_head is None else output_head)
+
+    @staticmethod
+    def _layer_dual(layer, x):
+        """A residual stage whose output is an encoder result: -> (fp32 output, bf16 copy for the next stage)."""
+        blocks = list(layer)
+        for blk in blocks[:-1]:
+            x = blk(x)
+        return blocks[-1](x, dual=True)
+
+    def _forward_bf16(self, x, head=None):
+        """The encoder on bf16 maps (ops.encoder_dtype): the 3 -> 32 stem convolution reads the fp32 image and stays fp32, its
+        GroupNorm + ReLU writes bf16; every later layer runs on the bf16 kernels (a layer outside them raises).  The three
+        results are written in fp32 by the kernel that produces them: the full-resolution map by firstconv's bare last
+        convolution ("conv" variants) or by a GroupNorm that also writes the bf16 copy the next layer reads ("convbn"); layer1's
+        output the same way; the low-resolution feature by lastconv's 1x1.  `head`: a slice of the fp32 map (no autograd)."""
+        ops._enc_no_grad("feature_extraction")                  # before the first launch
+        bf = torch.bfloat16
+        fc = list(self.firstconv)
+        conv0, gn0 = fc[0][0], fc[0][1]
+        h = gn0.fused(conv0(x), None, True, out_dtype=bf)
+        if self._first_tail == "conv":
+            h = _seq_fused(fc[2:-1], h)
+            output_all = fc[-1](h, out_dtype=torch.float32)
+            h = _seq_fused(self.secondconv, self.secondconv[0].fused(output_all, None, True, out_dtype=bf), start=2)
+            output_rt, h = self._layer_dual(self.layer1, h)
+        elif self._first_tail == "convbn":
+            h = _seq_fused(fc[2:-2], h)
+            conv, gn = fc[-2][0], fc[-2][1]
+            output_all, h = ops.group_norm_act_bf16_f32(conv(h), gn.weight, gn.bias, None, True, dual=True)
+            output_rt, h = self._layer_dual(self.layer1, _seq_fused(self.secondconv, h))
+        else:                                                   # "none" (cmf): layer1's output is the map
+            output_rt, h = self._layer_dual(self.layer1, _seq_fused(fc[2:], h))
+            output_all = output_rt
+        output_raw = self.layer2(h)
+        if self._raw_is_layer3:
+            output_raw = self._run_layer(self.layer3, output_raw)
+            output_skip = self._run_layer(self.layer4, output_raw)
+        else:
+            output_skip = self._run_layer(self.layer4, self._run_layer(self.layer3, output_raw))
+        size = output_skip.shape[-2:]
+        pooled = _pyramid_pools(output_skip, [getattr(self, f"branch{i}")[0] for i in (1, 2, 3, 4)])
+        pyramid = [bilinear_upsample(_seq_fused(getattr(self, f"branch{i}"), pooled[i - 1], start=1), size) for i in (4, 3, 2, 1)]
+        last = list(self.lastconv_16 if self._raw_is_layer3 else self.lastconv)
+        feature = last[-1](_seq_fused(last[:-1], torch.cat([output_raw, output_skip] + pyramid, 1)), out_dtype=torch.float32)
+        return feature, output_rt, (output_all if head is None else output_all[:head])
 
 
 # ------------------------------------------------------------------------------------------------

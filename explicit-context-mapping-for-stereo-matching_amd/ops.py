@@ -1707,3 +1707,100 @@ def _classifier_tail_bf16(x, gamma, beta, w):
     y = torch.empty(B, 1, D, H, W, device=x.device, dtype=torch.float32)
     _lib.call("ecm_conv3d_c1_gn_fwd_bf16", _p(x), _p(stats), _p(gamma), _p(beta), _p(w), _p(y), B, Cc, D, H, W, _stream())
     return y
+
+
+# ---- opt-in bf16 inference of the 2-D feature encoder ------------------------------------------------------------------------
+# Inside `with encoder_dtype(torch.bfloat16):` models.feature_extraction runs every layer after the stem convolution on bf16
+# maps (csrc/bf16_encoder.hip: bf16 operands on the matrix cores, fp32 accumulation, one rounding per output); its three
+# results stay fp32.  Independent of aggregation_dtype; process-wide, inference only, and the fp32 path outside the block is
+# untouched.  Weights stay fp32 parameters, packed to bf16 images per call (cached under frozen_weights(), key "bf16_conv2d").
+_ENC_DTYPE = torch.float32
+
+
+@_contextlib.contextmanager
+def encoder_dtype(dtype):
+    """torch.float32 (the default; a no-op) or torch.bfloat16 for the 2-D feature encoder inside the block; nests and
+    restores the previous setting on exit.  bf16 is inference only: run the model under torch.no_grad()."""
+    global _ENC_DTYPE
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"encoder_dtype: {dtype} is not supported (torch.float32 or torch.bfloat16)")
+    prev, _ENC_DTYPE = _ENC_DTYPE, dtype
+    try:
+        yield
+    finally:
+        _ENC_DTYPE = prev
+
+
+def encoder_bf16():
+    """True inside an encoder_dtype(torch.bfloat16) block."""
+    return _ENC_DTYPE == torch.bfloat16
+
+
+def _enc_no_grad(what):
+    if torch.is_grad_enabled():
+        raise RuntimeError(f"{what}: the bf16 encoder has no backward (inference only); run the model under torch.no_grad() "
+                           "or leave the encoder_dtype(torch.bfloat16) block")
+
+
+def conv2d_bf16_supported(Ci, Co, k, stride, dil):
+    """Is this Conv2d(bias=False, padding dil*(k-1)/2) inside the bf16 encoder kernel (csrc/bf16_encoder.hip)?"""
+    if Ci % 16 or Co % 32 or Ci <= 0 or Co <= 0:
+        return False
+    if k == 3:
+        return (stride == 1 and dil in (1, 2, 4)) or (stride == 2 and dil == 1)
+    return k == 1 and stride in (1, 2) and dil == 1
+
+
+def _pack_bf16_2d(w):
+    """bf16 weight image [Ci/16][k*k][Co][16] of a Conv2d weight [Co,Ci,k,k]."""
+    Co, Ci, k = w.shape[0], w.shape[1], w.shape[2]
+
+    def build():
+        wc = _c(w.detach())
+        packed = torch.empty(_lib.query("ecm_conv2d_bf16_packed_elems", Ci, Co, k), device=w.device, dtype=torch.bfloat16)
+        _lib.call("ecm_conv2d_bf16_pack_weight", _p(wc), _p(packed), Ci, Co, k, _stream())
+        return packed
+    return _cached_pack(w, "bf16_conv2d", build)
+
+
+def conv2d_bf16(x, w, stride=1, dil=1, fork=False, out_dtype=torch.bfloat16):
+    """Conv2d(bias=False) of the bf16 encoder on a bf16 x [B,Ci,H,W]: 3x3 (padding = dil; stride 1 with dilation 1|2|4, or
+    stride 2) or 1x1 (stride 1|2).  out_dtype torch.float32: the result leaves the encoder in fp32 (rounded nowhere).
+    fork=True: returns (y, x) -- x for the skip connection (no backward here)."""
+    _enc_no_grad("conv2d_bf16")
+    _chk_bf16(x)
+    _chk(w)
+    _need(x.dim() == 4 and w.dim() == 4 and w.shape[1] == x.shape[1] and w.shape[2] == w.shape[3] and x.numel() > 0
+          and conv2d_bf16_supported(x.shape[1], w.shape[0], w.shape[2], stride, dil) and out_dtype in (torch.bfloat16, torch.float32),
+          lambda: f"conv2d_bf16: x {tuple(x.shape)}, w {tuple(w.shape)}, stride {stride}, dilation {dil}, out {out_dtype}: want "
+                  "[B,Ci,H,W] and [Co,Ci,k,k] with Ci % 16 == 0, Co % 32 == 0, k 3 (stride 1 and dilation 1|2|4, or stride 2) "
+                  "or 1 (stride 1|2)")
+    x = _c(x)
+    B, Ci, H, W = x.shape
+    Co, k = w.shape[0], w.shape[2]
+    y = torch.empty(B, Co, (H - 1) // stride + 1, (W - 1) // stride + 1, device=x.device, dtype=out_dtype)
+    _lib.call("ecm_conv2d_bf16_fwd", _p(x), _p(_pack_bf16_2d(w)), _p(y), B, Ci, Co, H, W, k, int(stride), int(dil),
+              int(out_dtype == torch.float32), _stream())
+    return (y, x) if fork else y
+
+
+def group_norm_act_bf16_f32(x, gamma, beta, skip=None, relu=False, dual=False):
+    """relu?(GroupNorm32(x)*gamma+beta (+ skip)) of a bf16 x written in fp32 -- the encoder's results.  dual=True: returns
+    (y32, y16), the same values also rounded to bf16 in the same pass for the next bf16 layer."""
+    _enc_no_grad("group_norm_act_bf16_f32")
+    _chk_bf16(x, skip)
+    _chk(gamma, beta)
+    _need(x.dim() >= 3 and x.numel() > 0 and x.shape[1] % GN_GROUPS == 0 and gamma.numel() == x.shape[1] == beta.numel()
+          and (skip is None or skip.shape == x.shape),
+          lambda: f"group_norm_act_bf16_f32: x {tuple(x.shape)}, gamma {tuple(gamma.shape)}, skip "
+                  f"{None if skip is None else tuple(skip.shape)}: {GN_GROUPS} groups over C channels, bf16 skip of x's shape")
+    x, gamma, beta = _c(x), _c(gamma), _c(beta)
+    skip = _c(skip) if skip is not None else None
+    B, Cc = x.shape[:2]
+    S = x.numel() // (B * Cc)
+    stats = _gn_stats_any(x)
+    y32 = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    y16 = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16) if dual else None
+    _lib.call("ecm_gn3d_apply_bf16_f32", _p(x), _p(stats), _p(gamma), _p(beta), _p(skip), _p(y32), _p(y16), B, Cc,
+              C.c_longlong(S), int(relu), _stream())
+    return (y32, y16) if dual else y32

@@ -396,6 +396,24 @@ int ecm_gn3d_apply_f32_bf16(const float* x, const float* mean_rstd, const float*
 int ecm_conv3d_c1_gn_fwd_bf16(const unsigned short* x, const float* mean_rstd, const float* gamma, const float* beta,
                               const float* w, float* y, int B, int Ci, int D, int H, int W, void* stream);
 
+/* ---- opt-in bf16 inference of the 2-D feature encoder (ops.encoder_dtype; bf16_encoder.hip) -----------------------------
+ * Forward only; replaces the encoder's Conv2d / GroupNorm layers after the stem (cmfsm.py:126-236).  Maps are contiguous
+ * bf16 NCHW (unsigned short = the bf16 bit pattern), weights fp32 parameters packed to a bf16 image; products accumulate in
+ * fp32 and every output is rounded once (round to nearest even, NaN stays NaN).  No atomics: bit-reproducible.
+ * Weight image: [Ci/16][k*k taps][Co][16] bf16 of w [Co,Ci,k,k], k in {1, 3}; Ci % 16 == 0 (0 elements otherwise). */
+long long ecm_conv2d_bf16_packed_elems(int Ci, int Co, int k);
+int ecm_conv2d_bf16_pack_weight(const float* w, unsigned short* packed, int Ci, int Co, int k, void* stream);
+/* Conv2d without bias (convbn, cmfsm.py:36-46; the 1x1 projections): k = 3 with padding = dilation, stride 1 (dilation
+ * 1|2|4) or 2 (dilation 1); k = 1 with padding 0, stride 1|2.  y [B,Co,Ho,Wo], Ho = (H-1)/stride+1: bf16, or fp32 with
+ * out_f32 = 1 (the layers whose result leaves the encoder).  Ci % 16 == 0, Co % 32 == 0; any H, W >= 1. */
+int ecm_conv2d_bf16_fwd(const unsigned short* x, const unsigned short* wpacked, void* y, int B, int Ci, int Co, int H, int W,
+                        int k, int stride, int dil, int out_f32, void* stream);
+/* y32 = relu?( GroupNorm(x)*gamma + beta (+ skip) ) in fp32 from a bf16 x (statistics from ecm_gn3d_stats_bf16), skip bf16
+ * or NULL; y16 non-NULL: the same values rounded to bf16 as well (the encoder's results that also feed its next layer). */
+int ecm_gn3d_apply_bf16_f32(const unsigned short* x, const float* mean_rstd, const float* gamma, const float* beta,
+                            const unsigned short* skip, float* y32, unsigned short* y16, int B, int C, long long S, int relu,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

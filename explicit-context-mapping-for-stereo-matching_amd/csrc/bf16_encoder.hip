@@ -14,21 +14,14 @@
 //   loads (issued one chunk earlier) are in flight under them; one barrier per chunk.
 //   The output type is a template parameter: bf16 inside the encoder, fp32 for the layers whose result leaves it.
 // No atomics: each output is one workgroup's fixed-order sum, so results are bit-reproducible.
-//
-// GroupNorm at the region's end: a bf16-in apply that writes the fp32 result (and, where the same map also feeds the next
-// bf16 layer, its bf16 copy in the same pass).  Statistics and the variance formulation are those of bf16_infer.hip.
-// f32 -> bf16 is a plain cast: v_cvt_pk_bf16_f32, round to nearest even, NaN stays NaN.
+// The GroupNorm that ends the region (bf16 in, fp32 out plus an optional bf16 copy) is gn3d.hip's ecm_gn3d_apply_bf16_f32.
 #include "common.h"
+#include "bf16.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned short u16;
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));     // a native vector: promoted to registers, unlike uint4 copies
-
-__device__ __forceinline__ float bf2f(u16 v) { return __builtin_bit_cast(float, (unsigned)v << 16); }
-__device__ __forceinline__ u16 f2bf(float v) { return __builtin_bit_cast(u16, (__bf16)v); }
 
 __device__ __forceinline__ void store_out(u16* p, float v) { *p = f2bf(v); }
 __device__ __forceinline__ void store_out(float* p, float v) { *p = v; }
@@ -272,72 +265,6 @@ __global__ void pack_bf16_2d(const float* __restrict__ w, u16* __restrict__ out,
     out[i] = f2bf(w[((size_t)co * Ci + ci) * KK + t]);
 }
 
-// ---- GroupNorm apply, bf16 in, fp32 out (+ optional bf16 copy) ---------------------------------------------------------------
-constexpr int GROUPS = 32;
-constexpr int THREADS = 256;
-
-template <bool RELU, bool SKIP, bool DUAL>
-__global__ __launch_bounds__(THREADS) void gn_apply_bf16_f32(const u16* __restrict__ x, const float* __restrict__ mean_rstd,
-                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                             const u16* __restrict__ skip, float* __restrict__ y32,
-                                                             u16* __restrict__ y16, int C, long long S) {
-    const int bc = blockIdx.y;
-    const int b = bc / C, c = bc - b * C;
-    const int g = c / (C / GROUPS);
-    const float mean = mean_rstd[(b * GROUPS + g) * 2], rstd = mean_rstd[(b * GROUPS + g) * 2 + 1];
-    const float a = rstd * gamma[c];
-    const float sh = __builtin_fmaf(-mean, a, beta[c]);
-    const size_t base = (size_t)bc * S;
-    auto one = [&](float v, float k) {
-        v = __builtin_fmaf(v, a, sh);
-        if (SKIP) v += k;
-        if (RELU) v = fmaxf(v, 0.f);
-        return v;
-    };
-    if ((S & 7) == 0) {                 // every row starts 16-byte aligned (bf16) / 32-byte aligned (fp32)
-        const long long stride = (long long)gridDim.x * THREADS * 8;
-        for (long long i = ((long long)blockIdx.x * THREADS + threadIdx.x) * 8; i < S; i += stride) {
-            float v[8], k[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            {
-                const uint4 p = *reinterpret_cast<const uint4*>(x + base + i);
-                const unsigned u[4] = {p.x, p.y, p.z, p.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { v[2 * j] = bf2f((u16)(u[j] & 0xffffu)); v[2 * j + 1] = bf2f((u16)(u[j] >> 16)); }
-            }
-            if (SKIP) {
-                const uint4 p = *reinterpret_cast<const uint4*>(skip + base + i);
-                const unsigned u[4] = {p.x, p.y, p.z, p.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { k[2 * j] = bf2f((u16)(u[j] & 0xffffu)); k[2 * j + 1] = bf2f((u16)(u[j] >> 16)); }
-            }
-            float o[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = one(v[j], k[j]);
-            ecm_st_stream(y32 + base + i, make_float4(o[0], o[1], o[2], o[3]));
-            ecm_st_stream(y32 + base + i + 4, make_float4(o[4], o[5], o[6], o[7]));
-            if (DUAL) {
-                unsigned h[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) h[j] = (unsigned)f2bf(o[2 * j]) | ((unsigned)f2bf(o[2 * j + 1]) << 16);
-                *reinterpret_cast<uint4*>(y16 + base + i) = make_uint4(h[0], h[1], h[2], h[3]);
-            }
-        }
-    } else {
-        for (long long i = (long long)blockIdx.x * THREADS + threadIdx.x; i < S; i += (long long)gridDim.x * THREADS) {
-            const float o = one(bf2f(x[base + i]), SKIP ? bf2f(skip[base + i]) : 0.f);
-            y32[base + i] = o;
-            if (DUAL) y16[base + i] = f2bf(o);
-        }
-    }
-}
-
-template <bool RELU, bool SKIP>
-void launch_apply_f32(dim3 grid, hipStream_t st, const u16* x, const float* mr, const float* g, const float* be, const u16* skip,
-                      float* y32, u16* y16, int C, long long S) {
-    if (y16) hipLaunchKernelGGL((gn_apply_bf16_f32<RELU, SKIP, true>), grid, dim3(THREADS), 0, st, x, mr, g, be, skip, y32, y16, C, S);
-    else hipLaunchKernelGGL((gn_apply_bf16_f32<RELU, SKIP, false>), grid, dim3(THREADS), 0, st, x, mr, g, be, skip, y32, y16, C, S);
-}
-
 }  // namespace
 
 extern "C" long long ecm_conv2d_bf16_packed_elems(int Ci, int Co, int k) {
@@ -362,19 +289,4 @@ extern "C" int ecm_conv2d_bf16_fwd(const unsigned short* x, const unsigned short
     if ((long long)Ci * H * W >= 0x7fffffffLL || (long long)Co * Ho * Wo >= 0x7fffffffLL) return ECM_EUNSUP;
     if (out_f32) return dispatch<float>(x, wpacked, static_cast<float*>(y), B, Ci, Co, H, W, k, stride, dil, stream);
     return dispatch<u16>(x, wpacked, static_cast<u16*>(y), B, Ci, Co, H, W, k, stride, dil, stream);
-}
-
-extern "C" int ecm_gn3d_apply_bf16_f32(const unsigned short* x, const float* mean_rstd, const float* gamma, const float* beta,
-                                       const unsigned short* skip, float* y32, unsigned short* y16, int B, int C, long long S,
-                                       int relu, void* stream) {
-    ECM_CHECK_ARG(x && mean_rstd && gamma && beta && y32 && B > 0 && C > 0 && S > 0);
-    if (C % GROUPS != 0 || (long long)B * C > 65535) return ECM_EUNSUP;
-    const long long per = (S + THREADS * 8 - 1) / (THREADS * 8);
-    const dim3 grid((unsigned)(per < 64 ? per : 64), B * C);
-    hipStream_t st = ecm_stream(stream);
-    if (relu && skip) launch_apply_f32<true, true>(grid, st, x, mean_rstd, gamma, beta, skip, y32, y16, C, S);
-    else if (relu) launch_apply_f32<true, false>(grid, st, x, mean_rstd, gamma, beta, skip, y32, y16, C, S);
-    else if (skip) launch_apply_f32<false, true>(grid, st, x, mean_rstd, gamma, beta, skip, y32, y16, C, S);
-    else launch_apply_f32<false, false>(grid, st, x, mean_rstd, gamma, beta, skip, y32, y16, C, S);
-    return ECM_LAUNCH_RESULT();
 }

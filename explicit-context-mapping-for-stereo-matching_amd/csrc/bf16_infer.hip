@@ -11,20 +11,13 @@
 //   at m (p = 1).  Each of the 8 output phases is a stride-1 convolution with 1..8 taps over the input grid; the phase is
 //   blockIdx.y and every phase re-reads its small input tile through L2.  27 taps in all: every product is computed once.
 // No atomics: each output is one workgroup's fixed-order sum, so results are bit-reproducible.
-//
-// GroupNorm(32): the two-stage form of gn3d.hip (stats partials -> fixed-order finish in double around a trimmed-mean
-// pivot; apply pass) with bf16 storage -- and an fp32-input apply for the boundary into the bf16 region.
-// f32 -> bf16 is a plain cast: v_cvt_pk_bf16_f32, round to nearest even, NaN stays NaN.
+// GroupNorm on bf16 volumes is gn3d.hip's two-stage forward (ecm_gn3d_stats_bf16 / ecm_gn3d_apply_bf16 / _f32_bf16).
 #include "common.h"
+#include "bf16.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned short u16;
-
-__device__ __forceinline__ float bf2f(u16 v) { return __builtin_bit_cast(float, (unsigned)v << 16); }
-__device__ __forceinline__ u16 f2bf(float v) { return __builtin_bit_cast(u16, (__bf16)v); }
 
 constexpr int TW = 32;          // output voxels along w per MFMA row (the B operand's 32 columns)
 constexpr int NSLOT = 28;       // weight-image tap slots per 8-channel chunk: 27 taps + 1 zero (conv), or 8 phases padded to even
@@ -274,160 +267,6 @@ __global__ void pack_bf16(const float* __restrict__ w, u16* __restrict__ out, in
     out[i] = f2bf(v);
 }
 
-// ---- GroupNorm ---------------------------------------------------------------------------------------------------------------
-constexpr int GROUPS = 32;
-constexpr int THREADS = 256;
-constexpr long long CHUNK = 32768;           // elements reduced per workgroup in stage 1 (as gn3d.hip: same scratch size)
-
-template <class T> __device__ __forceinline__ float ld(const T* p, long long i);
-template <> __device__ __forceinline__ float ld<float>(const float* p, long long i) { return p[i]; }
-template <> __device__ __forceinline__ float ld<u16>(const u16* p, long long i) { return bf2f(p[i]); }
-
-__device__ __forceinline__ void block_reduce2(float& a, float& b, float* sm) {
-    a = wave_sum(a);
-    b = wave_sum(b);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) { sm[wave * 2] = a; sm[wave * 2 + 1] = b; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float x = 0.f, y = 0.f;
-        for (int i = 0; i < THREADS / 64; ++i) { x += sm[2 * i]; y += sm[2 * i + 1]; }
-        sm[0] = x; sm[1] = y;
-    }
-    __syncthreads();
-    a = sm[0];
-    b = sm[1];
-}
-
-// the trimmed-mean pivot of gn3d.hip (gn_pivot): variance as E[d^2] - E[d]^2 of d = x - K
-__device__ __forceinline__ float pivot_bf16(const u16* __restrict__ p, long long n) {
-    float s = 0.f;
-    if (n < 16) {
-        for (long long i = 0; i < n; ++i) s += bf2f(p[i]);
-        return s / (float)n;
-    }
-    const long long st = n / 16;
-    float lo = bf2f(p[st >> 1]), hi = lo;
-    s = lo;
-#pragma unroll
-    for (int j = 1; j < 16; ++j) {
-        const float v = bf2f(p[(long long)j * st + (st >> 1)]);
-        s += v;
-        lo = fminf(lo, v);
-        hi = fmaxf(hi, v);
-    }
-    return (s - lo - hi) * (1.0f / 14.0f);
-}
-
-__global__ __launch_bounds__(THREADS) void gn_stats_partial_bf16(const u16* __restrict__ x, float* __restrict__ part,
-                                                                 long long n, int nchunks) {
-    __shared__ float sm[2 * THREADS / 64];
-    const u16* p = x + (size_t)blockIdx.y * n;
-    const float K = pivot_bf16(p, n);
-    const long long beg = (long long)blockIdx.x * CHUNK;
-    const long long end = beg + CHUNK < n ? beg + CHUNK : n;
-    float s = 0.f, q = 0.f;
-    if ((n & 7) == 0) {                                            // span start and chunk bounds are 16-byte aligned
-        for (long long i = beg + threadIdx.x * 8; i < end; i += THREADS * 8) {
-            const uint4 v = *reinterpret_cast<const uint4*>(p + i);
-            const unsigned u[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float a = bf2f((u16)(u[k] & 0xffffu)) - K, c = bf2f((u16)(u[k] >> 16)) - K;
-                s += a + c;
-                q += a * a + c * c;
-            }
-        }
-    } else {
-        for (long long i = beg + threadIdx.x; i < end; i += THREADS) { const float v = bf2f(p[i]) - K; s += v; q += v * v; }
-    }
-    block_reduce2(s, q, sm);
-    if (threadIdx.x == 0) {
-        part[((size_t)blockIdx.y * nchunks + blockIdx.x) * 2] = s;
-        part[((size_t)blockIdx.y * nchunks + blockIdx.x) * 2 + 1] = q;
-    }
-}
-
-__global__ void gn_stats_final_bf16(const u16* __restrict__ x, const float* __restrict__ part, float* __restrict__ mean_rstd,
-                                    int nspans, int nchunks, long long n, float eps) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nspans) return;
-    double s = 0.0, q = 0.0;
-    for (int c = 0; c < nchunks; ++c) { s += part[((size_t)i * nchunks + c) * 2]; q += part[((size_t)i * nchunks + c) * 2 + 1]; }
-    const double dm = s / (double)n;
-    const double mean = (double)pivot_bf16(x + (size_t)i * n, n) + dm;
-    double var = q / (double)n - dm * dm;
-    if (var < 0.0) var = 0.0;
-    mean_rstd[2 * i] = (float)mean;
-    mean_rstd[2 * i + 1] = (float)(1.0 / sqrt(var + (double)eps));
-}
-
-// y = bf16( relu?( fma(x, a, sh) (+ skip) ) ), a = rstd*gamma, sh = beta - mean*a (gn3d.hip's gn_affine); x fp32 or bf16
-template <class T, bool RELU, bool SKIP>
-__global__ __launch_bounds__(THREADS) void gn_apply_bf16(const T* __restrict__ x, const float* __restrict__ mean_rstd,
-                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                         const u16* __restrict__ skip, u16* __restrict__ y, int C, long long S) {
-    const int bc = blockIdx.y;
-    const int b = bc / C, c = bc - b * C;
-    const int g = c / (C / GROUPS);
-    const float mean = mean_rstd[(b * GROUPS + g) * 2], rstd = mean_rstd[(b * GROUPS + g) * 2 + 1];
-    const float a = rstd * gamma[c];
-    const float sh = __builtin_fmaf(-mean, a, beta[c]);
-    const size_t base = (size_t)bc * S;
-    auto one = [&](float v, float k) {
-        v = __builtin_fmaf(v, a, sh);
-        if (SKIP) v += k;
-        if (RELU) v = fmaxf(v, 0.f);
-        return v;
-    };
-    if ((S & 7) == 0) {                 // every row starts 16-byte aligned (bf16) / 32-byte aligned (fp32)
-        const long long stride = (long long)gridDim.x * THREADS * 8;
-        for (long long i = ((long long)blockIdx.x * THREADS + threadIdx.x) * 8; i < S; i += stride) {
-            float v[8], k[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            if constexpr (sizeof(T) == 4) {
-                const float4 p = *reinterpret_cast<const float4*>(x + base + i), q = *reinterpret_cast<const float4*>(x + base + i + 4);
-                v[0] = p.x; v[1] = p.y; v[2] = p.z; v[3] = p.w; v[4] = q.x; v[5] = q.y; v[6] = q.z; v[7] = q.w;
-            } else {
-                const uint4 p = *reinterpret_cast<const uint4*>(x + base + i);
-                const unsigned u[4] = {p.x, p.y, p.z, p.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { v[2 * j] = bf2f((u16)(u[j] & 0xffffu)); v[2 * j + 1] = bf2f((u16)(u[j] >> 16)); }
-            }
-            if (SKIP) {
-                const uint4 p = *reinterpret_cast<const uint4*>(skip + base + i);
-                const unsigned u[4] = {p.x, p.y, p.z, p.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { k[2 * j] = bf2f((u16)(u[j] & 0xffffu)); k[2 * j + 1] = bf2f((u16)(u[j] >> 16)); }
-            }
-            unsigned o[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                o[j] = (unsigned)f2bf(one(v[2 * j], k[2 * j])) | ((unsigned)f2bf(one(v[2 * j + 1], k[2 * j + 1])) << 16);
-            *reinterpret_cast<uint4*>(y + base + i) = make_uint4(o[0], o[1], o[2], o[3]);
-        }
-    } else {
-        for (long long i = (long long)blockIdx.x * THREADS + threadIdx.x; i < S; i += (long long)gridDim.x * THREADS)
-            y[base + i] = f2bf(one(ld<T>(x + base, i), SKIP ? bf2f(skip[base + i]) : 0.f));
-    }
-}
-
-inline int chunks_of(long long n) { return (int)((n + CHUNK - 1) / CHUNK); }
-
-template <class T>
-int launch_apply(const T* x, const float* mean_rstd, const float* gamma, const float* beta, const u16* skip, u16* y, int B,
-                 int C, long long S, int relu, void* stream) {
-    if (C % GROUPS != 0 || (long long)B * C > 65535) return ECM_EUNSUP;
-    const long long per = (S + THREADS * 8 - 1) / (THREADS * 8);
-    const int gx = (int)(per < 64 ? per : 64);
-    dim3 grid(gx, B * C), block(THREADS);
-    hipStream_t st = ecm_stream(stream);
-    if (relu && skip) hipLaunchKernelGGL((gn_apply_bf16<T, true, true>), grid, block, 0, st, x, mean_rstd, gamma, beta, skip, y, C, S);
-    else if (relu) hipLaunchKernelGGL((gn_apply_bf16<T, true, false>), grid, block, 0, st, x, mean_rstd, gamma, beta, skip, y, C, S);
-    else if (skip) hipLaunchKernelGGL((gn_apply_bf16<T, false, true>), grid, block, 0, st, x, mean_rstd, gamma, beta, skip, y, C, S);
-    else hipLaunchKernelGGL((gn_apply_bf16<T, false, false>), grid, block, 0, st, x, mean_rstd, gamma, beta, skip, y, C, S);
-    return ECM_LAUNCH_RESULT();
-}
-
 bool conv_shape_ok(int Ci, int Co, long long D, long long H, long long W) {
     // channel chunks of 8, output channels in tiles of 32; 32-bit byte offsets inside one sample's volume
     return (Ci == 32 || Ci == 64) && (Co == 32 || Co == 64) && (long long)Ci * D * H * W * 2 < 0x7fffffffLL;
@@ -466,31 +305,4 @@ extern "C" int ecm_deconv3d_k3s2_bf16_fwd(const unsigned short* x, const unsigne
     if (!conv_shape_ok(Ci, Co, D, H, W) || (long long)Co * 8 * D * H * W * 2 >= 0x7fffffffLL) return ECM_EUNSUP;
     return Co == 32 ? launch_conv_bf16<1, 2, DC_TD, DC_TH>(x, wpacked, y, B, Ci, D, H, W, 2 * D, 2 * H, 2 * W, stream)
                     : launch_conv_bf16<2, 2, DC_TD, DC_TH>(x, wpacked, y, B, Ci, D, H, W, 2 * D, 2 * H, 2 * W, stream);
-}
-
-extern "C" int ecm_gn3d_stats_bf16(const unsigned short* x, float* mean_rstd, void* scratch, long long scratch_bytes, int B,
-                                   int C, long long S, float eps, void* stream) {
-    ECM_CHECK_ARG(x && mean_rstd && scratch && B > 0 && C > 0 && S > 0);
-    if (C % GROUPS != 0) return ECM_EUNSUP;
-    if (scratch_bytes < ecm_gn3d_scratch_bytes(B, C, S)) return ECM_ESCRATCH;
-    const long long n = (long long)(C / GROUPS) * S;
-    const int nchunks = chunks_of(n);
-    float* part = static_cast<float*>(scratch);
-    hipLaunchKernelGGL(gn_stats_partial_bf16, dim3(nchunks, B * GROUPS), dim3(THREADS), 0, ecm_stream(stream), x, part, n, nchunks);
-    hipLaunchKernelGGL(gn_stats_final_bf16, dim3((B * GROUPS + 63) / 64), dim3(64), 0, ecm_stream(stream), x, part, mean_rstd,
-                       B * GROUPS, nchunks, n, eps);
-    return ECM_LAUNCH_RESULT();
-}
-
-extern "C" int ecm_gn3d_apply_bf16(const unsigned short* x, const float* mean_rstd, const float* gamma, const float* beta,
-                                   const unsigned short* skip, unsigned short* y, int B, int C, long long S, int relu, void* stream) {
-    ECM_CHECK_ARG(x && mean_rstd && gamma && beta && y && B > 0 && C > 0 && S > 0);
-    return launch_apply<u16>(x, mean_rstd, gamma, beta, skip, y, B, C, S, relu, stream);
-}
-
-extern "C" int ecm_gn3d_apply_f32_bf16(const float* x, const float* mean_rstd, const float* gamma, const float* beta,
-                                       const unsigned short* skip, unsigned short* y, int B, int C, long long S, int relu,
-                                       void* stream) {
-    ECM_CHECK_ARG(x && mean_rstd && gamma && beta && y && B > 0 && C > 0 && S > 0);
-    return launch_apply<float>(x, mean_rstd, gamma, beta, skip, y, B, C, S, relu, stream);
 }

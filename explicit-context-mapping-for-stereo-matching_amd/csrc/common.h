@@ -50,6 +50,14 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 __device__ __forceinline__ float leaky(float x) { return x > 0.f ? x : 0.01f * x; }   // nn.LeakyReLU default slope
 
+// GroupNorm's per-channel affine map y = fma(x, a, sh): the coefficients are formed the same way wherever they are needed
+// (gn3d.hip's kernels, the classifier tail's fused normalisation in conv3d_c1.hip), so that every kernel writes the same bits
+// and the ReLU mask recomputed in the backward pass is bit-identical to the forward decision.
+__device__ __forceinline__ void gn_affine(float mean, float rstd, float gamma, float beta, float& a, float& sh) {
+    a = rstd * gamma;
+    sh = __builtin_fmaf(-mean, a, beta);
+}
+
 // Streaming 16-byte store of a result that nothing in THIS kernel reads again (non-temporal hint: `global_store_dwordx4 ... nt`).
 // Measured in round 4 on the GroupNorm kernels (profiles/r04_gn_store_policy.txt): 4-18 % faster launches with the hint on the
 // stores, nothing from hinting the loads; the line still stays in the XCD's L2 for the next kernel (MI355X_MICROARCH.md).

@@ -8,6 +8,7 @@
 //             covers all 32 x 27 products; the tap shift is a per-lane LDS offset on the small gy tile)
 // Both are then bound by reading x once (212 MB at 576x960) instead of by ~92 GFLOP of padded MFMA work.
 #include "common.h"
+#include "bf16.h"
 #include <cstdlib>
 
 namespace {
@@ -39,7 +40,7 @@ __device__ __forceinline__ int v_slot(int dz, int hy, int wx) { return ((dz * VH
 
 // GN = true (round 4): x is the RAW output of the classifier's first convolution and the kernel applies GroupNorm(32) + ReLU
 // (cmfsm.py:621-634: convbn_3d -> ReLU -> Conv3d 32 -> 1) while it stages the halo tile: h = max(fma(x, a_c, sh_c), 0) with
-// a_c = rstd * gamma_c, sh_c = fma(-mean, a_c, beta_c) -- the expression of gn3d.hip's gn_affine, so h has the bits the
+// a_c = rstd * gamma_c, sh_c = fma(-mean, a_c, beta_c) (gn_affine, common.h), so h has the bits the
 // stand-alone GroupNorm kernel would have written -- and positions outside the volume stay 0 (the convolution pads h, not x).
 // The normalised tensor (849 MB per head at batch 4) is then never written or read: one read pass of x for the statistics
 // (ecm_gn3d_stats) replaces the GroupNorm kernel's read + write.  Ci == 32 only (one channel per group).
@@ -94,9 +95,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_c1_fwd_v(const T* __restrict__ 
             if constexpr (sizeof(T) == 4) {
                 rr[k].x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, goff[k], s0, 0));
                 rr[k].y = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, goff[k], s0 + cstride, 0));
-            } else {                                         // bf16 bits -> the high half of an fp32
-                rr[k].x = __builtin_bit_cast(float, (unsigned)__builtin_amdgcn_raw_buffer_load_b16(xr, goff[k], s0, 0) << 16);
-                rr[k].y = __builtin_bit_cast(float, (unsigned)__builtin_amdgcn_raw_buffer_load_b16(xr, goff[k], s0 + cstride, 0) << 16);
+            } else {
+                rr[k].x = bf2f(__builtin_amdgcn_raw_buffer_load_b16(xr, goff[k], s0, 0));
+                rr[k].y = bf2f(__builtin_amdgcn_raw_buffer_load_b16(xr, goff[k], s0 + cstride, 0));
             }
         }
     };
@@ -119,8 +120,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_c1_fwd_v(const T* __restrict__ 
             const int c0 = 2 * pair;
             const float m0 = mean_rstd[(b * 32 + c0) * 2], r0 = mean_rstd[(b * 32 + c0) * 2 + 1];
             const float m1 = mean_rstd[(b * 32 + c0 + 1) * 2], r1 = mean_rstd[(b * 32 + c0 + 1) * 2 + 1];
-            const float a0 = r0 * gamma[c0], a1 = r1 * gamma[c0 + 1];
-            const float s0 = __builtin_fmaf(-m0, a0, beta[c0]), s1 = __builtin_fmaf(-m1, a1, beta[c0 + 1]);
+            float a0, s0, a1, s1;
+            gn_affine(m0, r0, gamma[c0], beta[c0], a0, s0);
+            gn_affine(m1, r1, gamma[c0 + 1], beta[c0 + 1], a1, s1);
 #pragma unroll
             for (int k = 0; k < VSLOTS; ++k) {
                 const bool in = goff[k] != 0x80000000u;
@@ -456,7 +458,8 @@ __global__ __launch_bounds__(256) void conv3d_c1_wgrad(const float* __restrict__
 #pragma unroll
             for (int cc = 0; cc < 32; ++cc) {
                 const float m = mean_rstd[(xb_next * 32 + cc) * 2], r = mean_rstd[(xb_next * 32 + cc) * 2 + 1];
-                const float a = r * gamma[cc], sh = __builtin_fmaf(-m, a, beta[cc]);
+                float a, sh;
+                gn_affine(m, r, gamma[cc], beta[cc], a, sh);
 #pragma unroll
                 for (int j = 0; j < 2; ++j) xr[cc * 2 + j] = xin[j] ? fmaxf(__builtin_fmaf(xr[cc * 2 + j], a, sh), 0.f) : 0.f;
             }

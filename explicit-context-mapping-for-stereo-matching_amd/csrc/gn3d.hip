@@ -1,15 +1,19 @@
 // GroupNorm(32 groups) over 5-D volumes + fused ReLU / residual add, fwd + bwd
 // (reference: nn.GroupNorm in convbn_3d cmfsm.py:49-58, hourglass 269/280, ReLU/skip logic 287-299, 685-693).
-// HBM-bound: stats = 1 read of x; apply = 1 read (+1 skip read) + 1 write; all float4, grid-strided.
+// HBM-bound: stats = 1 read of x; apply = 1 read (+1 skip read) + 1 write; all 16-byte vectors, grid-strided.
 // Deterministic: two-stage reductions through caller-provided scratch, no float atomics.
+// The two-stage forward (stats, then apply) also serves the bf16 inference paths (ops.aggregation_dtype / encoder_dtype):
+// one template per stage over the storage types, fp32 or bf16 in, fp32, bf16 or both out.
 #include "common.h"
+#include "bf16.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace {
 
 constexpr int GROUPS = 32;
 constexpr int THREADS = 256;
-constexpr long long CHUNK = 32768;           // floats reduced per workgroup in stage 1
+constexpr long long CHUNK = 32768;           // elements reduced per workgroup in stage 1
 
 __device__ __forceinline__ void block_reduce2(float& a, float& b, float* sm) {
     a = wave_sum(a);
@@ -27,12 +31,9 @@ __device__ __forceinline__ void block_reduce2(float& a, float& b, float* sm) {
     b = sm[1];
 }
 
-// y = fma(x, a, sh): the coefficients are formed the same way wherever they are needed, so that the ReLU mask
-// recomputed in the backward pass is bit-identical to the forward decision.
-__device__ __forceinline__ void gn_affine(float mean, float rstd, float gamma, float beta, float& a, float& sh) {
-    a = rstd * gamma;
-    sh = __builtin_fmaf(-mean, a, beta);
-}
+// element i of an fp32 or bf16 span, as fp32
+__device__ __forceinline__ float ld(const float* p, long long i) { return p[i]; }
+__device__ __forceinline__ float ld(const u16* p, long long i) { return bf2f(p[i]); }
 
 // Statistics are accumulated as sums of d = x - K and d^2 around a PIVOT K (gn_pivot below), and the variance is
 // E[d^2] - E[d]^2: the textbook E[x^2] - E[x]^2 cancels catastrophically when |mean| >> std -- the SPP branches normalise
@@ -45,18 +46,19 @@ __device__ __forceinline__ void gn_affine(float mean, float rstd, float gamma, f
 // sixteenths; smallest and largest sample dropped), or the plain mean of a span shorter than 16: a single outlier among the
 // samples is discarded outright, and a typical span gives |K - mean| ~ std / 4.  Every workgroup of a span and the
 // finishing stage evaluate the same expression in the same order, so they agree bit for bit.
-__device__ __forceinline__ float gn_pivot(const float* __restrict__ p, long long n) {
+template <class T>
+__device__ __forceinline__ float gn_pivot(const T* __restrict__ p, long long n) {
     float s = 0.f;
     if (n < 16) {
-        for (long long i = 0; i < n; ++i) s += p[i];
+        for (long long i = 0; i < n; ++i) s += ld(p, i);
         return s / (float)n;
     }
     const long long st = n / 16;
-    float lo = p[st >> 1], hi = lo;
+    float lo = ld(p, st >> 1), hi = lo;
     s = lo;
 #pragma unroll
     for (int j = 1; j < 16; ++j) {
-        const float v = p[(long long)j * st + (st >> 1)];
+        const float v = ld(p, (long long)j * st + (st >> 1));
         s += v;
         lo = fminf(lo, v);
         hi = fmaxf(hi, v);
@@ -64,24 +66,41 @@ __device__ __forceinline__ float gn_pivot(const float* __restrict__ p, long long
     return (s - lo - hi) * (1.0f / 14.0f);
 }
 
-// stage 1: partial (sum d, sum d^2) of chunk `blockIdx.x` of span `blockIdx.y` (= b*32+g); span = n contiguous floats
-__global__ __launch_bounds__(THREADS) void gn_stats_partial(const float* __restrict__ x, float* __restrict__ part,
-                                                            long long n, int nchunks) {
+// One 16-byte vector of stage 1 into (sum d, sum d^2).  The summation order differs between the types and is part of the
+// results (mean_rstd, and through it every output, is bit-identical to what each type's kernel has always computed):
+// fp32 sums its 4 elements pairwise, bf16 adds its 8 elements to the running sums one pair at a time.
+__device__ __forceinline__ void stats_vec(const float* p, float K, float& s, float& q) {
+    float4 v = *reinterpret_cast<const float4*>(p);
+    v.x -= K; v.y -= K; v.z -= K; v.w -= K;
+    s += (v.x + v.y) + (v.z + v.w);
+    q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+}
+__device__ __forceinline__ void stats_vec(const u16* p, float K, float& s, float& q) {
+    const uint4 v = *reinterpret_cast<const uint4*>(p);
+    const unsigned u[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float a = bf2f((u16)(u[k] & 0xffffu)) - K, c = bf2f((u16)(u[k] >> 16)) - K;
+        s += a + c;
+        q += a * a + c * c;
+    }
+}
+
+// stage 1: partial (sum d, sum d^2) of chunk `blockIdx.x` of span `blockIdx.y` (= b*32+g); span = n contiguous elements
+template <class T>
+__global__ __launch_bounds__(THREADS) void gn_stats_partial(const T* __restrict__ x, float* __restrict__ part, long long n,
+                                                            int nchunks) {
+    constexpr int VEC = 16 / sizeof(T);
     __shared__ float sm[2 * THREADS / 64];
-    const float* p = x + (size_t)blockIdx.y * n;
+    const T* p = x + (size_t)blockIdx.y * n;
     const float K = gn_pivot(p, n);
     const long long beg = (long long)blockIdx.x * CHUNK;
     const long long end = beg + CHUNK < n ? beg + CHUNK : n;
     float s = 0.f, q = 0.f;
-    if ((n & 3) == 0) {
-        for (long long i = beg + threadIdx.x * 4; i < end; i += THREADS * 4) {
-            float4 v = *reinterpret_cast<const float4*>(p + i);
-            v.x -= K; v.y -= K; v.z -= K; v.w -= K;
-            s += (v.x + v.y) + (v.z + v.w);
-            q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-        }
+    if (n % VEC == 0) {                                            // span start and chunk bounds are 16-byte aligned
+        for (long long i = beg + threadIdx.x * VEC; i < end; i += THREADS * VEC) stats_vec(p + i, K, s, q);
     } else {
-        for (long long i = beg + threadIdx.x; i < end; i += THREADS) { const float v = p[i] - K; s += v; q += v * v; }
+        for (long long i = beg + threadIdx.x; i < end; i += THREADS) { const float v = ld(p, i) - K; s += v; q += v * v; }
     }
     block_reduce2(s, q, sm);
     if (threadIdx.x == 0) {
@@ -91,7 +110,8 @@ __global__ __launch_bounds__(THREADS) void gn_stats_partial(const float* __restr
 }
 
 // stage 2: one thread per span, fixed-order sum in double -> (mean, rstd)
-__global__ void gn_stats_final(const float* __restrict__ x, const float* __restrict__ part, float* __restrict__ mean_rstd,
+template <class T>
+__global__ void gn_stats_final(const T* __restrict__ x, const float* __restrict__ part, float* __restrict__ mean_rstd,
                                int nspans, int nchunks, long long n, float eps) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nspans) return;
@@ -105,12 +125,57 @@ __global__ void gn_stats_final(const float* __restrict__ x, const float* __restr
     mean_rstd[2 * i + 1] = (float)(1.0 / sqrt(var + (double)eps));
 }
 
-// y = relu?( x*a[b,c] + sh[b,c] (+ skip) ),  a = rstd*gamma, sh = beta - mean*a.  grid: (chunks, B*C)
-template <bool RELU, bool SKIP>
-__global__ __launch_bounds__(THREADS) void gn_apply(const float* __restrict__ x, const float* __restrict__ mean_rstd,
+// VEC elements of fp32 or bf16 storage <-> fp32 registers, in 16-byte accesses
+template <int VEC>
+__device__ __forceinline__ void ld_vec(const float* p, float (&v)[VEC]) {
+#pragma unroll
+    for (int j = 0; j < VEC; j += 4) {
+        const float4 q = *reinterpret_cast<const float4*>(p + j);
+        v[j] = q.x; v[j + 1] = q.y; v[j + 2] = q.z; v[j + 3] = q.w;
+    }
+}
+__device__ __forceinline__ void ld_vec(const u16* p, float (&v)[8]) {
+    const uint4 q = *reinterpret_cast<const uint4*>(p);
+    const unsigned u[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { v[2 * j] = bf2f((u16)(u[j] & 0xffffu)); v[2 * j + 1] = bf2f((u16)(u[j] >> 16)); }
+}
+template <bool STREAM = false, int VEC>
+__device__ __forceinline__ void st_vec(float* p, const float (&v)[VEC]) {
+#pragma unroll
+    for (int j = 0; j < VEC; j += 4) {
+        const float4 f = make_float4(v[j], v[j + 1], v[j + 2], v[j + 3]);
+        if (STREAM) ecm_st_stream(p + j, f);
+        else *reinterpret_cast<float4*>(p + j) = f;
+    }
+}
+template <bool STREAM = false>                                  // (bf16 results take plain stores)
+__device__ __forceinline__ void st_vec(u16* p, const float (&v)[8]) {
+    unsigned h[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) h[j] = (unsigned)f2bf(v[2 * j]) | ((unsigned)f2bf(v[2 * j + 1]) << 16);
+    *reinterpret_cast<uint4*>(p) = make_uint4(h[0], h[1], h[2], h[3]);
+}
+__device__ __forceinline__ void st(float* p, long long i, float v) { p[i] = v; }
+__device__ __forceinline__ void st(u16* p, long long i, float v) { p[i] = f2bf(v); }
+
+// The forms of the apply pass: TI in -> TO out.  The residual operand is fp32 only in the all-fp32 form (bf16 wherever bf16 is
+// involved); DUAL (bf16 in, fp32 out) also writes the result rounded to bf16 into y16.  Per thread and step: 16 bytes of fp32
+// (4 elements) in the all-fp32 form, 8 elements otherwise.  Only the encoder's fp32 results (bf16 in) are written with the
+// streaming hint.
+template <class TI, class TO>
+using gn_skip_t = std::conditional_t<std::is_same_v<TI, float> && std::is_same_v<TO, float>, float, u16>;
+template <class TI, class TO>
+constexpr int gn_apply_vec() { return std::is_same_v<TI, float> && std::is_same_v<TO, float> ? 4 : 8; }
+
+// y = relu?( fma(x, a[b,c], sh[b,c]) (+ skip) ),  a = rstd*gamma, sh = beta - mean*a (gn_affine).  grid: (chunks, B*C)
+template <class TI, class TO, bool DUAL, bool RELU, bool SKIP, class TS = gn_skip_t<TI, TO>>
+__global__ __launch_bounds__(THREADS) void gn_apply(const TI* __restrict__ x, const float* __restrict__ mean_rstd,
                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                    const float* __restrict__ skip, float* __restrict__ y, int C,
-                                                    long long S) {
+                                                    const TS* __restrict__ skip, TO* __restrict__ y, u16* __restrict__ y16,
+                                                    int C, long long S) {
+    constexpr int VEC = gn_apply_vec<TI, TO>();
+    constexpr bool STREAM = std::is_same_v<TI, u16> && std::is_same_v<TO, float>;
     const int bc = blockIdx.y;
     const int b = bc / C, c = bc - b * C;
     const int g = c / (C / GROUPS);
@@ -118,25 +183,31 @@ __global__ __launch_bounds__(THREADS) void gn_apply(const float* __restrict__ x,
     float a, sh;
     gn_affine(mean, rstd, gamma[c], beta[c], a, sh);
     const size_t base = (size_t)bc * S;
-    const long long stride = (long long)gridDim.x * THREADS * 4;
-    if ((S & 3) == 0) {
-        for (long long i = ((long long)blockIdx.x * THREADS + threadIdx.x) * 4; i < S; i += stride) {
-            float4 v = *reinterpret_cast<const float4*>(x + base + i);
-            v.x = __builtin_fmaf(v.x, a, sh); v.y = __builtin_fmaf(v.y, a, sh);
-            v.z = __builtin_fmaf(v.z, a, sh); v.w = __builtin_fmaf(v.w, a, sh);
-            if (SKIP) {
-                const float4 k = *reinterpret_cast<const float4*>(skip + base + i);
-                v.x += k.x; v.y += k.y; v.z += k.z; v.w += k.w;
-            }
-            if (RELU) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
-            *reinterpret_cast<float4*>(y + base + i) = v;
+    auto one = [&](float v, float k) {
+        v = __builtin_fmaf(v, a, sh);
+        if (SKIP) v += k;
+        if (RELU) v = fmaxf(v, 0.f);
+        return v;
+    };
+    if (S % VEC == 0) {                 // every row starts 16-byte aligned
+        const long long stride = (long long)gridDim.x * THREADS * VEC;
+        for (long long i = ((long long)blockIdx.x * THREADS + threadIdx.x) * VEC; i < S; i += stride) {
+            float v[VEC], k[VEC] = {};
+            ld_vec(x + base + i, v);
+            if (SKIP) ld_vec(skip + base + i, k);
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) v[j] = one(v[j], k[j]);
+            st_vec<STREAM>(y + base + i, v);
+            if constexpr (DUAL) st_vec(y16 + base + i, v);
         }
     } else {
         for (long long i = (long long)blockIdx.x * THREADS + threadIdx.x; i < S; i += (long long)gridDim.x * THREADS) {
-            float v = __builtin_fmaf(x[base + i], a, sh);
-            if (SKIP) v += skip[base + i];
-            if (RELU) v = fmaxf(v, 0.f);
-            y[base + i] = v;
+            // x through a row pointer for a bf16 result, by element index otherwise: the two forms trade scalar for vector
+            // registers, and each is the one the kernel this template replaced used (same code, same register counts)
+            const float xv = std::is_same_v<TO, u16> ? ld(x + base, i) : ld(x, base + i);
+            const float o = one(xv, SKIP ? ld(skip, base + i) : 0.f);
+            st(y, base + i, o);
+            if constexpr (DUAL) st(y16, base + i, o);
         }
     }
 }
@@ -741,6 +812,36 @@ inline long long fused_scratch_floats(int B) { return (long long)B * GROUPS * FU
 
 inline int chunks_of(long long n) { return (int)((n + CHUNK - 1) / CHUNK); }
 
+// launchers of the two-stage forward (the extern "C" entry points below, and gn_fwd_impl's path without clusters)
+template <class T>
+int launch_stats(const T* x, float* mean_rstd, void* scratch, long long scratch_bytes, int B, int C, long long S, float eps,
+                 void* stream) {
+    ECM_CHECK_ARG(x && mean_rstd && scratch && B > 0 && C > 0 && S > 0);
+    if (C % GROUPS != 0) return ECM_EUNSUP;
+    if (scratch_bytes < ecm_gn3d_scratch_bytes(B, C, S)) return ECM_ESCRATCH;
+    const long long n = (long long)(C / GROUPS) * S;
+    const int nchunks = chunks_of(n);
+    float* part = static_cast<float*>(scratch);
+    hipLaunchKernelGGL(gn_stats_partial<T>, dim3(nchunks, B * GROUPS), dim3(THREADS), 0, ecm_stream(stream), x, part, n, nchunks);
+    hipLaunchKernelGGL(gn_stats_final<T>, dim3((B * GROUPS + 63) / 64), dim3(64), 0, ecm_stream(stream), x, part, mean_rstd,
+                       B * GROUPS, nchunks, n, eps);
+    return ECM_LAUNCH_RESULT();
+}
+
+template <class TI, class TO, bool DUAL = false>
+int launch_apply(const TI* x, const float* mean_rstd, const float* gamma, const float* beta, const gn_skip_t<TI, TO>* skip,
+                 TO* y, u16* y16, int B, int C, long long S, int relu, void* stream) {
+    ECM_CHECK_ARG(x && mean_rstd && gamma && beta && y && B > 0 && C > 0 && S > 0);
+    if (C % GROUPS != 0 || (long long)B * C > 65535) return ECM_EUNSUP;
+    constexpr int VEC = gn_apply_vec<TI, TO>();
+    const long long per = (S + THREADS * VEC - 1) / (THREADS * VEC);
+    const auto kern = relu ? (skip ? gn_apply<TI, TO, DUAL, true, true> : gn_apply<TI, TO, DUAL, true, false>)
+                           : (skip ? gn_apply<TI, TO, DUAL, false, true> : gn_apply<TI, TO, DUAL, false, false>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(per < 64 ? per : 64), B * C), dim3(THREADS), 0, ecm_stream(stream), x, mean_rstd,
+                       gamma, beta, skip, y, y16, C, S);
+    return ECM_LAUNCH_RESULT();
+}
+
 }  // namespace
 
 extern "C" long long ecm_gn3d_scratch_bytes(int B, int C, long long S) {
@@ -753,34 +854,38 @@ extern "C" long long ecm_gn3d_scratch_bytes(int B, int C, long long S) {
     return (m > f ? m : f) * (long long)sizeof(float);
 }
 
+// ---- the two-stage forward: statistics, then the apply pass, over fp32 and bf16 storage ------------------------------------
 extern "C" int ecm_gn3d_stats(const float* x, float* mean_rstd, void* scratch, long long scratch_bytes, int B, int C,
                               long long S, float eps, void* stream) {
-    ECM_CHECK_ARG(x && mean_rstd && scratch && B > 0 && C > 0 && S > 0);
-    if (C % GROUPS != 0) return ECM_EUNSUP;
-    if (scratch_bytes < ecm_gn3d_scratch_bytes(B, C, S)) return ECM_ESCRATCH;
-    const long long n = (long long)(C / GROUPS) * S;
-    const int nchunks = chunks_of(n);
-    float* part = static_cast<float*>(scratch);
-    hipLaunchKernelGGL(gn_stats_partial, dim3(nchunks, B * GROUPS), dim3(THREADS), 0, ecm_stream(stream), x, part, n,
-                       nchunks);
-    hipLaunchKernelGGL(gn_stats_final, dim3((B * GROUPS + 63) / 64), dim3(64), 0, ecm_stream(stream), x, part, mean_rstd,
-                       B * GROUPS, nchunks, n, eps);
-    return ECM_LAUNCH_RESULT();
+    return launch_stats(x, mean_rstd, scratch, scratch_bytes, B, C, S, eps, stream);
+}
+
+extern "C" int ecm_gn3d_stats_bf16(const unsigned short* x, float* mean_rstd, void* scratch, long long scratch_bytes, int B,
+                                   int C, long long S, float eps, void* stream) {
+    return launch_stats(x, mean_rstd, scratch, scratch_bytes, B, C, S, eps, stream);
 }
 
 extern "C" int ecm_gn3d_apply(const float* x, const float* mean_rstd, const float* gamma, const float* beta,
                               const float* skip, float* y, int B, int C, long long S, int relu, void* stream) {
-    ECM_CHECK_ARG(x && mean_rstd && gamma && beta && y && B > 0 && C > 0 && S > 0);
-    if (C % GROUPS != 0 || (long long)B * C > 65535) return ECM_EUNSUP;
-    long long per = (S + THREADS * 4 - 1) / (THREADS * 4);
-    int gx = (int)(per < 64 ? per : 64);
-    dim3 grid(gx, B * C), block(THREADS);
-    hipStream_t st = ecm_stream(stream);
-    if (relu && skip) hipLaunchKernelGGL((gn_apply<true, true>), grid, block, 0, st, x, mean_rstd, gamma, beta, skip, y, C, S);
-    else if (relu) hipLaunchKernelGGL((gn_apply<true, false>), grid, block, 0, st, x, mean_rstd, gamma, beta, skip, y, C, S);
-    else if (skip) hipLaunchKernelGGL((gn_apply<false, true>), grid, block, 0, st, x, mean_rstd, gamma, beta, skip, y, C, S);
-    else hipLaunchKernelGGL((gn_apply<false, false>), grid, block, 0, st, x, mean_rstd, gamma, beta, skip, y, C, S);
-    return ECM_LAUNCH_RESULT();
+    return launch_apply(x, mean_rstd, gamma, beta, skip, y, nullptr, B, C, S, relu, stream);
+}
+
+extern "C" int ecm_gn3d_apply_bf16(const unsigned short* x, const float* mean_rstd, const float* gamma, const float* beta,
+                                   const unsigned short* skip, unsigned short* y, int B, int C, long long S, int relu, void* stream) {
+    return launch_apply(x, mean_rstd, gamma, beta, skip, y, nullptr, B, C, S, relu, stream);
+}
+
+extern "C" int ecm_gn3d_apply_f32_bf16(const float* x, const float* mean_rstd, const float* gamma, const float* beta,
+                                       const unsigned short* skip, unsigned short* y, int B, int C, long long S, int relu,
+                                       void* stream) {
+    return launch_apply(x, mean_rstd, gamma, beta, skip, y, nullptr, B, C, S, relu, stream);
+}
+
+extern "C" int ecm_gn3d_apply_bf16_f32(const unsigned short* x, const float* mean_rstd, const float* gamma, const float* beta,
+                                       const unsigned short* skip, float* y32, unsigned short* y16, int B, int C, long long S,
+                                       int relu, void* stream) {
+    return y16 ? launch_apply<u16, float, true>(x, mean_rstd, gamma, beta, skip, y32, y16, B, C, S, relu, stream)
+               : launch_apply<u16, float, false>(x, mean_rstd, gamma, beta, skip, y32, y16, B, C, S, relu, stream);
 }
 
 namespace {
@@ -1012,9 +1117,9 @@ int gn_fwd_impl(const float* x, const float* gamma, const float* beta, const flo
     else if (skip) rc = launch_fused_fwd<false, true>(x, gamma, beta, skip, y, mean_rstd, cluster, preset, B, C, S, eps, st);
     else rc = launch_fused_fwd<false, false>(x, gamma, beta, skip, y, mean_rstd, cluster, preset, B, C, S, eps, st);
     if (rc != -100) return rc;
-    rc = ecm_gn3d_stats(x, mean_rstd, scratch, scratch_bytes, B, C, S, eps, stream);
+    rc = launch_stats(x, mean_rstd, scratch, scratch_bytes, B, C, S, eps, stream);
     if (rc) return rc;
-    return ecm_gn3d_apply(x, mean_rstd, gamma, beta, skip, y, B, C, S, relu, stream);
+    return launch_apply(x, mean_rstd, gamma, beta, skip, y, nullptr, B, C, S, relu, stream);
 }
 
 int gn_bwd_impl(const float* x, const float* mean_rstd, const float* gamma, const float* beta, const float* y,

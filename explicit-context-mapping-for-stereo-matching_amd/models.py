@@ -178,7 +178,7 @@ def _costvol_dres0(dres0, lr_l, lr_r, ndisp):
     conv, gn = dres0[0][0], dres0[0][1]
     out_dtype = None
     if ops.aggregation_bf16():
-        ops._agg_grad_guard("the bf16 aggregation stack")           # before the first 3-D launch
+        ops._AGG.guard("the bf16 aggregation stack")           # before the first 3-D launch
         out_dtype = torch.bfloat16
     if EXPLICIT_COST_VOLUME:
         return gn.fused(conv(ops.cost_volume(lr_l, lr_r, ndisp)), None, True, out_dtype=out_dtype)
@@ -427,7 +427,7 @@ class feature_extraction(nn.Module):
         results are written in fp32 by the kernel that produces them: the full-resolution map by firstconv's bare last
         convolution ("conv" variants) or by a GroupNorm that also writes the bf16 copy the next layer reads ("convbn"); layer1's
         output the same way; the low-resolution feature by lastconv's 1x1.  `head`: a slice of the fp32 map (no autograd)."""
-        ops._enc_no_grad("feature_extraction")                  # before the first launch
+        ops._ENC.no_grad("feature_extraction")                  # before the first launch
         bf = torch.bfloat16
         fc = list(self.firstconv)
         conv0, gn0 = fc[0][0], fc[0][1]

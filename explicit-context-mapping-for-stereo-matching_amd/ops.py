@@ -88,7 +88,7 @@ class CostVolumeConcat(torch.autograd.Function):
 
 
 def cost_volume(left, right, ndisp):
-    _agg_grad_guard("cost_volume")
+    _AGG.guard("cost_volume")
     return CostVolumeConcat.apply(left, right, int(ndisp))
 
 
@@ -153,7 +153,7 @@ def costvol_conv3d(left, right, weight, ndisp):
     halves of the concat volume are constant along a line in (d, x), so the 3x3x3 convolution collapses to class-indexed
     2-D convolutions of the two feature maps (3x3 on `left`, sheared 3x5 on `right`) -- see csrc/costvol_conv.hip.
     weight: [Co, 2C, 3, 3, 3] (the reference's dres0[0][0].weight)."""
-    _agg_grad_guard("costvol_conv3d")
+    _AGG.guard("costvol_conv3d")
     _need(left.dim() == 4 and right.shape == left.shape and weight.dim() == 5,
           lambda: f"costvol_conv3d: left {tuple(left.shape)}, right {tuple(right.shape)}, weight {tuple(weight.shape)}")
     Cc = left.shape[1]
@@ -1083,7 +1083,7 @@ def conv3d_k3(x, w, stride=1, fork=False):
     A bf16 x runs the bf16 inference kernel (see aggregation_dtype)."""
     if x.dtype == torch.bfloat16:
         return _conv3d_bf16(x, w, int(stride), bool(fork))
-    _agg_grad_guard("conv3d_k3")
+    _AGG.guard("conv3d_k3")
     return Conv3dK3.apply(x, w, int(stride), bool(fork), torch.is_grad_enabled())
 
 
@@ -1118,7 +1118,7 @@ class Deconv3dK3S2(torch.autograd.Function):
 def deconv3d_k3s2(x, w):
     if x.dtype == torch.bfloat16:
         return _deconv3d_bf16(x, w)
-    _agg_grad_guard("deconv3d_k3s2")
+    _AGG.guard("deconv3d_k3s2")
     return Deconv3dK3S2.apply(x, w)
 
 
@@ -1348,11 +1348,7 @@ class ClassifierTail(torch.autograd.Function):
         B, Cc, D, H, W = x.shape
         if Cc != 32 or tuple(w.shape) != (1, 32, 3, 3, 3):
             raise RuntimeError(f"classifier_tail: x {tuple(x.shape)}, w {tuple(w.shape)}: the fused tail exists for 32 -> 1 only")
-        S = D * H * W
-        stats = torch.empty(B, GN_GROUPS, 2, device=x.device, dtype=x.dtype)
-        nb = _lib.query("ecm_gn3d_scratch_bytes", B, Cc, C.c_longlong(S))
-        scratch = _scratch(nb, x.device)
-        _gn_call("ecm_gn3d_stats", _p(x), _p(stats), _p(scratch), C.c_longlong(nb), B, Cc, C.c_longlong(S), C.c_float(GN_EPS), _stream())
+        stats = _gn_stats(x)
         y = torch.empty(B, 1, D, H, W, device=x.device, dtype=x.dtype)
         _lib.call("ecm_conv3d_c1_gn_fwd", _p(x), _p(stats), _p(gamma), _p(beta), _p(w), _p(y), B, Cc, D, H, W, _stream())
         ctx.save_for_backward(x, stats, gamma, beta, w)
@@ -1399,7 +1395,7 @@ def classifier_tail(x, gamma, beta, w):
     """relu(GroupNorm32(x)) -> Conv3d(32 -> 1): see ClassifierTail.  A bf16 x gives the same fp32 logits from the bf16 volume."""
     if x.dtype == torch.bfloat16:
         return _classifier_tail_bf16(x, gamma, beta, w)
-    _agg_grad_guard("classifier_tail")
+    _AGG.guard("classifier_tail")
     return ClassifierTail.apply(x, gamma, beta, w)
 
 
@@ -1544,7 +1540,8 @@ def group_norm_act(x, gamma, beta, skip=None, relu=False, head=0, out_dtype=None
     the bf16 region: fp32 x), runs the bf16 inference kernels and returns a bf16 y (see aggregation_dtype)."""
     if x.dtype == torch.bfloat16 or out_dtype == torch.bfloat16:
         _need(not head, "group_norm_act: the bf16 form takes no head fork")
-        return _group_norm_bf16(x, gamma, beta, skip, bool(relu))
+        _AGG.no_grad("group_norm_act")
+        return _gn_apply_two_stage(x, gamma, beta, skip, bool(relu), torch.bfloat16)
     _need(out_dtype in (None, torch.float32), lambda: f"group_norm_act: out_dtype {out_dtype}: float32 or bfloat16")
     _need(0 <= int(head) <= x.shape[0], lambda: f"group_norm_act: head {head} of a batch of {x.shape[0]}")
     if head and not (torch.is_grad_enabled() and x.requires_grad):
@@ -1576,38 +1573,50 @@ def check_async_errors(clear=True):
 # a backward: a 3-D op reached with grad enabled raises), and the fp32 path outside the block is untouched.  The ops below
 # dispatch on the dtype of the volume; weights stay fp32 parameters, packed to bf16 images per call (cached under
 # frozen_weights() beside the fp32 layouts, under their own keys).
-_AGG_DTYPE = torch.float32
+class _Bf16Switch:
+    """A process-wide opt-in bf16 inference switch (aggregation_dtype, encoder_dtype): nests, restores the previous setting
+    on exit, and is inference only."""
+
+    def __init__(self, name, what):
+        self.name, self.what, self.dtype = name, what, torch.float32
+
+    @_contextlib.contextmanager
+    def scope(self, dtype):
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"{self.name}: {dtype} is not supported (torch.float32 or torch.bfloat16)")
+        prev, self.dtype = self.dtype, dtype
+        try:
+            yield
+        finally:
+            self.dtype = prev
+
+    def on(self):
+        return self.dtype == torch.bfloat16
+
+    def no_grad(self, op):
+        """Raise the inference-only error if grad is enabled."""
+        if torch.is_grad_enabled():
+            raise RuntimeError(f"{op}: {self.what} has no backward (inference only); run the model under torch.no_grad() "
+                               f"or leave the {self.name}(torch.bfloat16) block")
+
+    def guard(self, op):
+        """An op reached inside a bf16 block with grad enabled raises before it launches anything (no silent fp32 path)."""
+        if self.on():
+            self.no_grad(op)
 
 
-@_contextlib.contextmanager
+_AGG = _Bf16Switch("aggregation_dtype", "bf16 aggregation")
+
+
 def aggregation_dtype(dtype):
     """torch.float32 (the default; a no-op) or torch.bfloat16 for the 3-D aggregation stack inside the block; nests and
     restores the previous setting on exit.  bf16 is inference only: run the model under torch.no_grad()."""
-    global _AGG_DTYPE
-    if dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError(f"aggregation_dtype: {dtype} is not supported (torch.float32 or torch.bfloat16)")
-    prev, _AGG_DTYPE = _AGG_DTYPE, dtype
-    try:
-        yield
-    finally:
-        _AGG_DTYPE = prev
+    return _AGG.scope(dtype)
 
 
 def aggregation_bf16():
     """True inside an aggregation_dtype(torch.bfloat16) block."""
-    return _AGG_DTYPE == torch.bfloat16
-
-
-def _bf16_no_grad(what):
-    if torch.is_grad_enabled():
-        raise RuntimeError(f"{what}: bf16 aggregation has no backward (inference only); run the model under torch.no_grad() "
-                           "or leave the aggregation_dtype(torch.bfloat16) block")
-
-
-def _agg_grad_guard(what):
-    """A 3-D op reached inside a bf16 block with grad enabled raises before it launches anything (no silent fp32 path)."""
-    if _AGG_DTYPE == torch.bfloat16:
-        _bf16_no_grad(what)
+    return _AGG.on()
 
 
 def _chk_bf16(*ts):
@@ -1629,7 +1638,7 @@ def _pack_bf16(w, transposed):
 
 
 def _conv3d_bf16(x, w, stride, fork):
-    _bf16_no_grad("conv3d_k3")
+    _AGG.no_grad("conv3d_k3")
     _chk_bf16(x)
     _chk(w)
     _need(x.dim() == 5 and w.dim() == 5 and tuple(w.shape[2:]) == (3, 3, 3) and w.shape[1] == x.shape[1] and stride in (1, 2)
@@ -1646,7 +1655,7 @@ def _conv3d_bf16(x, w, stride, fork):
 
 
 def _deconv3d_bf16(x, w):
-    _bf16_no_grad("deconv3d_k3s2")
+    _AGG.no_grad("deconv3d_k3s2")
     _chk_bf16(x)
     _chk(w)
     _need(x.dim() == 5 and w.dim() == 5 and tuple(w.shape[2:]) == (3, 3, 3) and w.shape[0] == x.shape[1]
@@ -1661,7 +1670,7 @@ def _deconv3d_bf16(x, w):
     return y
 
 
-def _gn_stats_any(x):
+def _gn_stats(x):
     """GroupNorm(32) statistics [B,32,2] (mean, rstd) of an fp32 or bf16 volume (two-stage kernels)."""
     B, Cc = x.shape[:2]
     S = x.numel() // (B * Cc)
@@ -1669,33 +1678,44 @@ def _gn_stats_any(x):
     nb = _lib.query("ecm_gn3d_scratch_bytes", B, Cc, C.c_longlong(S))
     scratch = _scratch(nb, x.device)
     name = "ecm_gn3d_stats_bf16" if x.dtype == torch.bfloat16 else "ecm_gn3d_stats"
-    _lib.call(name, _p(x), _p(stats), _p(scratch), C.c_longlong(nb), B, Cc, C.c_longlong(S), C.c_float(GN_EPS), _stream())
+    _gn_call(name, _p(x), _p(stats), _p(scratch), C.c_longlong(nb), B, Cc, C.c_longlong(S), C.c_float(GN_EPS), _stream())
     return stats
 
 
-def _group_norm_bf16(x, gamma, beta, skip, relu):
-    _bf16_no_grad("group_norm_act")
-    if x.dtype != torch.bfloat16:
-        _chk(x)
+def _gn_apply_two_stage(x, gamma, beta, skip, relu, out):
+    """relu?(GroupNorm32(x)*gamma+beta (+ skip)) by the two-stage kernels for the bf16 paths.  x fp32 or bf16, skip bf16;
+    out: torch.bfloat16 (a bf16 y), torch.float32 (a bf16 x written in fp32) or "dual" (bf16 x: fp32 y and its bf16 copy)."""
+    x_bf16 = x.dtype == torch.bfloat16
+    what = "group_norm_act (bf16)" if out == torch.bfloat16 else "group_norm_act_bf16_f32"
+    if not x_bf16 and out == torch.bfloat16:
+        _chk(x)                             # the boundary into the bf16 region: an fp32 x
+    else:
+        _chk_bf16(x)
     _chk(gamma, beta)
-    _chk_bf16(x if x.dtype == torch.bfloat16 else None, skip)
+    _chk_bf16(skip)
     _need(x.dim() >= 3 and x.numel() > 0 and x.shape[1] % GN_GROUPS == 0 and gamma.numel() == x.shape[1] == beta.numel()
           and (skip is None or skip.shape == x.shape),
-          lambda: f"group_norm_act (bf16): x {tuple(x.shape)}, gamma {tuple(gamma.shape)}, skip "
+          lambda: f"{what}: x {tuple(x.shape)}, gamma {tuple(gamma.shape)}, skip "
                   f"{None if skip is None else tuple(skip.shape)}: {GN_GROUPS} groups over C channels, bf16 skip of x's shape")
     x, gamma, beta = _c(x), _c(gamma), _c(beta)
     skip = _c(skip) if skip is not None else None
     B, Cc = x.shape[:2]
     S = x.numel() // (B * Cc)
-    stats = _gn_stats_any(x)
-    y = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16)
-    name = "ecm_gn3d_apply_bf16" if x.dtype == torch.bfloat16 else "ecm_gn3d_apply_f32_bf16"
-    _lib.call(name, _p(x), _p(stats), _p(gamma), _p(beta), _p(skip), _p(y), B, Cc, C.c_longlong(S), int(relu), _stream())
-    return y
+    stats = _gn_stats(x)
+    args = (_p(x), _p(stats), _p(gamma), _p(beta), _p(skip))
+    tail = (B, Cc, C.c_longlong(S), int(relu), _stream())
+    if out == torch.bfloat16:
+        y = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16)
+        _lib.call("ecm_gn3d_apply_bf16" if x_bf16 else "ecm_gn3d_apply_f32_bf16", *args, _p(y), *tail)
+        return y
+    y32 = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    y16 = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16) if out == "dual" else None
+    _lib.call("ecm_gn3d_apply_bf16_f32", *args, _p(y32), _p(y16), *tail)
+    return (y32, y16) if out == "dual" else y32
 
 
 def _classifier_tail_bf16(x, gamma, beta, w):
-    _bf16_no_grad("classifier_tail")
+    _AGG.no_grad("classifier_tail")
     _chk_bf16(x)
     _chk(gamma, beta, w)
     _need(x.dim() == 5 and x.numel() > 0 and x.shape[1] == 32 and gamma.numel() == 32 == beta.numel()
@@ -1703,7 +1723,7 @@ def _classifier_tail_bf16(x, gamma, beta, w):
           lambda: f"classifier_tail (bf16): x {tuple(x.shape)}, gamma {tuple(gamma.shape)}, w {tuple(w.shape)}: 32 -> 1 only")
     x, gamma, beta, w = _c(x), _c(gamma), _c(beta), _c(w)
     B, Cc, D, H, W = x.shape
-    stats = _gn_stats_any(x)
+    stats = _gn_stats(x)
     y = torch.empty(B, 1, D, H, W, device=x.device, dtype=torch.float32)
     _lib.call("ecm_conv3d_c1_gn_fwd_bf16", _p(x), _p(stats), _p(gamma), _p(beta), _p(w), _p(y), B, Cc, D, H, W, _stream())
     return y
@@ -1714,32 +1734,18 @@ def _classifier_tail_bf16(x, gamma, beta, w):
 # maps (csrc/bf16_encoder.hip: bf16 operands on the matrix cores, fp32 accumulation, one rounding per output); its three
 # results stay fp32.  Independent of aggregation_dtype; process-wide, inference only, and the fp32 path outside the block is
 # untouched.  Weights stay fp32 parameters, packed to bf16 images per call (cached under frozen_weights(), key "bf16_conv2d").
-_ENC_DTYPE = torch.float32
+_ENC = _Bf16Switch("encoder_dtype", "the bf16 encoder")
 
 
-@_contextlib.contextmanager
 def encoder_dtype(dtype):
     """torch.float32 (the default; a no-op) or torch.bfloat16 for the 2-D feature encoder inside the block; nests and
     restores the previous setting on exit.  bf16 is inference only: run the model under torch.no_grad()."""
-    global _ENC_DTYPE
-    if dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError(f"encoder_dtype: {dtype} is not supported (torch.float32 or torch.bfloat16)")
-    prev, _ENC_DTYPE = _ENC_DTYPE, dtype
-    try:
-        yield
-    finally:
-        _ENC_DTYPE = prev
+    return _ENC.scope(dtype)
 
 
 def encoder_bf16():
     """True inside an encoder_dtype(torch.bfloat16) block."""
-    return _ENC_DTYPE == torch.bfloat16
-
-
-def _enc_no_grad(what):
-    if torch.is_grad_enabled():
-        raise RuntimeError(f"{what}: the bf16 encoder has no backward (inference only); run the model under torch.no_grad() "
-                           "or leave the encoder_dtype(torch.bfloat16) block")
+    return _ENC.on()
 
 
 def conv2d_bf16_supported(Ci, Co, k, stride, dil):
@@ -1767,7 +1773,7 @@ def conv2d_bf16(x, w, stride=1, dil=1, fork=False, out_dtype=torch.bfloat16):
     """Conv2d(bias=False) of the bf16 encoder on a bf16 x [B,Ci,H,W]: 3x3 (padding = dil; stride 1 with dilation 1|2|4, or
     stride 2) or 1x1 (stride 1|2).  out_dtype torch.float32: the result leaves the encoder in fp32 (rounded nowhere).
     fork=True: returns (y, x) -- x for the skip connection (no backward here)."""
-    _enc_no_grad("conv2d_bf16")
+    _ENC.no_grad("conv2d_bf16")
     _chk_bf16(x)
     _chk(w)
     _need(x.dim() == 4 and w.dim() == 4 and w.shape[1] == x.shape[1] and w.shape[2] == w.shape[3] and x.numel() > 0
@@ -1787,20 +1793,5 @@ def conv2d_bf16(x, w, stride=1, dil=1, fork=False, out_dtype=torch.bfloat16):
 def group_norm_act_bf16_f32(x, gamma, beta, skip=None, relu=False, dual=False):
     """relu?(GroupNorm32(x)*gamma+beta (+ skip)) of a bf16 x written in fp32 -- the encoder's results.  dual=True: returns
     (y32, y16), the same values also rounded to bf16 in the same pass for the next bf16 layer."""
-    _enc_no_grad("group_norm_act_bf16_f32")
-    _chk_bf16(x, skip)
-    _chk(gamma, beta)
-    _need(x.dim() >= 3 and x.numel() > 0 and x.shape[1] % GN_GROUPS == 0 and gamma.numel() == x.shape[1] == beta.numel()
-          and (skip is None or skip.shape == x.shape),
-          lambda: f"group_norm_act_bf16_f32: x {tuple(x.shape)}, gamma {tuple(gamma.shape)}, skip "
-                  f"{None if skip is None else tuple(skip.shape)}: {GN_GROUPS} groups over C channels, bf16 skip of x's shape")
-    x, gamma, beta = _c(x), _c(gamma), _c(beta)
-    skip = _c(skip) if skip is not None else None
-    B, Cc = x.shape[:2]
-    S = x.numel() // (B * Cc)
-    stats = _gn_stats_any(x)
-    y32 = torch.empty(x.shape, device=x.device, dtype=torch.float32)
-    y16 = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16) if dual else None
-    _lib.call("ecm_gn3d_apply_bf16_f32", _p(x), _p(stats), _p(gamma), _p(beta), _p(skip), _p(y32), _p(y16), B, Cc,
-              C.c_longlong(S), int(relu), _stream())
-    return (y32, y16) if dual else y32
+    _ENC.no_grad("group_norm_act_bf16_f32")
+    return _gn_apply_two_stage(x, gamma, beta, skip, relu, "dual" if dual else torch.float32)

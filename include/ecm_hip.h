@@ -248,15 +248,34 @@ int ecm_conv2d_c1_wgrad(const float* x, const float* gy, const float* y, float* 
  * scratch for every call: >= ecm_gn3d_scratch_bytes(B,C,S).
  * fwd: y = relu?( (x-mean)*rstd*gamma[c]+beta[c] (+ skip) ) (skip may be NULL) and mean_rstd [B,32,2] in ONE pass over x
  *      (a cluster of co-resident workgroups keeps the span in registers across the reduction); shapes that do not fit
- *      that kernel run stats + apply.  stats / apply are also exported on their own. */
+ *      that kernel run the two-stage forward below. */
 long long ecm_gn3d_scratch_bytes(int B, int C, long long S);
 int ecm_gn3d_fwd(const float* x, const float* gamma, const float* beta, const float* skip, float* y,
                  float* mean_rstd, void* scratch, long long scratch_bytes, int B, int C, long long S,
                  int relu, float eps, void* stream);
+/* The two-stage forward, also the storage conversions of the bf16 inference paths (ops.aggregation_dtype / encoder_dtype).
+ * bf16 travels as its bit pattern (unsigned short); every bf16 output is rounded once (round to nearest even, NaN stays NaN).
+ * stats: mean_rstd [B,32,2] fp32 of an fp32 or (_bf16) a bf16 x, one variance formulation for both; scratch >=
+ * ecm_gn3d_scratch_bytes(B,C,S).  apply: y = relu?( GroupNorm(x)*gamma + beta (+ skip) ), skip NULL or of x's shape, from
+ * mean_rstd of the matching stats call:
+ *   ecm_gn3d_apply           fp32 x, fp32 skip -> fp32 y
+ *   ecm_gn3d_apply_bf16      bf16 x, bf16 skip -> bf16 y
+ *   ecm_gn3d_apply_f32_bf16  fp32 x, bf16 skip -> bf16 y   (the boundary into the bf16 aggregation region)
+ *   ecm_gn3d_apply_bf16_f32  bf16 x, bf16 skip -> fp32 y32 and, with y16 non-NULL, the same values rounded to bf16 (the
+ *                            encoder's results; y16 for those that also feed its next layer) */
 int ecm_gn3d_stats(const float* x, float* mean_rstd, void* scratch, long long scratch_bytes,
                    int B, int C, long long S, float eps, void* stream);
+int ecm_gn3d_stats_bf16(const unsigned short* x, float* mean_rstd, void* scratch, long long scratch_bytes,
+                        int B, int C, long long S, float eps, void* stream);
 int ecm_gn3d_apply(const float* x, const float* mean_rstd, const float* gamma, const float* beta,
                    const float* skip, float* y, int B, int C, long long S, int relu, void* stream);
+int ecm_gn3d_apply_bf16(const unsigned short* x, const float* mean_rstd, const float* gamma, const float* beta,
+                        const unsigned short* skip, unsigned short* y, int B, int C, long long S, int relu, void* stream);
+int ecm_gn3d_apply_f32_bf16(const float* x, const float* mean_rstd, const float* gamma, const float* beta,
+                            const unsigned short* skip, unsigned short* y, int B, int C, long long S, int relu, void* stream);
+int ecm_gn3d_apply_bf16_f32(const unsigned short* x, const float* mean_rstd, const float* gamma, const float* beta,
+                            const unsigned short* skip, float* y32, unsigned short* y16, int B, int C, long long S, int relu,
+                            void* stream);
 /* The one-pass forms of ecm_gn3d_fwd / ecm_gn3d_bwd make workgroups of one launch wait for each other (a cluster of
  * <= 128 workgroups per (sample, group) span exchanges partial sums).  Members are assigned by tickets drawn at run
  * time, so progress needs only one cluster's worth of this launch's workgroups running, whatever else shares the
@@ -368,6 +387,7 @@ int ecm_stereo_loss_bwd(const float* p1, const float* p2, const float* p3, const
                         float w1, float w2, float w3, void* stream);
 
 /* ---- opt-in bf16 inference of the 3-D aggregation stack (ops.aggregation_dtype; bf16_infer.hip) ------------------------
+ * (Its GroupNorm is the two-stage forward above: ecm_gn3d_stats_bf16, ecm_gn3d_apply_bf16 / _f32_bf16.)
  * Forward only.  Volumes are contiguous bf16 NCDHW (unsigned short = the bf16 bit pattern), weights and GroupNorm
  * parameters fp32; products accumulate in fp32 and every output is rounded once to bf16 (round to nearest even, NaN stays
  * NaN).  No atomics: bit-reproducible.
@@ -381,22 +401,13 @@ int ecm_conv3d_k3_bf16_fwd(const unsigned short* x, const unsigned short* wpacke
 /* ConvTranspose3d k3 stride 2 pad 1 output_padding 1, no bias (cmfsm.py:262-268): y [B,Co,2D,2H,2W].  Ci, Co in {32, 64}. */
 int ecm_deconv3d_k3s2_bf16_fwd(const unsigned short* x, const unsigned short* wpacked, unsigned short* y,
                                int B, int Ci, int Co, int D, int H, int W, void* stream);
-/* GroupNorm(32) statistics of a bf16 volume: mean_rstd [B,32,2] fp32 as ecm_gn3d_stats (same variance formulation);
- * scratch >= ecm_gn3d_scratch_bytes(B, C, S). */
-int ecm_gn3d_stats_bf16(const unsigned short* x, float* mean_rstd, void* scratch, long long scratch_bytes,
-                        int B, int C, long long S, float eps, void* stream);
-/* y = bf16( relu?( GroupNorm(x)*gamma + beta (+ skip) ) ), skip bf16 or NULL; _f32_bf16: x fp32 (its statistics from
- * ecm_gn3d_stats) -- the boundary into the bf16 region. */
-int ecm_gn3d_apply_bf16(const unsigned short* x, const float* mean_rstd, const float* gamma, const float* beta,
-                        const unsigned short* skip, unsigned short* y, int B, int C, long long S, int relu, void* stream);
-int ecm_gn3d_apply_f32_bf16(const float* x, const float* mean_rstd, const float* gamma, const float* beta,
-                            const unsigned short* skip, unsigned short* y, int B, int C, long long S, int relu, void* stream);
 /* The classifier tail (ecm_conv3d_c1_gn_fwd) reading a bf16 x: relu(GroupNorm(x)) -> Conv3d(32 -> 1) with fp32 output
  * y [B,1,D,H,W]; statistics from ecm_gn3d_stats_bf16. */
 int ecm_conv3d_c1_gn_fwd_bf16(const unsigned short* x, const float* mean_rstd, const float* gamma, const float* beta,
                               const float* w, float* y, int B, int Ci, int D, int H, int W, void* stream);
 
 /* ---- opt-in bf16 inference of the 2-D feature encoder (ops.encoder_dtype; bf16_encoder.hip) -----------------------------
+ * (Its GroupNorm is the two-stage forward above: ecm_gn3d_stats_bf16, ecm_gn3d_apply_bf16_f32.)
  * Forward only; replaces the encoder's Conv2d / GroupNorm layers after the stem (cmfsm.py:126-236).  Maps are contiguous
  * bf16 NCHW (unsigned short = the bf16 bit pattern), weights fp32 parameters packed to a bf16 image; products accumulate in
  * fp32 and every output is rounded once (round to nearest even, NaN stays NaN).  No atomics: bit-reproducible.
@@ -408,11 +419,6 @@ int ecm_conv2d_bf16_pack_weight(const float* w, unsigned short* packed, int Ci, 
  * out_f32 = 1 (the layers whose result leaves the encoder).  Ci % 16 == 0, Co % 32 == 0; any H, W >= 1. */
 int ecm_conv2d_bf16_fwd(const unsigned short* x, const unsigned short* wpacked, void* y, int B, int Ci, int Co, int H, int W,
                         int k, int stride, int dil, int out_f32, void* stream);
-/* y32 = relu?( GroupNorm(x)*gamma + beta (+ skip) ) in fp32 from a bf16 x (statistics from ecm_gn3d_stats_bf16), skip bf16
- * or NULL; y16 non-NULL: the same values rounded to bf16 as well (the encoder's results that also feed its next layer). */
-int ecm_gn3d_apply_bf16_f32(const unsigned short* x, const float* mean_rstd, const float* gamma, const float* beta,
-                            const unsigned short* skip, float* y32, unsigned short* y16, int B, int C, long long S, int relu,
-                            void* stream);
 
 #ifdef __cplusplus
 }

@@ -46,12 +46,20 @@ __device__ __forceinline__ float ld(const u16* p, long long i) { return bf2f(p[i
 // sixteenths; smallest and largest sample dropped), or the plain mean of a span shorter than 16: a single outlier among the
 // samples is discarded outright, and a typical span gives |K - mean| ~ std / 4.  Every workgroup of a span and the
 // finishing stage evaluate the same expression in the same order, so they agree bit for bit.
+// The pivot of a bf16 span is rounded to a bf16 value.  bf16 data lie on a coarse grid, so with a full-precision K the low bits
+// of every d = x - K are those of -K: the rounding of d, and of the k-th addition to a thread's running sum, is then the SAME in
+// every thread instead of independent, and the errors add up coherently -- the mean of a 40 000-element bf16 span came out
+// 8e-7 from the fp64 mean of the same values, 20x torch's fp32 (tests/test_hip_groupnorm_fp64.py; fp32 data: 4e-8).  With K on
+// the grid d is exact and the sums stay (nearly) so; the pivot only has to be NEAR the mean, which 8 bits of it are.
+__device__ __forceinline__ float gn_pivot_of(const float*, float k) { return k; }
+__device__ __forceinline__ float gn_pivot_of(const u16*, float k) { return bf2f(f2bf(k)); }
+
 template <class T>
 __device__ __forceinline__ float gn_pivot(const T* __restrict__ p, long long n) {
     float s = 0.f;
     if (n < 16) {
         for (long long i = 0; i < n; ++i) s += ld(p, i);
-        return s / (float)n;
+        return gn_pivot_of(p, s / (float)n);
     }
     const long long st = n / 16;
     float lo = ld(p, st >> 1), hi = lo;
@@ -63,11 +71,11 @@ __device__ __forceinline__ float gn_pivot(const T* __restrict__ p, long long n) 
         lo = fminf(lo, v);
         hi = fmaxf(hi, v);
     }
-    return (s - lo - hi) * (1.0f / 14.0f);
+    return gn_pivot_of(p, (s - lo - hi) * (1.0f / 14.0f));
 }
 
 // One 16-byte vector of stage 1 into (sum d, sum d^2).  The summation order differs between the types and is part of the
-// results (mean_rstd, and through it every output, is bit-identical to what each type's kernel has always computed):
+// results (for fp32, mean_rstd and through it every output is bit-identical to what its kernel has always computed):
 // fp32 sums its 4 elements pairwise, bf16 adds its 8 elements to the running sums one pair at a time.
 __device__ __forceinline__ void stats_vec(const float* p, float K, float& s, float& q) {
     float4 v = *reinterpret_cast<const float4*>(p);
@@ -97,7 +105,23 @@ __global__ __launch_bounds__(THREADS) void gn_stats_partial(const T* __restrict_
     const long long beg = (long long)blockIdx.x * CHUNK;
     const long long end = beg + CHUNK < n ? beg + CHUNK : n;
     float s = 0.f, q = 0.f;
-    if (n % VEC == 0) {                                            // span start and chunk bounds are 16-byte aligned
+    if constexpr (std::is_same_v<T, u16>) {
+        // bf16 data: d = x - K is a multiple j * g of the grid step, and j^2 mod 8 is only ever 0, 1 or 4 -- added to a running
+        // fp32 sum that keeps fewer bits, d^2 is rounded DOWN or not at all, never up, in every thread alike: the variance came
+        // out low and rstd 3.3e-7 (6 x torch's fp32) from fp64 at 80 000 elements (tests/test_hip_groupnorm_fp64.py).  The
+        // thread's running sums are therefore kept in double (one vector's 8 terms in fp32, as before); rounded once at the end.
+        double ds = 0.0, dq = 0.0;
+        if (n % VEC == 0) {                                        // span start and chunk bounds are 16-byte aligned
+            for (long long i = beg + threadIdx.x * VEC; i < end; i += THREADS * VEC) {
+                float vs = 0.f, vq = 0.f;
+                stats_vec(p + i, K, vs, vq);
+                ds += (double)vs; dq += (double)vq;
+            }
+        } else {
+            for (long long i = beg + threadIdx.x; i < end; i += THREADS) { const double v = (double)(ld(p, i) - K); ds += v; dq += v * v; }
+        }
+        s = (float)ds; q = (float)dq;
+    } else if (n % VEC == 0) {                                     // span start and chunk bounds are 16-byte aligned
         for (long long i = beg + threadIdx.x * VEC; i < end; i += THREADS * VEC) stats_vec(p + i, K, s, q);
     } else {
         for (long long i = beg + threadIdx.x; i < end; i += THREADS) { const float v = ld(p, i) - K; s += v; q += v * v; }

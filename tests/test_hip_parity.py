@@ -202,6 +202,7 @@ def test_costvol_conv3d_split(ecm, B, h, w, D):
 
 
 # ------------------------------------------------------------------ GroupNorm
+# (a smoke-level comparison with torch fp32; the sharp check of every kernel path against fp64 is tests/test_hip_groupnorm_fp64.py)
 @pytest.mark.parametrize("B,C,dims,relu,skip", [(1, 32, (4, 6, 10), True, False), (2, 64, (3, 5, 7), True, True),
                                                 (1, 32, (8, 8, 8), False, True), (2, 32, (2, 3, 5), False, False),
                                                 (1, 64, (16, 24, 40), True, True),

@@ -15,6 +15,7 @@ Deliberate deviations (documented in DESIGN.md):
 from __future__ import annotations
 
 import math
+import os as _os
 
 import torch
 import torch.nn as nn
@@ -28,7 +29,6 @@ NUM_GROUPS = 32  # cmfsm.py:31-33
 # exactly the reference's op sequence (cmfsm.py:667-684).  False (default): the same result from class-indexed 2-D
 # convolutions of the feature maps without the 4-D tensor (ops.costvol_conv3d).  Env ECM_EXPLICIT_COST_VOLUME=1 or
 # set `models.EXPLICIT_COST_VOLUME = True`.
-import os as _os
 EXPLICIT_COST_VOLUME = _os.environ.get("ECM_EXPLICIT_COST_VOLUME", "0") == "1"
 # Nothing in this package falls back to a vendor library silently: a layer outside the native kernels raises unless
 # ECM_ALLOW_FALLBACK=1, and every time a slower-than-designed path IS taken (that opt-in, or a dilated stage whose map is
@@ -378,6 +378,22 @@ class feature_extraction(nn.Module):
             return layer(x)
         return ops.phase_merge(layer(ops.phase_split(x, d)), d)
 
+    def _tail(self, x, out_dtype=None):
+        """layer2 -> layer3/4 -> pooled pyramid -> last conv: layer1's output -> the low-resolution 32-channel feature.
+        `out_dtype` (bf16 encoder): the final 1x1 writes its result in that dtype instead of x's."""
+        output_raw = self.layer2(x)
+        if self._raw_is_layer3:                       # cmfsm_sub_16.py:205-207
+            output_raw = self._run_layer(self.layer3, output_raw)
+            output_skip = self._run_layer(self.layer4, output_raw)
+        else:
+            output_skip = self._run_layer(self.layer4, self._run_layer(self.layer3, output_raw))
+        size = output_skip.shape[-2:]
+        pooled = _pyramid_pools(output_skip, [getattr(self, f"branch{i}")[0] for i in (1, 2, 3, 4)])
+        pyramid = [bilinear_upsample(_seq_fused(getattr(self, f"branch{i}"), pooled[i - 1], start=1), size) for i in (4, 3, 2, 1)]
+        last = list(self.lastconv_16 if self._raw_is_layer3 else self.lastconv)
+        h = _seq_fused(last[:-1], torch.cat([output_raw, output_skip] + pyramid, 1))
+        return last[-1](h) if out_dtype is None else last[-1](h, out_dtype=out_dtype)
+
     def forward(self, x, head=None):
         """`head` (extension): the caller only needs the first `head` samples of the full-resolution map (third result); their
         gradient is then folded into the map's gradient in place (ops.fork_head) instead of through a zero-padded copy.
@@ -400,17 +416,7 @@ class feature_extraction(nn.Module):
             if head is not None:
                 output_all, output_head = ops.fork_head(output_all, head)
             output_rt = self.layer1(_seq_fused(self.secondconv, output_all))
-        output_raw = self.layer2(output_rt)
-        if self._raw_is_layer3:                       # cmfsm_sub_16.py:205-207
-            output_raw = self._run_layer(self.layer3, output_raw)
-            output_skip = self._run_layer(self.layer4, output_raw)
-        else:
-            output_skip = self._run_layer(self.layer4, self._run_layer(self.layer3, output_raw))
-        size = output_skip.shape[-2:]
-        pooled = _pyramid_pools(output_skip, [getattr(self, f"branch{i}")[0] for i in (1, 2, 3, 4)])
-        pyramid = [bilinear_upsample(_seq_fused(getattr(self, f"branch{i}"), pooled[i - 1], start=1), size) for i in (4, 3, 2, 1)]
-        last = self.lastconv_16 if self._raw_is_layer3 else self.lastconv
-        feature = _seq_fused(last, torch.cat([output_raw, output_skip] + pyramid, 1))
+        feature = self._tail(output_rt)
         return feature, output_rt, (output_all if output_head is None else output_head)
 
     @staticmethod
@@ -445,17 +451,7 @@ class feature_extraction(nn.Module):
         else:                                                   # "none" (cmf): layer1's output is the map
             output_rt, h = self._layer_dual(self.layer1, _seq_fused(fc[2:], h))
             output_all = output_rt
-        output_raw = self.layer2(h)
-        if self._raw_is_layer3:
-            output_raw = self._run_layer(self.layer3, output_raw)
-            output_skip = self._run_layer(self.layer4, output_raw)
-        else:
-            output_skip = self._run_layer(self.layer4, self._run_layer(self.layer3, output_raw))
-        size = output_skip.shape[-2:]
-        pooled = _pyramid_pools(output_skip, [getattr(self, f"branch{i}")[0] for i in (1, 2, 3, 4)])
-        pyramid = [bilinear_upsample(_seq_fused(getattr(self, f"branch{i}"), pooled[i - 1], start=1), size) for i in (4, 3, 2, 1)]
-        last = list(self.lastconv_16 if self._raw_is_layer3 else self.lastconv)
-        feature = last[-1](_seq_fused(last[:-1], torch.cat([output_raw, output_skip] + pyramid, 1)), out_dtype=torch.float32)
+        feature = self._tail(h, out_dtype=torch.float32)
         return feature, output_rt, (output_all if head is None else output_all[:head])
 
 
@@ -555,66 +551,6 @@ class eight_related_context_mapping(nn.Module):
         return tuple(w9[:, n:n + 1] for n in range(9))
 
 
-class cmfsm(nn.Module):
-    """cmfsm.py:594-774.  forward(left, right) -> (pred1, pred2, pred3), each [B,1,H,W] in pixels."""
-
-    def __init__(self, maxdisp=192):
-        super().__init__()
-        self.maxdisp = maxdisp
-        self.feature_extraction = feature_extraction()
-        self.dres0 = nn.Sequential(convbn_3d(64, 32, 3, 1, 1), HipReLU(inplace=True),
-                                   convbn_3d(32, 32, 3, 1, 1), HipReLU(inplace=True))
-        self.dres1 = nn.Sequential(convbn_3d(32, 32, 3, 1, 1), HipReLU(inplace=True),
-                                   convbn_3d(32, 32, 3, 1, 1))
-        self.dres2 = hourglass(32)
-        self.dres3 = hourglass(32)
-        self.dres4 = hourglass(32)
-        for i in (1, 2, 3):
-            setattr(self, f"classif{i}", nn.Sequential(
-                convbn_3d(32, 32, 3, 1, 1), HipReLU(inplace=True),
-                HipConv3d(32, 1, kernel_size=3, padding=1, stride=1, bias=False)))
-        self.mapping_matrix = eight_related_context_mapping()
-        # the reference re-initialises every Conv2d/Conv3d with the PSMNet rule (cmfsm.py:638-645)
-        for m in self.modules():
-            if isinstance(m, nn.Conv2d):
-                m.weight.data.normal_(0, math.sqrt(2.0 / (m.kernel_size[0] * m.kernel_size[1] * m.out_channels)))
-            elif isinstance(m, nn.Conv3d):
-                k = m.kernel_size
-                m.weight.data.normal_(0, math.sqrt(2.0 / (k[0] * k[1] * k[2] * m.out_channels)))
-
-    def hot_path(self, lr_l, hr_l, lr_r):
-        """Everything after the encoder (cmfsm.py:659-774)."""
-        scale = hr_l.shape[-1] // lr_l.shape[-1]
-        w9 = self.mapping_matrix.weights(lr_l, hr_l)                                   # :664
-        cost0 = _costvol_dres0(self.dres0, lr_l, lr_r, self.maxdisp // scale)          # :667-684
-        cost0 = _cbn(self.dres0[2], cost0, relu=True)
-        y, cost0 = _cbn(self.dres1[0], cost0, relu=True, fork=True)                    # :685
-        cost0 = _cbn(self.dres1[2], y, skip=cost0)
-        # out1 / out2 feed the next hourglass AND their classifier: the classifier's first convolution hands them back
-        # (fork), so that its data gradient absorbs the gradient arriving through the hourglass
-        # cost0 has four consumers (first hourglass + three residual adds): one 4-ary gradient sum instead of three adds
-        c_in, c_r1, c_r2, c_r3 = ops.fork(cost0, 4)
-        # pre1 has four consumers (two inside dres2, the skips of dres3 and dres4): one 4-ary gradient sum
-        out1, (pre1a, pre1b), post1 = self.dres2(c_in, None, None, residual=c_r1, pre_uses=2)   # :686-687
-        c1, out1 = _classifier(self.classif1, out1, fork=True)                         # :695
-        out2, pre2, post2 = self.dres3(out1, pre1a, post1, residual=c_r2)              # :689-690
-        c2, out2 = _classifier(self.classif2, out2, fork=True)                         # :724
-        out3, pre3, post3 = self.dres4(out2, pre1b, post2, residual=c_r3)              # :692-693
-        c3 = _classifier(self.classif3, out3)                                          # :747
-        disp = ops.softargmin_heads(torch.stack([c1, c2, c3], 0))                      # :703-706,725-728,748-753
-        preds = ops.ecm_aggregate9(disp, w9, scale)                                    # :709-723 (x3)
-        return preds[0].unsqueeze(1), preds[1].unsqueeze(1), preds[2].unsqueeze(1)
-
-    def forward(self, left, right):
-        # cmfsm.py:657-658 runs the shared encoder twice; both images go through it as ONE batch here (GroupNorm has no
-        # cross-sample statistics, so the result is identical) -- half the launches, better-filled small layers.
-        B = left.shape[0]
-        if torch.is_grad_enabled():
-            ops.pace_side_streams()        # host run-ahead bound: the previous step's side-stream weight gradients have finished
-        lr, _, hr = self.feature_extraction(torch.cat([left, right], 0), head=B)      # hr: the left images' map only
-        return self.hot_path(lr[:B], hr, lr[B:])
-
-
 class similarity_measure2(nn.Module):
     """3->3->2->1 1x1-conv MLP on the offset table (cm_sub_4.py: instantiated, never used in forward)."""
 
@@ -657,8 +593,11 @@ class six_related_context_mapping(nn.Module):
 
 class _ECMNet(nn.Module):
     """Shared skeleton of the registered architectures: encoder -> cost volume -> dres0/1 -> 1 or 3 hourglasses ->
-    classifiers -> head.  Subclasses set ENCODER, HOURGLASSES and HEAD exactly as their reference file does."""
-    ENCODER, HOURGLASSES, HEAD, SIM2 = "cmfsm", 3, "eight", False
+    classifiers (`_aggregate`) -> head (`hot_path`).  Subclasses set ENCODER, HOURGLASSES and HEAD exactly as their reference
+    file does.  PRE1_FORK: the first hourglass's `pre` has four consumers in a three-hourglass net (two inside that
+    hourglass, the skips of the other two); True sums their gradients with one ops.fork kernel, False leaves the sum to
+    autograd.  The two orders of summation differ in the last bit, so the attribute is part of each net's definition."""
+    ENCODER, HOURGLASSES, HEAD, SIM2, PRE1_FORK = "cmfsm", 3, "eight", False, False
 
     def __init__(self, maxdisp=192):
         super().__init__()
@@ -674,38 +613,52 @@ class _ECMNet(nn.Module):
             setattr(self, f"classif{i + 1}", nn.Sequential(
                 convbn_3d(32, 32, 3, 1, 1), HipReLU(inplace=True),
                 HipConv3d(32, 1, kernel_size=3, padding=1, stride=1, bias=False)))
-        if self.HEAD in ("five", "volume"):
+        if self.HEAD == "eight":
+            self.mapping_matrix = eight_related_context_mapping()
+        elif self.HEAD in ("five", "volume"):
             self.mapping_matrix = six_related_context_mapping(self.SIM2)
-        for m in self.modules():                                      # PSMNet init rule, e.g. cmfsm_sub_8.py:703-711
+        for m in self.modules():                                      # PSMNet init rule, e.g. cmfsm.py:638-645
             if isinstance(m, nn.Conv2d):
                 m.weight.data.normal_(0, math.sqrt(2.0 / (m.kernel_size[0] * m.kernel_size[1] * m.out_channels)))
             elif isinstance(m, nn.Conv3d):
                 k = m.kernel_size
                 m.weight.data.normal_(0, math.sqrt(2.0 / (k[0] * k[1] * k[2] * m.out_channels)))
 
+    def _aggregate(self, lr_l, lr_r, ndisp):
+        """The 3-D trunk (cmfsm.py:667-693 and every classifier's layers): cost volume -> dres0 -> dres1 -> the hourglasses
+        chained through the first one's `pre` and the previous one's `post` -> the classifiers.
+        Returns the list of raw classifier outputs [B,ndisp,h,w], one per hourglass."""
+        n = self.HOURGLASSES
+        cost0 = _costvol_dres0(self.dres0, lr_l, lr_r, ndisp)                          # :667-684
+        cost0 = _cbn(self.dres0[2], cost0, relu=True)
+        y, cost0 = _cbn(self.dres1[0], cost0, relu=True, fork=True)                    # :685
+        cost0 = _cbn(self.dres1[2], y, skip=cost0)
+        # cost0's consumers (first hourglass + one residual add per hourglass): one n-ary gradient sum instead of n adds
+        c_forks = ops.fork(cost0, n + 1)
+        pre_uses = max(n - 1, 1) if self.PRE1_FORK else 1
+        heads, x, post = [], c_forks[0], None
+        for i in range(n):
+            if i == 0:
+                out, pre, post = self.dres2(x, None, None, residual=c_forks[1], pre_uses=pre_uses)    # :686-687
+                pre1 = pre if pre_uses > 1 else (pre,) * (n - 1)          # one alias of `pre` per later hourglass
+            else:
+                out, _, post = getattr(self, f"dres{i + 2}")(x, pre1[i - 1], post, residual=c_forks[i + 1])   # :689-693
+            # `out` feeds the next hourglass AND its classifier: the classifier's first convolution hands it back (fork), so
+            # that its data gradient absorbs the gradient arriving through the hourglass
+            clf = getattr(self, f"classif{i + 1}")
+            if i + 1 < n:
+                c_i, x = _classifier(clf, out, fork=True)
+            else:
+                c_i = _classifier(clf, out)
+            heads.append(c_i)
+        return heads
+
     def hot_path(self, lr_l, hr_l, lr_r, hr_r, out_hw=None):
         scale = hr_l.shape[-1] // lr_l.shape[-1]
         planes = None
         if self.HEAD in ("five", "volume"):
             planes = self.mapping_matrix.planes(lr_l, hr_l, lr_r, hr_r)
-        cost0 = _costvol_dres0(self.dres0, lr_l, lr_r, self.maxdisp // scale)
-        cost0 = _cbn(self.dres0[2], cost0, relu=True)
-        y, cost0 = _cbn(self.dres1[0], cost0, relu=True, fork=True)
-        cost0 = _cbn(self.dres1[2], y, skip=cost0)
-        c_forks = ops.fork(cost0, self.HOURGLASSES + 1)     # first hourglass + one residual add per hourglass
-        heads, x, pre1, post = [], c_forks[0], None, None
-        for i in range(self.HOURGLASSES):
-            out, pre, post = getattr(self, f"dres{i + 2}")(x, pre1 if i > 0 else None, post, residual=c_forks[i + 1])
-            if i == 0:
-                pre1 = pre
-            clf = getattr(self, f"classif{i + 1}")
-            if i + 1 < self.HOURGLASSES:       # `out` also feeds the next hourglass: the classifier's conv hands it back
-                c_i, out = _classifier(clf, out, fork=True)
-            else:
-                c_i = _classifier(clf, out)
-            x = out
-            heads.append(c_i)
-        c = torch.stack(heads, 0)                                        # raw classifier outputs [NH,B,Dl,h,w]
+        c = torch.stack(self._aggregate(lr_l, lr_r, self.maxdisp // scale), 0)   # raw classifier outputs [NH,B,Dl,h,w]
         if self.HEAD == "five":                                          # cmfsm_sub_8.py:757-803 (heads NOT accumulated)
             disp = torch.cat([ops.softargmin_heads(c[k:k + 1]) for k in range(c.shape[0])], 0)
             m5 = planes[0]
@@ -728,6 +681,29 @@ class _ECMNet(nn.Module):
             ops.pace_side_streams()
         lr, _, hr = self.feature_extraction(torch.cat([left, right], 0))      # one encoder pass for both images
         return self.hot_path(lr[:B], hr[:B], lr[B:], hr[B:], out_hw=left.shape[-2:])
+
+
+class cmfsm(_ECMNet):
+    """cmfsm.py:594-774.  forward(left, right) -> (pred1, pred2, pred3), each [B,1,H,W] in pixels."""
+    ENCODER, HOURGLASSES, HEAD, PRE1_FORK = "cmfsm", 3, "eight", True
+
+    def hot_path(self, lr_l, hr_l, lr_r):
+        """Everything after the encoder (cmfsm.py:659-774)."""
+        scale = hr_l.shape[-1] // lr_l.shape[-1]
+        w9 = self.mapping_matrix.weights(lr_l, hr_l)                                   # :664
+        heads = self._aggregate(lr_l, lr_r, self.maxdisp // scale)                     # :667-693, 695, 724, 747
+        disp = ops.softargmin_heads(torch.stack(heads, 0))                             # :703-706,725-728,748-753
+        preds = ops.ecm_aggregate9(disp, w9, scale)                                    # :709-723 (x3)
+        return preds[0].unsqueeze(1), preds[1].unsqueeze(1), preds[2].unsqueeze(1)
+
+    def forward(self, left, right):
+        # cmfsm.py:657-658 runs the shared encoder twice; both images go through it as ONE batch here (GroupNorm has no
+        # cross-sample statistics, so the result is identical) -- half the launches, better-filled small layers.
+        B = left.shape[0]
+        if torch.is_grad_enabled():
+            ops.pace_side_streams()        # host run-ahead bound: the previous step's side-stream weight gradients have finished
+        lr, _, hr = self.feature_extraction(torch.cat([left, right], 0), head=B)      # hr: the left images' map only
+        return self.hot_path(lr[:B], hr, lr[B:])
 
 
 class cmfsm_sub_8(_ECMNet):
@@ -866,23 +842,7 @@ class cmf(_ECMNet):
 
     def hot_path(self, lr_l, lr_r, left, half):
         """Cost volume -> dres0/1 -> three hourglasses -> accumulated heads (cmf.py:394-436) -> decoder (cmf.py:437-449)."""
-        cost0 = _costvol_dres0(self.dres0, lr_l, lr_r, self.maxdisp // 4)
-        cost0 = _cbn(self.dres0[2], cost0, relu=True)
-        y, cost0 = _cbn(self.dres1[0], cost0, relu=True, fork=True)
-        cost0 = _cbn(self.dres1[2], y, skip=cost0)
-        c_forks = ops.fork(cost0, 4)
-        heads, x, pre1, post = [], c_forks[0], None, None
-        for i in range(3):                                             # dres4(out2, pre1, post2): cmf.py:413
-            out, pre, post = getattr(self, f"dres{i + 2}")(x, pre1, post, residual=c_forks[i + 1])
-            if i == 0:
-                pre1 = pre
-            clf = getattr(self, f"classif{i + 1}")
-            if i < 2:
-                c_i, out = _classifier(clf, out, fork=True)
-            else:
-                c_i = _classifier(clf, out)
-            x = out
-            heads.append(c_i)
+        heads = self._aggregate(lr_l, lr_r, self.maxdisp // 4)         # dres4(out2, pre1, post2): cmf.py:413
         disp = ops.softargmin_heads(torch.stack(heads, 0))            # [3,B,h,w], quarter-resolution units
         preds = self.srr(disp, left, lr_l, half)
         return preds[0], preds[1], preds[2]
@@ -902,7 +862,6 @@ class cmf(_ECMNet):
 _MODELS = {"cmfsm": cmfsm, "cmfsm_sub_8": cmfsm_sub_8, "cmfsm_sub_16": cmfsm_sub_16, "cm_sub_4": cm_sub_4,
            "cm_sub_8": cm_sub_8, "cm_sub_16": cm_sub_16, "bilinear_cmf": bilinear_cmf,
            "bilinear_cmf_sub_8": bilinear_cmf_sub_8, "bilinear_cmf_sub_16": bilinear_cmf_sub_16, "cmf": cmf}
-
 
 
 def get_model(name):

@@ -6,7 +6,9 @@ through `_lib.call`.  There is no eager/CPU fallback: a non-CUDA tensor or a mis
 """
 from __future__ import annotations
 
+import contextlib as _contextlib
 import ctypes as C
+import os as _os
 
 import torch
 
@@ -14,6 +16,47 @@ from . import _lib
 
 GN_GROUPS = 32
 GN_EPS = 1e-5
+
+
+# ------------------------------------------------------------------------------------ environment switches
+# Read once at import; tests and bench.py assign the module attributes afterwards, so every use reads them at call time.
+#
+# Stride-1 3x3(x3) convolutions -- forward and data gradient -- run on the Winograd F(2x2,3x3) kernel (csrc/conv_wino.hip):
+# 2.25x fewer matrix-core multiplies, fp32 throughout.  ECM_WINOGRAD=0 (or ops.WINOGRAD = False) selects the direct
+# implicit-GEMM kernels for everything; both are parity-tested.
+WINOGRAD = _os.environ.get("ECM_WINOGRAD", "1") != "0"
+WINO2D_MIN_CI = int(_os.environ.get("ECM_WINO2D_MIN_CI", "32"))
+WINOGRAD_WGRAD = _os.environ.get("ECM_WINOGRAD_WGRAD", "1") != "0"
+
+# Weight gradients on a side stream.  A layer's weight gradient feeds nothing but the optimizer, while its data gradient is on
+# the critical path of backward together with the HBM-bound GroupNorm backward passes: launched on a second stream, the
+# matrix-bound weight-gradient kernels run under those passes instead of queueing between them (backward at batch 4:
+# 86.9 -> 82.3 ms, gradients bit-identical).  Ordering: the side stream waits for the main stream's position at launch (x and
+# gy are ready), the operands are recorded on it (the caching allocator must not recycle them under the kernel), and the main
+# stream waits for the side stream once per backward pass, from an engine callback that runs when the pass has finished.
+# That is safe exactly when nothing reads a weight gradient DURING the pass: it is therefore OFF unless the training harness
+# that owns the gradients' consumers turns it on (dist.FlatBucketDDP does: it joins before it gathers) or ECM_WGRAD_OVERLAP=1
+# asks for it; non-leaf weights (nn.DataParallel replicas, whose gradients flow on through Broadcast.backward), weights with
+# tensor hooks and weights that already HAVE a gradient (a layer used twice in one graph, accumulation over several passes:
+# AccumulateGrad then adds on the main stream at once) always stay on the main stream, and so does everything during graph
+# capture.  ECM_WGRAD_OVERLAP=0: never.
+_WGRAD_ENV = _os.environ.get("ECM_WGRAD_OVERLAP", "")
+WGRAD_OVERLAP = _WGRAD_ENV == "1"
+
+# Host run-ahead (round 4).  The operands of a side-stream launch are recorded on that stream, so the caching allocator hands
+# their blocks out again only once the side stream's work has FINISHED on the device -- unlike main-stream blocks, which it
+# recycles in stream order however far the host runs ahead.  A training loop that never synchronises (the host enqueues a step
+# in 23 ms, the device runs it in 124) therefore found none of the previous steps' blocks free and went to the driver for new
+# ones every step: 320 hipMalloc calls and 40.7 -> 137.5 GiB reserved over 15 steps, and a step time that depended on how fast
+# the driver could hand out memory (2x slower right after another process had released its own: the driver scrubs what it
+# hands out again).  So the host waits, at the start of a training forward (models: hot path) and in front of a pass's first side launch, for the
+# event recorded behind the PREVIOUS pass's join: at most one step's operands are ever pending, the allocator reaches its steady
+# state in the first step, and the device still has the optimiser step + the queued forward to run while the host catches up
+# (no bubble: measured step time unchanged on a fresh device).  ECM_WGRAD_PACE=0 turns the wait off (A/B only).
+_WGRAD_PACE = _os.environ.get("ECM_WGRAD_PACE", "1") != "0"
+
+# Launch order of a layer's weight gradient and data gradient (see _launch_pair): ECM_WGRAD_FIRST=0 queues the data gradient first.
+WGRAD_FIRST = _os.environ.get("ECM_WGRAD_FIRST", "1") == "1"
 
 
 def _p(t):
@@ -59,6 +102,21 @@ def _empty_like(t):
 
 def _scratch(nbytes, device):
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
+
+
+_SCRATCH = object()      # in an argument list: the place of an entry point's (scratch pointer, scratch bytes) pair
+
+
+def _call_scratch(device, query, sizes, name, *args, call=None, zero=None):
+    """Query `query(*sizes)` for the scratch bytes of entry point `name`, allocate them on `device` and call `name` with
+    `args`, the _SCRATCH marker replaced by (pointer, byte count); every other argument is passed through unchanged.
+    call: the caller (default _lib.call);  zero: the RuntimeError text for a size query that answers 0 (= unsupported)."""
+    nb = _lib.query(query, *sizes)
+    if zero is not None and nb == 0:
+        raise RuntimeError(zero)
+    buf = _scratch(nb, device)
+    at = next(i for i, a in enumerate(args) if a is _SCRATCH)
+    (call or _lib.call)(name, *args[:at], _p(buf), C.c_longlong(nb), *args[at + 1:])
 
 
 # ------------------------------------------------------------------------------------ a1 cost volume
@@ -244,64 +302,14 @@ def ecm_aggregate9(d, w9, scale):
 
 # ------------------------------------------------------------------------------------ a3 ECM weights
 _ECM_MLP_SIZES = (2112, 512, 128, 8)      # similarity_measure1's four 1x1 kernels: 66->32, 32->16, 16->8, 8->1
-class ECMWeights9(torch.autograd.Function):
-    """eight_related_context_mapping (cmfsm.py:443-593): lr [B,32,h,w], hr [B,32,H,W] -> w9 [B,9,H,W]."""
-
-    @staticmethod
-    def forward(ctx, lr, hr, W0, W1, W2, W3):
-        _chk(lr, hr, W0, W1, W2, W3)
-        _need(lr.dim() == 4 and hr.dim() == 4 and hr.shape[0] == lr.shape[0] and lr.shape[-1] > 0 and lr.shape[-2] > 0,
-              lambda: f"context weights: lr {tuple(lr.shape)}, hr {tuple(hr.shape)}: want [B,32,h,w] and [B,32,H,W]")
-        _need((W0.numel(), W1.numel(), W2.numel(), W3.numel()) == _ECM_MLP_SIZES,
-              lambda: f"context weights: the similarity MLP's kernels hold {_ECM_MLP_SIZES} values (cmfsm.py:400-427), got "
-                      f"{(W0.numel(), W1.numel(), W2.numel(), W3.numel())}")
-        lr, hr = _c(lr), _c(hr)
-        W0, W1, W2, W3 = (_c(t) for t in (W0, W1, W2, W3))
-        B, Cc, h, w = lr.shape
-        H, W = hr.shape[-2:]
-        s = W // w
-        if s % 2 != 0:
-            raise ValueError("odd scale between hr and lr features (the reference calls exit() here, cmfsm.py:448-449)")
-        if Cc != 32 or hr.shape[1] != 32 or H != h * s or W != w * s:
-            raise RuntimeError(f"ecm_weights9: unsupported shapes lr {tuple(lr.shape)} hr {tuple(hr.shape)}")
-        if s != 4:      # matrix_generation hard-codes scale 4 (cmfsm.py:392): the reference's forward fails in torch.cat otherwise
-            raise RuntimeError(f"eight_related_context_mapping exists at scale 4 only (got {s}): the reference's offset tables "
-                               "are 4 x 4 and its forward raises a shape error at any other scale")
-        w9 = torch.empty(B, 9, H, W, device=lr.device, dtype=lr.dtype)
-        nb = _lib.query("ecm_weights9_scratch_bytes", B, h, w)
-        scratch = _scratch(nb, lr.device)
-        _lib.call("ecm_weights9_fwd", _p(lr), _p(hr), _p(W0), _p(W1), _p(W2), _p(W3), _p(w9), _p(scratch),
-                  C.c_longlong(nb), B, h, w, s, _stream())
-        ctx.save_for_backward(lr, hr, W0, W1, W2, W3, w9)
-        ctx.s = s
-        return w9
-
-    @staticmethod
-    def backward(ctx, gw9):
-        lr, hr, W0, W1, W2, W3, w9 = ctx.saved_tensors
-        B, _, h, w = lr.shape
-        s = ctx.s
-        gw9 = _c(gw9)
-        glr, ghr = _empty_like(lr), _empty_like(hr)
-        gW = torch.empty(2112 + 512 + 128 + 8, device=lr.device, dtype=lr.dtype)
-        nb = _lib.query("ecm_weights9_bwd_scratch_bytes", B, h, w, s)
-        scratch = _scratch(nb, lr.device)
-        _lib.call("ecm_weights9_bwd", _p(lr), _p(hr), _p(W0), _p(W1), _p(W2), _p(W3), _p(w9), _p(gw9), _p(glr), _p(ghr),
-                  _p(gW), _p(scratch), C.c_longlong(nb), B, h, w, s, _stream())
-        return (glr, ghr, gW[:2112].view_as(W0), gW[2112:2624].view_as(W1), gW[2624:2752].view_as(W2),
-                gW[2752:].view_as(W3))
-
-
-def ecm_weights9(lr, hr, W0, W1, W2, W3):
-    return ECMWeights9.apply(lr, hr, W0, W1, W2, W3)
-
-
 _VARIANT_PLANES = {0: 9, 1: 5, 2: 3}
 
 
 class ContextWeights(torch.autograd.Function):
-    """General context-mapping weights: variant 0 eight_related (cmfsm.py:431-593), 1/2 six_related on the reference /
-    target image (cmfsm_sub_8.py:440-572).  lr [B,32,h,w], hr [B,32,H,W] -> [B,N,H,W]."""
+    """Context-mapping weights: variant 0 eight_related (cmfsm.py:431-593), 1/2 six_related on the reference / target
+    image (cmfsm_sub_8.py:440-572).  lr [B,32,h,w], hr [B,32,H,W] -> [B,N,H,W] with N = 9, 5, 3.
+    Variant 0 goes through the entry points it was introduced under (ecm_weights9_fwd / _bwd: thin wrappers of
+    ecm_context_weights_* in the library, and the names the benchmark's timers key on)."""
 
     @staticmethod
     def forward(ctx, lr, hr, W0, W1, W2, W3, variant):
@@ -317,15 +325,19 @@ class ContextWeights(torch.autograd.Function):
         H, W = hr.shape[-2:]
         s = W // w
         if s % 2 != 0:
-            raise ValueError("odd scale between hr and lr features (the reference calls exit() here)")
+            raise ValueError("odd scale between hr and lr features (the reference calls exit() here"
+                             + (", cmfsm.py:448-449)" if variant == 0 else ")"))
         if Cc != 32 or hr.shape[1] != 32 or H != h * s or W != w * s:
-            raise RuntimeError(f"context_weights: unsupported shapes lr {tuple(lr.shape)} hr {tuple(hr.shape)}")
+            raise RuntimeError(f"{'ecm_weights9' if variant == 0 else 'context_weights'}: unsupported shapes "
+                               f"lr {tuple(lr.shape)} hr {tuple(hr.shape)}")
         _need(variant in _VARIANT_PLANES, lambda: f"context weights: variant {variant} (0 eight-related, 1 / 2 six-related)")
+        if variant == 0 and s != 4:   # matrix_generation hard-codes scale 4 (cmfsm.py:392): the reference's forward fails in torch.cat otherwise
+            raise RuntimeError(f"eight_related_context_mapping exists at scale 4 only (got {s}): the reference's offset tables "
+                               "are 4 x 4 and its forward raises a shape error at any other scale")
         out = torch.empty(B, _VARIANT_PLANES[variant], H, W, device=lr.device, dtype=lr.dtype)
-        nb = _lib.query("ecm_weights9_scratch_bytes", B, h, w)
-        scratch = _scratch(nb, lr.device)
-        _lib.call("ecm_context_weights_fwd", _p(lr), _p(hr), _p(W0), _p(W1), _p(W2), _p(W3), _p(out), _p(scratch),
-                  C.c_longlong(nb), B, h, w, s, variant, _stream())
+        name, tail = ("ecm_weights9_fwd", (s,)) if variant == 0 else ("ecm_context_weights_fwd", (s, variant))
+        _call_scratch(lr.device, "ecm_weights9_scratch_bytes", (B, h, w), name, _p(lr), _p(hr), _p(W0), _p(W1), _p(W2), _p(W3),
+                      _p(out), _SCRATCH, B, h, w, *tail, _stream())
         ctx.save_for_backward(lr, hr, W0, W1, W2, W3, out)
         ctx.s, ctx.variant = s, variant
         return out
@@ -337,21 +349,25 @@ class ContextWeights(torch.autograd.Function):
         s, variant = ctx.s, ctx.variant
         g = _c(g)
         glr, ghr = _empty_like(lr), _empty_like(hr)
-        gW = torch.empty(2112 + 512 + 128 + 8, device=lr.device, dtype=lr.dtype)
-        nb = _lib.query("ecm_context_weights_bwd_scratch_bytes", B, h, w, s, variant)
-        if nb == 0:
-            raise RuntimeError(f"context_weights backward: unsupported scale {s} (the registered architectures' scales are 4, 8, 16)")
-        scratch = _scratch(nb, lr.device)
-        _lib.call("ecm_context_weights_bwd", _p(lr), _p(hr), _p(W0), _p(W1), _p(W2), _p(W3), _p(out), _p(g), _p(glr),
-                  _p(ghr), _p(gW), _p(scratch), C.c_longlong(nb), B, h, w, s, variant, _stream())
+        gW = torch.empty(sum(_ECM_MLP_SIZES), device=lr.device, dtype=lr.dtype)
+        if variant == 0:
+            name, tail, zero = "ecm_weights9_bwd", (s,), None
+        else:
+            name, tail = "ecm_context_weights_bwd", (s, variant)
+            zero = f"context_weights backward: unsupported scale {s} (the registered architectures' scales are 4, 8, 16)"
+        _call_scratch(lr.device, name + "_scratch_bytes", (B, h, w) + tail, name, _p(lr), _p(hr), _p(W0), _p(W1), _p(W2), _p(W3),
+                      _p(out), _p(g), _p(glr), _p(ghr), _p(gW), _SCRATCH, B, h, w, *tail, _stream(), zero=zero)
         return (glr, ghr, gW[:2112].view_as(W0), gW[2112:2624].view_as(W1), gW[2624:2752].view_as(W2),
                 gW[2752:].view_as(W3), None)
 
 
 def context_weights(lr, hr, W0, W1, W2, W3, variant):
-    if variant == 0:
-        return ECMWeights9.apply(lr, hr, W0, W1, W2, W3)
     return ContextWeights.apply(lr, hr, W0, W1, W2, W3, int(variant))
+
+
+def ecm_weights9(lr, hr, W0, W1, W2, W3):
+    """eight_related_context_mapping (cmfsm.py:443-593): lr [B,32,h,w], hr [B,32,H,W] -> w9 [B,9,H,W]."""
+    return ContextWeights.apply(lr, hr, W0, W1, W2, W3, 0)
 
 
 class VolumeMapping(torch.autograd.Function):
@@ -379,10 +395,9 @@ class VolumeMapping(torch.autograd.Function):
         NH, B, Dl, h, w = c.shape
         g = _c(g)
         gc, gm5, gmt3 = _empty_like(c), _empty_like(m5), _empty_like(mt3)
-        nb = _lib.query("ecm_volume_mapping_bwd_scratch_bytes", NH, B, Dl, h, w, ctx.scale)
-        scratch = _scratch(nb, c.device)
-        _lib.call("ecm_volume_mapping_bwd", _p(c), C.c_longlong(B * Dl * h * w), _p(m5), _p(mt3), _p(g), _p(gc), _p(gm5),
-                  _p(gmt3), _p(scratch), C.c_longlong(nb), NH, B, Dl, h, w, ctx.scale, _stream())
+        _call_scratch(c.device, "ecm_volume_mapping_bwd_scratch_bytes", (NH, B, Dl, h, w, ctx.scale), "ecm_volume_mapping_bwd",
+                      _p(c), C.c_longlong(B * Dl * h * w), _p(m5), _p(mt3), _p(g), _p(gc), _p(gm5), _p(gmt3), _SCRATCH,
+                      NH, B, Dl, h, w, ctx.scale, _stream())
         return gc, gm5, gmt3, None
 
 
@@ -414,10 +429,9 @@ class TrilinearSoftArgmin(torch.autograd.Function):
         Do, H, W = ctx.dims
         g = _c(g)
         gc = _empty_like(c)
-        nb = _lib.query("ecm_trilinear_softargmin_bwd_scratch_bytes", NH, B, Dl, h, w, H, W)
-        scratch = _scratch(nb, c.device)
-        _lib.call("ecm_trilinear_softargmin_bwd", _p(c), C.c_longlong(B * Dl * h * w), _p(g), _p(gc), _p(scratch),
-                  C.c_longlong(nb), NH, B, Dl, h, w, Do, H, W, _stream())
+        _call_scratch(c.device, "ecm_trilinear_softargmin_bwd_scratch_bytes", (NH, B, Dl, h, w, H, W),
+                      "ecm_trilinear_softargmin_bwd", _p(c), C.c_longlong(B * Dl * h * w), _p(g), _p(gc), _SCRATCH,
+                      NH, B, Dl, h, w, Do, H, W, _stream())
         return gc, None, None, None
 
 
@@ -444,21 +458,12 @@ def _pack_deconv(w):
     return packed
 
 
-# Stride-1 3x3(x3) convolutions -- forward and data gradient -- run on the Winograd F(2x2,3x3) kernel (csrc/conv_wino.hip):
-# 2.25x fewer matrix-core multiplies, fp32 throughout.  ECM_WINOGRAD=0 (or ops.WINOGRAD = False) selects the direct
-# implicit-GEMM kernels for everything; both are parity-tested.
-import os as _os
-WINOGRAD = _os.environ.get("ECM_WINOGRAD", "1") != "0"
-WINO2D_MIN_CI = int(_os.environ.get("ECM_WINO2D_MIN_CI", "32"))
-
-
 def _wino_ok(x):
     """Winograd kernels read the patch as pairs of neighbouring columns (rows of at least two elements) and address 32
     channel planes with 32-bit byte offsets (a [D,]H,W plane set of at most 2^24 elements); anything else takes the direct
     kernels."""
     vol = x.shape[-1] * x.shape[-2] * (x.shape[-3] if x.dim() == 5 else 1)
     return WINOGRAD and x.shape[-1] >= 2 and vol * 128 <= 0x80000000
-WINOGRAD_WGRAD = _os.environ.get("ECM_WINOGRAD_WGRAD", "1") != "0"
 
 
 def _wino_pack(w, kd, flip_transpose):
@@ -618,22 +623,6 @@ def _deconv_fwd(x, packed, Co, out_dhw):
     return y
 
 
-# Weight gradients on a side stream.  A layer's weight gradient feeds nothing but the optimizer, while its data gradient is on
-# the critical path of backward together with the HBM-bound GroupNorm backward passes: launched on a second stream, the
-# matrix-bound weight-gradient kernels run under those passes instead of queueing between them (backward at batch 4:
-# 86.9 -> 82.3 ms, gradients bit-identical).  Ordering: the side stream waits for the main stream's position at launch (x and
-# gy are ready), the operands are recorded on it (the caching allocator must not recycle them under the kernel), and the main
-# stream waits for the side stream once per backward pass, from an engine callback that runs when the pass has finished.
-# That is safe exactly when nothing reads a weight gradient DURING the pass: it is therefore OFF unless the training harness
-# that owns the gradients' consumers turns it on (dist.FlatBucketDDP does: it joins before it gathers) or ECM_WGRAD_OVERLAP=1
-# asks for it; non-leaf weights (nn.DataParallel replicas, whose gradients flow on through Broadcast.backward), weights with
-# tensor hooks and weights that already HAVE a gradient (a layer used twice in one graph, accumulation over several passes:
-# AccumulateGrad then adds on the main stream at once) always stay on the main stream, and so does everything during graph
-# capture.  ECM_WGRAD_OVERLAP=0: never.
-_WGRAD_ENV = _os.environ.get("ECM_WGRAD_OVERLAP", "")
-WGRAD_OVERLAP = _WGRAD_ENV == "1"
-
-
 def enable_wgrad_overlap(on=True):
     """Called by a harness that guarantees a join (join_side_streams) before any weight gradient is read; returns the
     previous setting.  The environment's ECM_WGRAD_OVERLAP=0 wins."""
@@ -644,18 +633,6 @@ def enable_wgrad_overlap(on=True):
 
 
 _SIDE = {}     # device index -> [side stream, join queued for the running backward pass, weights seen since the join, event behind the last join]
-
-# Host run-ahead (round 4).  The operands of a side-stream launch are recorded on that stream, so the caching allocator hands
-# their blocks out again only once the side stream's work has FINISHED on the device -- unlike main-stream blocks, which it
-# recycles in stream order however far the host runs ahead.  A training loop that never synchronises (the host enqueues a step
-# in 23 ms, the device runs it in 124) therefore found none of the previous steps' blocks free and went to the driver for new
-# ones every step: 320 hipMalloc calls and 40.7 -> 137.5 GiB reserved over 15 steps, and a step time that depended on how fast
-# the driver could hand out memory (2x slower right after another process had released its own: the driver scrubs what it
-# hands out again).  So the host waits, at the start of a training forward (models: hot path) and in front of a pass's first side launch, for the
-# event recorded behind the PREVIOUS pass's join: at most one step's operands are ever pending, the allocator reaches its steady
-# state in the first step, and the device still has the optimiser step + the queued forward to run while the host catches up
-# (no bubble: measured step time unchanged on a fresh device).  ECM_WGRAD_PACE=0 turns the wait off (A/B only).
-_WGRAD_PACE = _os.environ.get("ECM_WGRAD_PACE", "1") != "0"
 
 
 def pace_side_streams():
@@ -721,9 +698,6 @@ def _on_side(fn, w, *operands):
     return out
 
 
-WGRAD_FIRST = _os.environ.get("ECM_WGRAD_FIRST", "1") == "1"
-
-
 def _launch_pair(wfn, dfn):
     """Launch order of a layer's weight gradient (wfn, may go to the side stream) and data gradient (dfn, main stream).
     Weight gradient first: the side stream forks BEFORE the data gradient is queued, so the two start together.  The other
@@ -748,9 +722,8 @@ def _wino_wgrad_now(x, gy, Co, Ci, kd):
     B = x.shape[0]
     D, H, W = (x.shape[2:] if x.dim() == 5 else (1,) + tuple(x.shape[2:]))
     gw = torch.empty((Co, Ci) + ((3, 3, 3) if kd == 3 else (3, 3)), device=x.device, dtype=x.dtype)
-    nb = _lib.query("ecm_conv_wino_wgrad_scratch_bytes", B, Ci, Co, D, H, W, kd)
-    scratch = _scratch(nb, x.device)
-    _lib.call("ecm_conv_wino_wgrad", _p(x), _p(gy), _p(gw), _p(scratch), C.c_longlong(nb), B, Ci, Co, D, H, W, kd, _stream())
+    _call_scratch(x.device, "ecm_conv_wino_wgrad_scratch_bytes", (B, Ci, Co, D, H, W, kd), "ecm_conv_wino_wgrad",
+                  _p(x), _p(gy), _p(gw), _SCRATCH, B, Ci, Co, D, H, W, kd, _stream())
     return gw
 
 
@@ -764,11 +737,42 @@ def _wgrad(x, gy, Co, Ci, stride, w=None):
 def _wgrad_direct(x, gy, Co, Ci, stride):
     B, _, D, H, W = x.shape
     gw = torch.empty(Co, Ci, 3, 3, 3, device=x.device, dtype=x.dtype)
-    nb = _lib.query("ecm_conv3d_wgrad_scratch_bytes", B, Ci, Co, D, H, W, stride)
-    scratch = _scratch(nb, x.device)
-    _lib.call("ecm_conv3d_k3_wgrad", _p(x), _p(gy), _p(gw), _p(scratch), C.c_longlong(nb), B, Ci, Co, D, H, W, stride,
-              _stream())
+    _call_scratch(x.device, "ecm_conv3d_wgrad_scratch_bytes", (B, Ci, Co, D, H, W, stride), "ecm_conv3d_k3_wgrad",
+                  _p(x), _p(gy), _p(gw), _SCRATCH, B, Ci, Co, D, H, W, stride, _stream())
     return gw
+
+
+# The classifier's 32 -> 1 layer has its own kernels (conv3d_c1.hip).  With gn = (stats, gamma, beta) they read the RAW
+# input of the GroupNorm + ReLU in front of the layer and normalise + rectify it while they stage it (ClassifierTail).
+def _is_c1(w, stride):
+    return w.shape[0] == 1 and stride == 1 and w.shape[1] <= 32 and w.shape[1] % 8 == 0
+
+
+def _c1_fwd(x, w, gn=None):
+    B, Ci, D, H, W = x.shape
+    y = torch.empty(B, 1, D, H, W, device=x.device, dtype=x.dtype)
+    if gn is None:
+        _lib.call("ecm_conv3d_c1_fwd", _p(x), _p(w), _p(y), B, Ci, D, H, W, _stream())
+    else:
+        _lib.call("ecm_conv3d_c1_gn_fwd", _p(x), *map(_p, gn), _p(w), _p(y), B, Ci, D, H, W, _stream())
+    return y
+
+
+def _c1_dgrad(gy, w, x):
+    """Gradient w.r.t. the layer's (normalised) input, of x's shape."""
+    B, Ci, D, H, W = x.shape
+    g = torch.empty(x.shape, device=x.device, dtype=x.dtype)
+    _lib.call("ecm_conv3d_c1_dgrad", _p(gy), _p(w), _p(g), B, Ci, D, H, W, _stream())
+    return g
+
+
+def _c1_wgrad(x, gy, w, gn=None):
+    B, Ci, D, H, W = x.shape
+    g = _empty_like(w)
+    name, xs = ("ecm_conv3d_c1_wgrad", (_p(x),)) if gn is None else ("ecm_conv3d_c1_gn_wgrad", (_p(x), *map(_p, gn)))
+    _call_scratch(x.device, "ecm_conv3d_c1_wgrad_scratch_bytes", (B, Ci, D, H, W), name, *xs, _p(gy), _p(g), _SCRATCH,
+                  B, Ci, D, H, W, _stream())
+    return g
 
 
 class Conv3dK3(torch.autograd.Function):
@@ -783,10 +787,9 @@ class Conv3dK3(torch.autograd.Function):
         ctx.side_ok = w.is_contiguous()        # else the saved weight is a COPY and AccumulateGrad will re-lay the gradient out (see _on_side)
         x, w = _c(x), _c(w)
         ctx.set_materialize_grads(False)
-        if _is_c1(w, stride):
-            B, Ci, D, H, W = x.shape
-            y = torch.empty(B, 1, D, H, W, device=x.device, dtype=x.dtype)
-            _lib.call("ecm_conv3d_c1_fwd", _p(x), _p(w), _p(y), B, Ci, D, H, W, _stream())
+        ctx.c1 = _is_c1(w, stride)
+        if ctx.c1:
+            y = _c1_fwd(x, w)
         elif stride == 1 and _wino_ok(x):
             y = _wino_run(x, _wino_pack_fwd(ctx, x, w, 3, grad_mode), w.shape[0], 3)
         else:
@@ -802,24 +805,17 @@ class Conv3dK3(torch.autograd.Function):
             return gskip, None, None, None, None
         gy = _c(gy)
         Co, Ci = w.shape[0], w.shape[1]
+
         def wfn():
-            if _is_c1(w, ctx.stride):
-                B, _, D, H, W = x.shape
-                g = _empty_like(w)
-                nb = _lib.query("ecm_conv3d_c1_wgrad_scratch_bytes", B, Ci, D, H, W)
-                scratch = _scratch(nb, x.device)
-                _lib.call("ecm_conv3d_c1_wgrad", _p(x), _p(gy), _p(g), _p(scratch), C.c_longlong(nb), B, Ci, D, H, W,
-                          _stream())
-                return g
+            if ctx.c1:
+                return _c1_wgrad(x, gy, w)
             return _wgrad(x, gy, Co, Ci, ctx.stride, w if ctx.side_ok else None)
 
         def dfn():
-            if ctx.stride == 1 and _wino_ok(x) and not _is_c1(w, ctx.stride):
+            if ctx.c1:
+                g = _c1_dgrad(gy, w, x)
+            elif ctx.stride == 1 and _wino_ok(x):
                 return _wino_run(gy, _wino_pack_b(ctx, w, 3), Ci, 3, addend=gskip)
-            if _is_c1(w, ctx.stride):
-                g = torch.empty(x.shape, device=x.device, dtype=x.dtype)
-                _lib.call("ecm_conv3d_c1_dgrad", _p(gy), _p(w), _p(g), x.shape[0], Ci, x.shape[2], x.shape[3], x.shape[4],
-                          _stream())
             elif ctx.stride == 1:
                 g = _conv_fwd(gy, _pack_conv(w, True), Ci, 1)
             else:
@@ -827,11 +823,6 @@ class Conv3dK3(torch.autograd.Function):
             return _fork_grad(g, gskip)
         gx, gw = _launch_pair(wfn if ctx.needs_input_grad[1] else None, dfn if ctx.needs_input_grad[0] else None)
         return gx, gw, None, None, None
-
-
-def _is_c1(w, stride):
-    """The classifier's 32 -> 1 layer has its own kernels (conv3d_c1.hip)."""
-    return w.shape[0] == 1 and stride == 1 and w.shape[1] <= 32 and w.shape[1] % 8 == 0
 
 
 # Packed-weight cache.  Packing a weight is one small launch per layer and call; a training step changes every weight, so
@@ -842,8 +833,6 @@ def _is_c1(w, stride):
 # context's epoch, the tensor's version counter and its storage address, and is reused until one of them moves; leaving the
 # outermost context (or `invalidate_packed()`) drops every cached layout.  Keying a global table by data_ptr would be wrong:
 # the caching allocator hands the same address to the next tensor of that size.
-import contextlib as _contextlib
-
 _FROZEN_DEPTH = 0
 _PACK_EPOCH = 0
 
@@ -976,10 +965,9 @@ class Conv2dG(torch.autograd.Function):
 
             def direct():
                 g = _empty_like(w)
-                nb = _lib.query("ecm_conv2d_wgrad_ex_scratch_bytes", B, Ci, Co, Ho, Wo, kh, kw, stride)
-                scratch = _scratch(nb, x.device)
-                _lib.call("ecm_conv2d_wgrad_ex", _p(x), _p(gy), _p(g), _p(scratch), C.c_longlong(nb), B, Ci, Co, H, W, kh, kw,
-                          stride, dil, pad_top, pad_left, Ho, Wo, _stream())
+                _call_scratch(x.device, "ecm_conv2d_wgrad_ex_scratch_bytes", (B, Ci, Co, Ho, Wo, kh, kw, stride),
+                              "ecm_conv2d_wgrad_ex", _p(x), _p(gy), _p(g), _SCRATCH, B, Ci, Co, H, W, kh, kw, stride, dil,
+                              pad_top, pad_left, Ho, Wo, _stream())
                 return g
             return _on_side(direct, w, x, gy)
 
@@ -1130,9 +1118,8 @@ def channel_sum(x):
     B, Cc = x.shape[0], x.shape[1]
     HW = x.numel() // max(B * Cc, 1)
     out = torch.empty(Cc, device=x.device, dtype=x.dtype)
-    nb = _lib.query("ecm_channel_sum_scratch_bytes", B, Cc, C.c_longlong(HW))
-    scratch = _scratch(nb, x.device)
-    _lib.call("ecm_channel_sum", _p(x), _p(out), _p(scratch), C.c_longlong(nb), B, Cc, C.c_longlong(HW), _stream())
+    _call_scratch(x.device, "ecm_channel_sum_scratch_bytes", (B, Cc, C.c_longlong(HW)), "ecm_channel_sum",
+                  _p(x), _p(out), _SCRATCH, B, Cc, C.c_longlong(HW), _stream())
     return out
 
 
@@ -1176,10 +1163,8 @@ class Deconv2dK3S2Bias(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             # gw[ci,co,k] = sum x[ci,i] gy[co,2i+k-1]: the conv-wgrad with x := gy, gy := x, "Co" := Ci, "Ci" := Co
             gw = _empty_like(w)
-            nb = _lib.query("ecm_conv2d_wgrad_ex_scratch_bytes", B, Co, Ci, H, W, 3, 3, 2)
-            scratch = _scratch(nb, x.device)
-            _lib.call("ecm_conv2d_wgrad_ex", _p(gy), _p(x), _p(gw), _p(scratch), C.c_longlong(nb), B, Co, Ci, Ho, Wo, 3, 3, 2, 1,
-                      1, 1, H, W, _stream())
+            _call_scratch(x.device, "ecm_conv2d_wgrad_ex_scratch_bytes", (B, Co, Ci, H, W, 3, 3, 2), "ecm_conv2d_wgrad_ex",
+                          _p(gy), _p(x), _p(gw), _SCRATCH, B, Co, Ci, Ho, Wo, 3, 3, 2, 1, 1, 1, H, W, _stream())
         if ctx.needs_input_grad[2]:
             gb = channel_sum(gy)
         return gx, gw, gb
@@ -1218,10 +1203,8 @@ class Conv2dC1Relu(torch.autograd.Function):
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             gw = _empty_like(w)
             gb = torch.empty(1, device=x.device, dtype=x.dtype)
-            nb = _lib.query("ecm_conv2d_c1_wgrad_scratch_bytes", B, Ci, H, W)
-            scratch = _scratch(nb, x.device)
-            _lib.call("ecm_conv2d_c1_wgrad", _p(x), _p(gy), _p(y), _p(gw), _p(gb), _p(scratch), C.c_longlong(nb), B, Ci, H, W,
-                      _stream())
+            _call_scratch(x.device, "ecm_conv2d_c1_wgrad_scratch_bytes", (B, Ci, H, W), "ecm_conv2d_c1_wgrad",
+                          _p(x), _p(gy), _p(y), _p(gw), _p(gb), _SCRATCH, B, Ci, H, W, _stream())
         return gx, gw, gb
 
 
@@ -1265,6 +1248,39 @@ def _gn_capturing():
     return torch.cuda.is_current_stream_capturing()
 
 
+def _gn_launch(stateless, kept, x, front, back):
+    """One fp32 GroupNorm launch: outside capture the entry point `kept` on the kept exchange memory (_gn_cluster), during
+    capture the `stateless` one (_gn_capturing).  front: the pointer arguments, which the scratch pair [and the exchange
+    pair] follow;  back: the arguments after (B, C, S)."""
+    B, Cc = x.shape[:2]
+    S = x.numel() // (B * Cc)
+    name, cl = stateless, ()
+    if not _gn_capturing():
+        buf = _gn_cluster(B, x.device)
+        name, cl = kept, (_p(buf), C.c_longlong(buf.numel()))
+    _call_scratch(x.device, "ecm_gn3d_scratch_bytes", (B, Cc, C.c_longlong(S)), name, *front, _SCRATCH, *cl,
+                  B, Cc, C.c_longlong(S), *back, _stream(), call=_gn_call)
+
+
+def _gn_fwd(x, gamma, beta, skip, relu):
+    """-> (y, stats [B,32,2]) of y = relu?(GroupNorm32(x)*gamma+beta (+ skip))."""
+    stats = torch.empty(x.shape[0], GN_GROUPS, 2, device=x.device, dtype=x.dtype)
+    y = _empty_like(x)
+    _gn_launch("ecm_gn3d_fwd", "ecm_gn3d_fwd_p", x, (_p(x), _p(gamma), _p(beta), _p(skip), _p(y), _p(stats)),
+               (int(relu), C.c_float(GN_EPS)))
+    return y, stats
+
+
+def _gn_bwd(x, stats, gamma, beta, y, gy, gskip_out, relu):
+    """Backward of _gn_fwd -> (gx, ggamma, gbeta).  y: the forward's output where the ReLU mask needs it (a skip was added),
+    else None (the mask is recomputed from x);  gskip_out: the tensor that receives the masked skip gradient, or None."""
+    gx = _empty_like(x)
+    ggamma, gbeta = _empty_like(gamma), _empty_like(gamma)
+    _gn_launch("ecm_gn3d_bwd", "ecm_gn3d_bwd_p", x, (_p(x), _p(stats), _p(gamma), _p(beta), _p(y), _p(gy), _p(gx),
+                                                    _p(gskip_out), _p(ggamma), _p(gbeta)), (int(relu),))
+    return gx, ggamma, gbeta
+
+
 class GroupNormAct(torch.autograd.Function):
     """y = relu?( GroupNorm32(x)*gamma+beta (+ skip) )  (cmfsm.py:58 + ReLU/residual at 287-299, 606-613, 685-693)."""
 
@@ -1281,19 +1297,7 @@ class GroupNormAct(torch.autograd.Function):
                       f"{None if skip is None else tuple(skip.shape)}, head {head}: {GN_GROUPS} groups over C channels, skip of x's shape")
         x, gamma, beta = _c(x), _c(gamma), _c(beta)
         skip = _c(skip) if skip is not None else None
-        B, Cc = x.shape[:2]
-        S = x.numel() // (B * Cc)
-        stats = torch.empty(B, GN_GROUPS, 2, device=x.device, dtype=x.dtype)
-        nb = _lib.query("ecm_gn3d_scratch_bytes", B, Cc, C.c_longlong(S))
-        scratch = _scratch(nb, x.device)
-        y = _empty_like(x)
-        if _gn_capturing():
-            _gn_call("ecm_gn3d_fwd", _p(x), _p(gamma), _p(beta), _p(skip), _p(y), _p(stats), _p(scratch), C.c_longlong(nb),
-                     B, Cc, C.c_longlong(S), int(relu), C.c_float(GN_EPS), _stream())
-        else:
-            cl = _gn_cluster(B, x.device)
-            _gn_call("ecm_gn3d_fwd_p", _p(x), _p(gamma), _p(beta), _p(skip), _p(y), _p(stats), _p(scratch), C.c_longlong(nb),
-                     _p(cl), C.c_longlong(cl.numel()), B, Cc, C.c_longlong(S), int(relu), C.c_float(GN_EPS), _stream())
+        y, stats = _gn_fwd(x, gamma, beta, skip, relu)
         # ReLU mask in backward: recomputed from x unless a skip was added (then the output y is needed)
         ctx.save_for_backward(x, stats, gamma, beta, y if (relu and skip is not None) else None)
         ctx.relu, ctx.has_skip, ctx.head = relu, skip is not None, int(head)
@@ -1308,24 +1312,10 @@ class GroupNormAct(torch.autograd.Function):
         if gy is None:
             raise RuntimeError("GroupNormAct: the normalised output produced no gradient")     # not a configuration of these models
         gy = _c(gy)
-        B, Cc = x.shape[:2]
-        S = x.numel() // (B * Cc)
-        gx = _empty_like(x)
         gskip = None
         if ctx.has_skip:                    # no mask: the skip gradient is gy itself (the same tensor: nobody writes a gradient in place)
             gskip = _empty_like(x) if ctx.relu else gy
-        ggamma, gbeta = _empty_like(gamma), _empty_like(gamma)
-        nb = _lib.query("ecm_gn3d_scratch_bytes", B, Cc, C.c_longlong(S))
-        scratch = _scratch(nb, x.device)
-        if _gn_capturing():
-            _gn_call("ecm_gn3d_bwd", _p(x), _p(stats), _p(gamma), _p(beta), _p(y), _p(gy), _p(gx),
-                     _p(gskip if (ctx.has_skip and ctx.relu) else None), _p(ggamma), _p(gbeta), _p(scratch),
-                     C.c_longlong(nb), B, Cc, C.c_longlong(S), int(ctx.relu), _stream())
-        else:
-            cl = _gn_cluster(B, x.device)
-            _gn_call("ecm_gn3d_bwd_p", _p(x), _p(stats), _p(gamma), _p(beta), _p(y), _p(gy), _p(gx),
-                     _p(gskip if (ctx.has_skip and ctx.relu) else None), _p(ggamma), _p(gbeta), _p(scratch),
-                     C.c_longlong(nb), _p(cl), C.c_longlong(cl.numel()), B, Cc, C.c_longlong(S), int(ctx.relu), _stream())
+        gx, ggamma, gbeta = _gn_bwd(x, stats, gamma, beta, y, gy, gskip if (ctx.has_skip and ctx.relu) else None, ctx.relu)
         if g_head is not None:
             gx[:ctx.head].add_(g_head)          # gx is this node's own fresh output (see forward)
         return gx, ggamma, gbeta, gskip, None, None
@@ -1345,49 +1335,21 @@ class ClassifierTail(torch.autograd.Function):
         _need(x.dim() == 5 and x.numel() > 0 and gamma.numel() == 32 == beta.numel(),
               lambda: f"classifier_tail: x {tuple(x.shape)}, gamma {tuple(gamma.shape)}, beta {tuple(beta.shape)}")
         x, gamma, beta, w = _c(x), _c(gamma), _c(beta), _c(w)
-        B, Cc, D, H, W = x.shape
-        if Cc != 32 or tuple(w.shape) != (1, 32, 3, 3, 3):
+        if x.shape[1] != 32 or tuple(w.shape) != (1, 32, 3, 3, 3):
             raise RuntimeError(f"classifier_tail: x {tuple(x.shape)}, w {tuple(w.shape)}: the fused tail exists for 32 -> 1 only")
         stats = _gn_stats(x)
-        y = torch.empty(B, 1, D, H, W, device=x.device, dtype=x.dtype)
-        _lib.call("ecm_conv3d_c1_gn_fwd", _p(x), _p(stats), _p(gamma), _p(beta), _p(w), _p(y), B, Cc, D, H, W, _stream())
+        y = _c1_fwd(x, w, (stats, gamma, beta))
         ctx.save_for_backward(x, stats, gamma, beta, w)
-        ctx.side_ok = True
         return y
 
     @staticmethod
     def backward(ctx, gy):
         x, stats, gamma, beta, w = ctx.saved_tensors
         gy = _c(gy)
-        B, Cc, D, H, W = x.shape
-        S = D * H * W
-
-        def wfn():
-            def now():
-                g = _empty_like(w)
-                nbw = _lib.query("ecm_conv3d_c1_wgrad_scratch_bytes", B, Cc, D, H, W)
-                sc = _scratch(nbw, x.device)
-                _lib.call("ecm_conv3d_c1_gn_wgrad", _p(x), _p(stats), _p(gamma), _p(beta), _p(gy), _p(g), _p(sc), C.c_longlong(nbw),
-                          B, Cc, D, H, W, _stream())
-                return g
-            return _on_side(now, w, x, gy, stats, gamma, beta)
-
-        def dfn():
-            gh = torch.empty(x.shape, device=x.device, dtype=x.dtype)
-            _lib.call("ecm_conv3d_c1_dgrad", _p(gy), _p(w), _p(gh), B, Cc, D, H, W, _stream())
-            return gh
-        gh, gw = _launch_pair(wfn if ctx.needs_input_grad[3] else None, dfn)
-        gx = _empty_like(x)
-        ggamma, gbeta = _empty_like(gamma), _empty_like(gamma)
-        nb = _lib.query("ecm_gn3d_scratch_bytes", B, Cc, C.c_longlong(S))
-        scratch = _scratch(nb, x.device)
-        if _gn_capturing():
-            _gn_call("ecm_gn3d_bwd", _p(x), _p(stats), _p(gamma), _p(beta), _p(None), _p(gh), _p(gx), _p(None), _p(ggamma),
-                     _p(gbeta), _p(scratch), C.c_longlong(nb), B, Cc, C.c_longlong(S), 1, _stream())
-        else:
-            cl = _gn_cluster(B, x.device)
-            _gn_call("ecm_gn3d_bwd_p", _p(x), _p(stats), _p(gamma), _p(beta), _p(None), _p(gh), _p(gx), _p(None), _p(ggamma),
-                     _p(gbeta), _p(scratch), C.c_longlong(nb), _p(cl), C.c_longlong(cl.numel()), B, Cc, C.c_longlong(S), 1, _stream())
+        gn = (stats, gamma, beta)
+        gh, gw = _launch_pair((lambda: _on_side(lambda: _c1_wgrad(x, gy, w, gn), w, x, gy, *gn)) if ctx.needs_input_grad[3] else None,
+                              lambda: _c1_dgrad(gy, w, x))
+        gx, ggamma, gbeta = _gn_bwd(x, stats, gamma, beta, None, gh, None, True)
         return gx, ggamma, gbeta, gw
 
 
@@ -1471,10 +1433,8 @@ def eval_epe(pred, gt, crop_h=540, crop_w=960, maxdisp=192):
         raise RuntimeError(f"prediction / ground-truth batch sizes differ: {B} vs {Bg}")
     out = torch.empty(6, device=pred.device, dtype=torch.float32)
     n = B * int(crop_h) * int(crop_w)
-    nb = _lib.query("ecm_eval_epe_scratch_bytes", C.c_longlong(n))
-    scratch = _scratch(nb, pred.device)
-    _lib.call("ecm_eval_epe", _p(pred), _p(gt), _p(out), _p(scratch), C.c_longlong(nb), B, Hp, Wp, Hg, Wg, int(crop_h),
-              int(crop_w), C.c_float(maxdisp), _stream())
+    _call_scratch(pred.device, "ecm_eval_epe_scratch_bytes", (C.c_longlong(n),), "ecm_eval_epe", _p(pred), _p(gt), _p(out),
+                  _SCRATCH, B, Hp, Wp, Hg, Wg, int(crop_h), int(crop_w), C.c_float(maxdisp), _stream())
     return out
 
 
@@ -1509,10 +1469,9 @@ class StereoLoss3(torch.autograd.Function):
         p1, p2, p3, gt = _c(p1), _c(p2), _c(p3), _c(gt)
         n = gt.numel()
         out = torch.empty(8, device=gt.device, dtype=gt.dtype)
-        nb = _lib.query("ecm_stereo_loss_scratch_bytes", C.c_longlong(n))
-        scratch = _scratch(nb, gt.device)
-        _lib.call("ecm_stereo_loss_fwd", _p(p1), _p(p2), _p(p3), _p(gt), _p(out), _p(scratch), C.c_longlong(nb),
-                  C.c_longlong(n), C.c_float(maxdisp), C.c_float(w1), C.c_float(w2), C.c_float(w3), _stream())
+        _call_scratch(gt.device, "ecm_stereo_loss_scratch_bytes", (C.c_longlong(n),), "ecm_stereo_loss_fwd",
+                      _p(p1), _p(p2), _p(p3), _p(gt), _p(out), _SCRATCH, C.c_longlong(n), C.c_float(maxdisp), C.c_float(w1),
+                      C.c_float(w2), C.c_float(w3), _stream())
         ctx.save_for_backward(p1, p2, p3, gt, out)
         ctx.cfg = (float(maxdisp), float(w1), float(w2), float(w3))
         ctx.mark_non_differentiable(out)
@@ -1675,10 +1634,9 @@ def _gn_stats(x):
     B, Cc = x.shape[:2]
     S = x.numel() // (B * Cc)
     stats = torch.empty(B, GN_GROUPS, 2, device=x.device, dtype=torch.float32)
-    nb = _lib.query("ecm_gn3d_scratch_bytes", B, Cc, C.c_longlong(S))
-    scratch = _scratch(nb, x.device)
     name = "ecm_gn3d_stats_bf16" if x.dtype == torch.bfloat16 else "ecm_gn3d_stats"
-    _gn_call(name, _p(x), _p(stats), _p(scratch), C.c_longlong(nb), B, Cc, C.c_longlong(S), C.c_float(GN_EPS), _stream())
+    _call_scratch(x.device, "ecm_gn3d_scratch_bytes", (B, Cc, C.c_longlong(S)), name, _p(x), _p(stats), _SCRATCH,
+                  B, Cc, C.c_longlong(S), C.c_float(GN_EPS), _stream(), call=_gn_call)
     return stats
 
 

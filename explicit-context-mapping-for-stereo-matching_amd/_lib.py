@@ -110,6 +110,10 @@ PROTOTYPES = {
     "ecm_conv2d_bf16_pack_weight": (_I, [_P, _P, _I, _I, _I, _P]),
     "ecm_conv2d_bf16_fwd": (_I, [_P, _P, _P] + [_I] * 9 + [_P]),
     "ecm_gn3d_apply_bf16_f32": (_I, [_P] * 7 + [_I, _I, _LL, _I, _P]),
+    "ecm_deconv2d_bf16_packed_elems": (_LL, [_I, _I]),                       # cmf.py:236-239
+    "ecm_deconv2d_bf16_pack_weight": (_I, [_P, _P, _I, _I, _P]),             # cmf.py:236-239
+    "ecm_deconv2d_k3s2_bias_bf16_fwd": (_I, [_P, _P, _P, _P] + [_I] * 5 + [_P]),   # cmf.py:236-239
+    "ecm_conv2d_c1_bf16_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),    # cmf.py:259-264
 }
 
 _lib = None

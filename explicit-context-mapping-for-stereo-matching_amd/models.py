@@ -752,6 +752,12 @@ class HipConvTranspose2d(nn.ConvTranspose2d):
                 and self.padding_mode == "zeros" and self.out_channels <= 64 and self.in_channels % 4 == 0)
 
     def forward(self, x, output_size=None):
+        if x.dtype == torch.bfloat16:                      # the bf16 decoder (ops.decoder_dtype)
+            if not (self._native() and output_size is None and ops.deconv2d_bf16_supported(self.in_channels, self.out_channels)):
+                raise RuntimeError(f"HipConvTranspose2d({self.in_channels}->{self.out_channels}, k={self.kernel_size}, "
+                                   f"s={self.stride}) is outside the bf16 decoder kernel (ops.deconv2d_bf16_supported); leave the "
+                                   "decoder_dtype(torch.bfloat16) block")
+            return ops.deconv2d_k3s2_bias_bf16(x, self.weight, self.bias)
         if self._native() and output_size is None:
             return ops.deconv2d_k3s2_bias(x, self.weight, self.bias)
         if not ALLOW_FALLBACK:
@@ -771,6 +777,11 @@ class HipConv2dC1(nn.Conv2d):
                 and self.dilation == (1, 1) and self.groups == 1 and self.bias is not None and self.padding_mode == "zeros")
 
     def forward(self, x):
+        if x.dtype == torch.bfloat16:                      # the bf16 decoder (ops.decoder_dtype): fp32 result
+            if not (self._native() and self.in_channels % 16 == 0):
+                raise RuntimeError(f"HipConv2dC1({self.in_channels}->{self.out_channels}, k={self.kernel_size}) is outside the "
+                                   "bf16 decoder kernel; leave the decoder_dtype(torch.bfloat16) block")
+            return ops.conv2d_c1_relu_bf16(x, self.weight, self.bias)
         if self._native():
             return ops.conv2d_c1_relu(x, self.weight, self.bias)
         if not ALLOW_FALLBACK:
@@ -810,6 +821,10 @@ class super_resolution_refinement(nn.Module):
         self.crap = HipReLU(inplace=True)                  # fused into conv_out
 
     def forward(self, preds, rgb, *rgb_zoom_feature):
+        """Inside ops.decoder_dtype(torch.bfloat16): _forward_bf16."""
+        bf16 = ops.decoder_bf16()
+        if bf16:
+            ops._DEC.no_grad("super_resolution_refinement")         # before the first launch
         if len(rgb_zoom_feature) != self.twice_times:
             raise ValueError(f"super_resolution_refinement: {self.twice_times} zoom features expected, got {len(rgb_zoom_feature)}")
         NH, B, h, w = preds.shape
@@ -819,11 +834,32 @@ class super_resolution_refinement(nn.Module):
         if got != want or rgb.shape[0] != B or tuple(rgb.shape[-2:]) != (h * f, w * f):
             raise ValueError(f"super_resolution_refinement: preds {tuple(preds.shape)}, rgb {tuple(rgb.shape)}, zoom features "
                              f"{[tuple(t.shape) for t in rgb_zoom_feature]}: each map must be twice the size of the previous one")
+        if bf16:
+            return self._forward_bf16(preds, rgb, rgb_zoom_feature)
         x = _seq_fused(self.conv1, preds.reshape(NH * B, 1, h, w))                 # cmf.py:258
         for dec, skip in zip(self.deconv_module_list, rgb_zoom_feature):            # cmf.py:259-260
             x = dec[1].fused(dec[0](_cat_shared(x, skip, NH)), None, True)
         x = _cat_shared(x, _seq_fused(self.rgb_fea, rgb), NH)                      # cmf.py:262
         x = self.conv_out(_seq_fused(self.conv2, x))                               # cmf.py:263-264 (+ crap)
+        return x.view(NH, B, 1, h * f, w * f)
+
+    def _forward_bf16(self, preds, rgb, rgb_zoom_feature):
+        """The decoder on bf16 maps (ops.decoder_dtype).  fp32 enters where rounding would hurt: conv1 reads the fp32
+        disparities (values up to maxdisp/4: 8 bits would not hold them) and rgb_fea's stem the fp32 image, both on the fp32
+        kernels, and their GroupNorm + ReLU writes bf16.  The encoder maps that join the concatenations are rounded once.
+        Every later layer runs on the bf16 kernels (a layer outside them raises): the transposed convolutions and conv_out on
+        bf16_decoder.hip, rgb_fea's 32 -> 32 layers and conv2 on the encoder's convolution kernel, the GroupNorms on the
+        two-stage kernels.  The result is fp32, written by conv_out's kernel."""
+        bf = torch.bfloat16
+        NH, B, h, w = preds.shape
+        f = 2 ** self.twice_times
+        conv, gn = self.conv1[0][0], self.conv1[0][1]
+        x = gn.fused(conv(preds.reshape(NH * B, 1, h, w)), None, True, out_dtype=bf)
+        for dec, skip in zip(self.deconv_module_list, rgb_zoom_feature):
+            x = dec[1].fused(dec[0](_cat_shared(x, skip.to(bf), NH)), None, True)
+        conv, gn = self.rgb_fea[0][0], self.rgb_fea[0][1]
+        r = _seq_fused(self.rgb_fea, gn.fused(conv(rgb), None, True, out_dtype=bf), start=2)
+        x = self.conv_out(_seq_fused(self.conv2, _cat_shared(x, r, NH)))
         return x.view(NH, B, 1, h * f, w * f)
 
 
@@ -853,6 +889,7 @@ class cmf(_ECMNet):
             raise ValueError(f"cmf: left {tuple(left.shape)}, right {tuple(right.shape)}: H and W must be multiples of 4 (the "
                              "decoder doubles 1/4 -> 1/2 -> 1) and both images the same size")
         B = left.shape[0]
+        ops._DEC.guard("cmf")                                          # the bf16 decoder has no backward: raise before any launch
         if torch.is_grad_enabled():
             ops.pace_side_streams()
         lr, _, half = self.feature_extraction(torch.cat([left, right], 0), head=B)   # one encoder pass for both images

@@ -1499,7 +1499,7 @@ def group_norm_act(x, gamma, beta, skip=None, relu=False, head=0, out_dtype=None
     the bf16 region: fp32 x), runs the bf16 inference kernels and returns a bf16 y (see aggregation_dtype)."""
     if x.dtype == torch.bfloat16 or out_dtype == torch.bfloat16:
         _need(not head, "group_norm_act: the bf16 form takes no head fork")
-        _AGG.no_grad("group_norm_act")
+        _bf16_region(_AGG, _ENC, _DEC).no_grad("group_norm_act")
         return _gn_apply_two_stage(x, gamma, beta, skip, bool(relu), torch.bfloat16)
     _need(out_dtype in (None, torch.float32), lambda: f"group_norm_act: out_dtype {out_dtype}: float32 or bfloat16")
     _need(0 <= int(head) <= x.shape[0], lambda: f"group_norm_act: head {head} of a batch of {x.shape[0]}")
@@ -1533,7 +1533,7 @@ def check_async_errors(clear=True):
 # dispatch on the dtype of the volume; weights stay fp32 parameters, packed to bf16 images per call (cached under
 # frozen_weights() beside the fp32 layouts, under their own keys).
 class _Bf16Switch:
-    """A process-wide opt-in bf16 inference switch (aggregation_dtype, encoder_dtype): nests, restores the previous setting
+    """A process-wide opt-in bf16 inference switch (aggregation_dtype, encoder_dtype, decoder_dtype): nests, restores the previous setting
     on exit, and is inference only."""
 
     def __init__(self, name, what):
@@ -1565,6 +1565,12 @@ class _Bf16Switch:
 
 
 _AGG = _Bf16Switch("aggregation_dtype", "bf16 aggregation")
+
+
+def _bf16_region(*switches):
+    """The switch whose block an op shared by several bf16 regions was reached in (for its error text): the first one that is
+    on, else the first."""
+    return next((s for s in switches if s.on()), switches[0])
 
 
 def aggregation_dtype(dtype):
@@ -1731,7 +1737,7 @@ def conv2d_bf16(x, w, stride=1, dil=1, fork=False, out_dtype=torch.bfloat16):
     """Conv2d(bias=False) of the bf16 encoder on a bf16 x [B,Ci,H,W]: 3x3 (padding = dil; stride 1 with dilation 1|2|4, or
     stride 2) or 1x1 (stride 1|2).  out_dtype torch.float32: the result leaves the encoder in fp32 (rounded nowhere).
     fork=True: returns (y, x) -- x for the skip connection (no backward here)."""
-    _ENC.no_grad("conv2d_bf16")
+    _bf16_region(_ENC, _DEC).no_grad("conv2d_bf16")
     _chk_bf16(x)
     _chk(w)
     _need(x.dim() == 4 and w.dim() == 4 and w.shape[1] == x.shape[1] and w.shape[2] == w.shape[3] and x.numel() > 0
@@ -1753,3 +1759,85 @@ def group_norm_act_bf16_f32(x, gamma, beta, skip=None, relu=False, dual=False):
     (y32, y16), the same values also rounded to bf16 in the same pass for the next bf16 layer."""
     _ENC.no_grad("group_norm_act_bf16_f32")
     return _gn_apply_two_stage(x, gamma, beta, skip, relu, "dual" if dual else torch.float32)
+
+
+# ---- opt-in bf16 inference of the cmf refinement decoder ---------------------------------------------------------------------
+# Inside `with decoder_dtype(torch.bfloat16):` models.super_resolution_refinement runs on bf16 maps from conv1's GroupNorm to
+# conv_out's input: its 3x3 convolutions on conv2d_bf16, its GroupNorms on the two-stage bf16 kernels, the two transposed
+# convolutions and conv_out on csrc/bf16_decoder.hip; the disparities it returns are fp32, written by conv_out's kernel.
+# Independent of aggregation_dtype and encoder_dtype and combinable with both (inference_dtype enters all three); a no-op for
+# the architectures without a decoder.  Process-wide, inference only, and the fp32 path outside the block is untouched.
+# Weights stay fp32 parameters: the transposed convolutions' bf16 images are packed per call (cached under frozen_weights(),
+# key "bf16_deconv2d"), conv_out's 9*Ci weights are rounded by its kernel.
+_DEC = _Bf16Switch("decoder_dtype", "the bf16 decoder")
+
+
+def decoder_dtype(dtype):
+    """torch.float32 (the default; a no-op) or torch.bfloat16 for cmf's refinement decoder inside the block; nests and
+    restores the previous setting on exit.  bf16 is inference only: run the model under torch.no_grad()."""
+    return _DEC.scope(dtype)
+
+
+def decoder_bf16():
+    """True inside a decoder_dtype(torch.bfloat16) block."""
+    return _DEC.on()
+
+
+@_contextlib.contextmanager
+def inference_dtype(dtype):
+    """All three bf16 inference regions at once: encoder_dtype, aggregation_dtype and decoder_dtype entered (and restored)
+    together.  torch.float32 sets all three to the default."""
+    with encoder_dtype(dtype), aggregation_dtype(dtype), decoder_dtype(dtype):
+        yield
+
+
+def deconv2d_bf16_supported(Ci, Co):
+    """Is this ConvTranspose2d(Ci, Co, 3, stride 2, padding 1, output_padding 1, bias=True) inside the bf16 decoder kernel?"""
+    return Ci > 0 and Ci % 16 == 0 and Co in (32, 64)
+
+
+def _pack_bf16_deconv2d(w):
+    """bf16 weight image [Ci/16][9][Co][16] of a ConvTranspose2d weight [Ci,Co,3,3]."""
+    Ci, Co = w.shape[0], w.shape[1]
+
+    def build():
+        wc = _c(w.detach())
+        packed = torch.empty(_lib.query("ecm_deconv2d_bf16_packed_elems", Ci, Co), device=w.device, dtype=torch.bfloat16)
+        _lib.call("ecm_deconv2d_bf16_pack_weight", _p(wc), _p(packed), Ci, Co, _stream())
+        return packed
+    return _cached_pack(w, "bf16_deconv2d", build)
+
+
+def deconv2d_k3s2_bias_bf16(x, w, b):
+    """ConvTranspose2d(Ci, Co, 3, stride 2, padding 1, output_padding 1, bias=True) (cmf.py:236-239) of the bf16 decoder on a
+    bf16 x [B,Ci,H,W] -> bf16 [B,Co,2H,2W]; w [Ci,Co,3,3] and b [Co] are the fp32 parameters (no backward here)."""
+    _DEC.no_grad("deconv2d_k3s2_bias_bf16")
+    _chk_bf16(x)
+    _chk(w, b)
+    _need(x.dim() == 4 and w.dim() == 4 and tuple(w.shape[2:]) == (3, 3) and w.shape[0] == x.shape[1] and x.numel() > 0
+          and b.dim() == 1 and b.shape[0] == w.shape[1] and deconv2d_bf16_supported(x.shape[1], w.shape[1]),
+          lambda: f"deconv2d_k3s2_bias_bf16: x {tuple(x.shape)}, w {tuple(w.shape)}, b {tuple(b.shape)}: want [B,Ci,H,W], "
+                  "ConvTranspose2d's [Ci,Co,3,3] with Ci % 16 == 0, Co in {32, 64} and [Co]")
+    x, b = _c(x), _c(b.detach())
+    B, Ci, H, W = x.shape
+    Co = w.shape[1]
+    y = torch.empty(B, Co, 2 * H, 2 * W, device=x.device, dtype=torch.bfloat16)
+    _lib.call("ecm_deconv2d_k3s2_bias_bf16_fwd", _p(x), _p(_pack_bf16_deconv2d(w)), _p(b), _p(y), B, Ci, Co, H, W, _stream())
+    return y
+
+
+def conv2d_c1_relu_bf16(x, w, b):
+    """relu(Conv2d(Ci, 1, 3, 1, 1, bias=True)(x)) (cmf.py:259-264, conv_out + crap) of the bf16 decoder on a bf16 x [B,Ci,H,W]
+    -> fp32 [B,1,H,W], rounded nowhere; w [1,Ci,3,3] (rounded to bf16 by the kernel) and b [1] are the fp32 parameters."""
+    _DEC.no_grad("conv2d_c1_relu_bf16")
+    _chk_bf16(x)
+    _chk(w, b)
+    _need(x.dim() == 4 and tuple(w.shape) == (1, x.shape[1], 3, 3) and b.numel() == 1 and x.numel() > 0
+          and x.shape[1] % 16 == 0 and x.shape[1] <= 1024,
+          lambda: f"conv2d_c1_relu_bf16: x {tuple(x.shape)}, w {tuple(w.shape)}, b {tuple(b.shape)}: want [B,Ci,H,W], "
+                  "[1,Ci,3,3] and [1] with Ci % 16 == 0, Ci <= 1024")
+    x, w, b = _c(x), _c(w.detach()), _c(b.detach())
+    B, Ci, H, W = x.shape
+    y = torch.empty(B, 1, H, W, device=x.device, dtype=torch.float32)
+    _lib.call("ecm_conv2d_c1_bf16_fwd", _p(x), _p(w), _p(b), _p(y), B, Ci, H, W, _stream())
+    return y

@@ -420,6 +420,24 @@ int ecm_conv2d_bf16_pack_weight(const float* w, unsigned short* packed, int Ci, 
 int ecm_conv2d_bf16_fwd(const unsigned short* x, const unsigned short* wpacked, void* y, int B, int Ci, int Co, int H, int W,
                         int k, int stride, int dil, int out_f32, void* stream);
 
+/* ---- opt-in bf16 inference of the cmf refinement decoder (ops.decoder_dtype; bf16_decoder.hip) --------------------------
+ * Forward only.  The decoder's 3x3 convolutions run on ecm_conv2d_bf16_fwd and its GroupNorms on the two-stage kernels
+ * above; these are the two layers they do not cover.  Maps are contiguous NCHW, bf16 as its bit pattern; products accumulate
+ * in fp32; no atomics: bit-reproducible.
+ * ConvTranspose2d(Ci, Co, 3, stride 2, padding 1, output_padding 1, bias=True) of deconv_module_list (cmf.py:236-239):
+ * weight image [Ci/16][9 taps][Co][16] bf16 of w [Ci,Co,3,3]; Ci % 16 == 0 and Co in {32, 64} (0 elements otherwise). */
+long long ecm_deconv2d_bf16_packed_elems(int Ci, int Co);
+int ecm_deconv2d_bf16_pack_weight(const float* w, unsigned short* packed, int Ci, int Co, void* stream);
+/* cmf.py:236-239: bf16 x [B,Ci,H,W] -> bf16 y [B,Co,2H,2W]; the fp32 bias is added to the fp32 accumulators and every output
+ * is rounded once (round to nearest even, NaN stays NaN).  Ci % 16 == 0, Co in {32, 64}; any H, W >= 1. */
+int ecm_deconv2d_k3s2_bias_bf16_fwd(const unsigned short* x, const unsigned short* wpacked, const float* bias, unsigned short* y,
+                                    int B, int Ci, int Co, int H, int W, void* stream);
+/* conv_out + crap (cmf.py:259-264): relu(Conv2d(Ci, 1, 3, 1, 1, bias=True)(x)) of a bf16 x
+ * [B,Ci,H,W] written as fp32 y [B,1,H,W], rounded nowhere.  w is the fp32 parameter [1,Ci,3,3], rounded to bf16 as the
+ * kernel stages it; bias fp32 [1].  Ci % 16 == 0, Ci <= 1024; any H, W >= 1. */
+int ecm_conv2d_c1_bf16_fwd(const unsigned short* x, const float* w, const float* bias, float* y, int B, int Ci, int H, int W,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

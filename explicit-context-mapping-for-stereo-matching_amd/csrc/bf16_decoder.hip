@@ -5,54 +5,37 @@
 //    Output (2i+py, 2j+px) reads the inputs (i+dy, j+dx), dy, dx in {0, 1}: tap k along an axis has phase p = (k != 1) and
 //    offset d = (k == 0), so the four phases are stride-1 convolutions over the input grid with 1, 2, 2 and 4 of the nine
 //    taps.  A workgroup stages ONE halo tile of (4+1) x (32+1) input positions per 16-channel chunk -- [position][16 channels]
-//    in LDS, written with the transposing channel-pair write of bf16_encoder.hip -- and computes all four phases from it on
+//    in LDS next to the chunk's [tap][Co][16] weight slice, through the staging pipeline of bf16_conv2d.h that conv2d_bf16
+//    (bf16_encoder.hip) runs on as well -- and computes all four phases from it on
 //    v_mfma_f32_32x32x16_bf16:  D[co][input column] += A[co][16 channels of one tap] * B[16 channels][input column + dx].
-//    Each of the four waves owns one input row: 4 phases x Co/32 accumulator tiles, preset with the fp32 bias.  The LDS
-//    tile (halo + the chunk's [tap][Co][16] weight slice) is double-buffered across chunks with one barrier per chunk.
+//    Each of the four waves owns one input row: 4 phases x Co/32 accumulator tiles, preset with the fp32 bias.
 //    A lane owns input column j, hence the px = 0 and px = 1 outputs 2j and 2j+1 of a row: they are rounded once and stored
 //    as one 4-byte pair, so a wave writes 128 contiguous bytes per (channel, output row).
 // B. conv_out: relu(Conv2d(Ci, 1, 3, 1, 1, bias)(x)) (cmf.py:259-264) on a bf16 x, fp32 y.  HBM-bound (Ci bf16 planes in, one
 //    fp32 plane out), on the vector ALU with no LDS staging of x and no barrier in the channel loop: a lane owns 8 adjacent
 //    columns of 4 output rows, reads the 6 input rows of a channel as 16-byte loads (a wave reads 1 KB of a row at once),
 //    takes the two columns beside its segment from its neighbour lanes, widens bf16 -> fp32 in registers and accumulates in
-//    fp32.  Every load is branch-free (an outside column loads a valid address and is zeroed by a select), so a channel's
-//    6 + 6 loads are issued back to back and waited for once; the latency is covered by the other waves of the SIMD (167
-//    VGPRs: 3 waves), not by a register pipeline -- two channels in flight per wave took 218-256 VGPRs.  The 9*Ci weights are rounded to
-//    bf16 once into LDS and read from there at a wave-uniform address.
+//    fp32.  Every load is branch-free (load8 of bf16_conv2d.h: an outside column loads a valid address and is zeroed by a
+//    select), so a channel's 6 + 6 loads are issued back to back and waited for once; the latency is covered by the other
+//    waves of the SIMD (167 VGPRs: 3 waves), not by a register pipeline -- two channels in flight per wave took 218-256
+//    VGPRs.  The 9*Ci weights are rounded to bf16 once into LDS and read from there at a wave-uniform address.
 // No atomics: each output is one thread's fixed-order sum, so results are bit-reproducible.
 #include "common.h"
-#include "bf16.h"
+#include "bf16_conv2d.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int KC = 16;          // input channels per k-step
-
 // ---- A: transposed convolution ------------------------------------------------------------------------------------------------
 constexpr int DTW = 32, DTH = 4;                       // input columns / rows per workgroup (one row per wave)
-constexpr int DIWP = 40, DNSEG = DIWP / 8;             // window columns: 33 needed, widened to whole 8-column segments
-constexpr int DHR = DTH + 1;                           // halo rows
-constexpr int DNU = (KC / 2) * DHR * DNSEG;            // staging units (channel pair x row x segment): 200 <= 256 threads
-constexpr int DHRA = (256 + 8 * DNSEG - 1) / (8 * DNSEG);   // rows allocated: every thread's unit lands in LDS, no branch
-constexpr int DXBYTES = DHRA * DIWP * KC * 2;
-static_assert(DNU <= 256, "one staging unit per thread");
-
+constexpr int DIWP = 40, DHR = DTH + 1;                // window columns (33 needed, widened to whole 8-column segments), halo rows
 template <int COT>
-constexpr int dec_lds_bytes() {
-    return 2 * (DXBYTES + (9 * COT * 64 + 255) / 256 * 256 * 16);
-}
+using DecStage = Stage2d<DHR, DIWP, 9, COT>;           // 200 staging units: one per thread
 
 template <int COT, bool VEC>
 __global__ __launch_bounds__(256, 2) void deconv2d_bf16(const u16* __restrict__ x, const u16* __restrict__ wp,
                                                         const float* __restrict__ bias, u16* __restrict__ y, int Ci, int H,
                                                         int W, int tiles_h, int tiles_w) {
     constexpr int COP = COT * 32;
-    constexpr int WQ = 9 * COP * 2;                                                // weight uint4s per chunk
-    constexpr int WPT = (WQ + 255) / 256;
-    constexpr int BUF = DXBYTES + WPT * 256 * 16;
-    static_assert(BUF * 2 == dec_lds_bytes<COT>(), "LDS size");
     extern __shared__ __attribute__((aligned(16))) char smem_d[];
 
     int bid = ecm_xcd_tile(blockIdx.x, gridDim.x);
@@ -64,80 +47,20 @@ __global__ __launch_bounds__(256, 2) void deconv2d_bf16(const u16* __restrict__ 
     const size_t HW = (size_t)H * W;
     const u16* xb = x + (size_t)b * Ci * HW;
 
-    // staging unit: channel pair cp (fastest), segment j, row r
-    const int cp = tid & 7, sj = (tid >> 3) % DNSEG, sr = (tid >> 3) / DNSEG;
-    const int gy = i0 + sr, gx = j0 + 8 * sj;
-    unsigned uok = 0;
-    if (tid < DNU && gy < H) {
-        if (VEC) uok = gx < W ? 0xffu : 0u;                                        // W % 8 == 0: a segment is all in or all out
-        else
-            for (int e = 0; e < 8; ++e) uok |= (gx + e < W ? 1u : 0u) << e;
-    }
-    const int uoff = gy * W + gx;
-    const int ulds = ((sr * DIWP + 8 * sj) * KC + 2 * cp) * 2;
-    uint4 xr[2];
-    u32x4 wr[WPT];
-    const int nchunks = Ci / KC;
-
-    auto fetch = [&](int chunk) __attribute__((always_inline)) {
-        const int c0 = chunk * KC;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const u16* src = xb + (size_t)(c0 + 2 * cp + q) * HW;
-            // branch-free: an outside position loads the plane's first element and is zeroed by a select
-            if (VEC) {
-                const uint4 v = *reinterpret_cast<const uint4*>(src + (uok ? uoff : 0));
-                xr[q] = uok ? v : make_uint4(0, 0, 0, 0);
-            } else {
-                unsigned v[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const bool ok = (uok >> e) & 1u;
-                    const unsigned t = src[ok ? uoff + e : 0];
-                    v[e] = ok ? t : 0u;
-                }
-                xr[q] = make_uint4(v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16));
-            }
-        }
-        // the chunk's weight slice [tap][COP][16]: contiguous in the image (Co == COP), L2-resident
-        const u32x4* wsrc = reinterpret_cast<const u32x4*>(wp) + (size_t)chunk * WQ;
-#pragma unroll
-        for (int i = 0; i < WPT; ++i) wr[i] = wsrc[min(tid + i * 256, WQ - 1)];    // the tail re-reads the last vector
-    };
-    auto store = [&](int buf) __attribute__((always_inline)) {
-        char* base = smem_d + buf * BUF;
-        const unsigned a[4] = {xr[0].x, xr[0].y, xr[0].z, xr[0].w};
-        const unsigned c[4] = {xr[1].x, xr[1].y, xr[1].z, xr[1].w};
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const unsigned lo = (a[e >> 1] >> (16 * (e & 1))) & 0xffffu, hi = (c[e >> 1] >> (16 * (e & 1))) & 0xffffu;
-            *reinterpret_cast<unsigned*>(base + ulds + e * KC * 2) = lo | (hi << 16);
-        }
-        u32x4* Ws = reinterpret_cast<u32x4*>(base + DXBYTES);
-#pragma unroll
-        for (int i = 0; i < WPT; ++i) Ws[tid + i * 256] = wr[i];                   // past WQ: padding nobody reads
-    };
-
     // accumulators [phase py*2+px][channel tile], preset with the bias of the register's channel
     f32x16 acc[4][COT];
 #pragma unroll
     for (int ct = 0; ct < COT; ++ct)
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const float bv = bias[ct * 32 + (i & 3) + 8 * (i >> 2) + 4 * half];
+            const float bv = bias[ct * 32 + mfma32_row(i, half)];
 #pragma unroll
             for (int p = 0; p < 4; ++p) acc[p][ct][i] = bv;
         }
     const int rbase = (wave * DIWP + l31) * 2 + half;                              // B fragment of offset (0, 0)
 
-    fetch(0);
-    store(0);
-    if (nchunks > 1) fetch(1);
-    __syncthreads();
-    for (int ch = 0; ch < nchunks; ++ch) {
-        const int buf = ch & 1;
-        const uint4* Xs = reinterpret_cast<const uint4*>(smem_d + buf * BUF);
-        const uint4* Ws = reinterpret_cast<const uint4*>(smem_d + buf * BUF + DXBYTES);
+    // the weight image has Co == COP, so the workgroup's slice is the whole (contiguous) chunk
+    stage2d_run<DecStage<COT>, VEC>(smem_d, xb, Ci, H, W, i0, j0, wp, COP, 0, [&](const uint4* Xs, const uint4* Ws) __attribute__((always_inline)) {
         bf16x8 bv[2][2];
 #pragma unroll
         for (int dy = 0; dy < 2; ++dy)
@@ -153,14 +76,9 @@ __global__ __launch_bounds__(256, 2) void deconv2d_bf16(const u16* __restrict__ 
                 acc[p][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bv[ky == 0][kx == 0], acc[p][ct], 0, 0, 0);
             }
         }
-        if (ch + 1 < nchunks) {
-            store(buf ^ 1);                                                        // the buffer chunk ch-1 used: free since the last barrier
-            if (ch + 2 < nchunks) fetch(ch + 2);                                   // in flight under chunk ch+1's MFMAs
-        }
-        __syncthreads();
-    }
+    });
 
-    // epilogue: lane = input column, register i = output channel (i&3) + 8*(i>>2) + 4*half of the tile
+    // epilogue: lane = input column, register i = output channel mfma32_row(i, half) of the tile
     const int i = i0 + wave, j = j0 + l31;
     if (i >= H || j >= W) return;
     const int Wo = 2 * W;
@@ -170,7 +88,7 @@ __global__ __launch_bounds__(256, 2) void deconv2d_bf16(const u16* __restrict__ 
     for (int ct = 0; ct < COT; ++ct)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            u16* dst = yb + (size_t)(ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * HWo;
+            u16* dst = yb + (size_t)(ct * 32 + mfma32_row(r, half)) * HWo;
 #pragma unroll
             for (int py = 0; py < 2; ++py)
                 *reinterpret_cast<unsigned*>(dst + py * Wo) = (unsigned)f2bf(acc[py * 2][ct][r]) | ((unsigned)f2bf(acc[py * 2 + 1][ct][r]) << 16);
@@ -182,54 +100,14 @@ int launch_dec(const u16* x, const u16* wp, const float* bias, u16* y, int B, in
     const int th = (H + DTH - 1) / DTH, tw = (W + DTW - 1) / DTW;
     const long long nb = (long long)B * th * tw;
     if (nb > 0x7fffffffLL) return ECM_EUNSUP;
-    constexpr int lds = dec_lds_bytes<COT>();
-    const bool vec = W % 8 == 0;
-    const void* kern = vec ? reinterpret_cast<const void*>(deconv2d_bf16<COT, true>) : reinterpret_cast<const void*>(deconv2d_bf16<COT, false>);
-    const hipError_t e = ecm_allow_lds(kern, lds);
-    if (e != hipSuccess) return (int)e;
-    if (vec)
-        hipLaunchKernelGGL((deconv2d_bf16<COT, true>), dim3((unsigned)nb), dim3(256), lds, ecm_stream(stream), x, wp, bias, y, Ci, H, W, th, tw);
-    else
-        hipLaunchKernelGGL((deconv2d_bf16<COT, false>), dim3((unsigned)nb), dim3(256), lds, ecm_stream(stream), x, wp, bias, y, Ci, H, W, th, tw);
-    return ECM_LAUNCH_RESULT();
-}
-
-// weight image [Ci/16][9 taps][Co][16 channels] bf16 from ConvTranspose2d's w [Ci,Co,3,3]
-__global__ void pack_bf16_deconv2d(const float* __restrict__ w, u16* __restrict__ out, int Ci, int Co) {
-    const long long n = (long long)Ci * 9 * Co;
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int j = (int)(i & 15);
-    long long r = i >> 4;
-    const int co = (int)(r % Co); r /= Co;
-    const int t = (int)(r % 9);
-    const int ci = (int)(r / 9) * KC + j;
-    out[i] = f2bf(w[((size_t)ci * Co + co) * 9 + t]);
+    return stage2d_launch(deconv2d_bf16<COT, true>, deconv2d_bf16<COT, false>, W % 8 == 0, dim3((unsigned)nb), DecStage<COT>::LDS_BYTES,
+                          stream, x, wp, bias, y, Ci, H, W, th, tw);
 }
 
 // ---- B: one output channel ----------------------------------------------------------------------------------------------------
 constexpr int C1R = 4;                                 // output rows per lane
 constexpr int C1W = 64 * 8;                            // columns per wave: 8 per lane
 constexpr int C1MAXW = 9 * 1024;                       // weights held in LDS: Ci <= 1024 (36 KB, under the default limit)
-
-// 8 columns of a row from element offset `off` of a channel plane; `ok` (VEC: one flag, else one bit per column) says which
-// are inside the map.  Branch-free: an outside column loads the plane's first element and is zeroed by a select, so no load
-// sits behind a branch and the compiler can keep a whole channel's loads in flight.
-template <bool VEC>
-__device__ __forceinline__ u32x4 c1_load_row(const u16* __restrict__ plane, int off, unsigned ok) {
-    if (VEC) {
-        const u32x4 v = *reinterpret_cast<const u32x4*>(plane + (ok ? off : 0));
-        return ok ? v : u32x4{0u, 0u, 0u, 0u};
-    }
-    unsigned e[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const bool in = (ok >> k) & 1u;
-        const unsigned t = plane[in ? off + k : 0];
-        e[k] = in ? t : 0u;
-    }
-    return u32x4{e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16)};
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void conv2d_c1_bf16(const u16* __restrict__ x, const float* __restrict__ w,
@@ -261,12 +139,7 @@ __global__ __launch_bounds__(256) void conv2d_c1_bf16(const u16* __restrict__ x,
     for (int r = 0; r < C1R + 2; ++r) {
         const int gy = r0 - 1 + r;
         const bool rok = gy >= 0 && gy < H;
-        vok[r] = 0u;
-        if (rok) {
-            if (VEC) vok[r] = c0 < W ? 0xffu : 0u;                                 // W % 8 == 0: a segment is all in or all out
-            else
-                for (int k = 0; k < 8; ++k) vok[r] |= (c0 + k < W ? 1u : 0u) << k;
-        }
+        vok[r] = mask8<VEC>(rok, c0, W);
         voff[r] = rok ? gy * W + c0 : 0;
         eok[r] = rok && edge && ecok;
         eoff[r] = eok[r] ? gy * W + ec : 0;
@@ -284,7 +157,7 @@ __global__ __launch_bounds__(256) void conv2d_c1_bf16(const u16* __restrict__ x,
         unsigned ev[C1R + 2];
 #pragma unroll
         for (int r = 0; r < C1R + 2; ++r) {
-            v[r] = c1_load_row<VEC>(plane, voff[r], vok[r]);
+            v[r] = load8<VEC>(plane, voff[r], vok[r]);
             const unsigned t = plane[eoff[r]];
             ev[r] = eok[r] ? t : 0u;
         }
@@ -346,8 +219,7 @@ extern "C" int ecm_deconv2d_bf16_pack_weight(const float* w, unsigned short* pac
     ECM_CHECK_ARG(w && packed && Ci > 0 && Co > 0);
     const long long n = ecm_deconv2d_bf16_packed_elems(Ci, Co);
     if (n == 0) return ECM_EUNSUP;
-    hipLaunchKernelGGL(pack_bf16_deconv2d, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ecm_stream(stream), w, packed, Ci, Co);
-    return ECM_LAUNCH_RESULT();
+    return pack_weight_2d(w, packed, Ci, Co, 9, 1, stream);
 }
 
 extern "C" int ecm_deconv2d_k3s2_bias_bf16_fwd(const unsigned short* x, const unsigned short* wpacked, const float* bias,

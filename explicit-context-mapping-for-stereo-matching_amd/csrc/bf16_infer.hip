@@ -17,8 +17,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int TW = 32;          // output voxels along w per MFMA row (the B operand's 32 columns)
 constexpr int NSLOT = 28;       // weight-image tap slots per 8-channel chunk: 27 taps + 1 zero (conv), or 8 phases padded to even
 
@@ -189,7 +187,7 @@ __device__ __forceinline__ void conv_bf16_body(const u16* __restrict__ x, const 
         for (int ct = 0; ct < CO_TILES; ++ct)
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int co = ct * 32 + (i & 3) + 8 * (i >> 2) + 4 * half;
+                const int co = ct * 32 + mfma32_row(i, half);
                 dst[(size_t)co * DHWo] = f2bf(acc[r][ct][i]);
             }
     }

@@ -32,9 +32,10 @@ def ecm():
 # ------------------------------------------------------------------------------------------------ kernel A parity
 # (B, Ci, Co, H, W): one position; less than a tile; exactly one tile of 4 x 32 inputs; one past it in both directions; several
 # tiles with a ragged edge (w = 78: rows that are not 16-byte aligned); Co = 32; a single 16-channel chunk; the decoder's first
-# level at B = 1 (3 heads) and at B = 4 (12 images)
+# level at B = 1 (3 heads) and at B = 4 (12 images); Co = 32 with 2-byte row loads at two chunks and 16-byte ones at three
 _DECONV = [(1, 96, 64, 1, 1), (2, 96, 64, 3, 5), (1, 96, 64, 4, 32), (1, 96, 64, 8, 32), (1, 96, 64, 9, 33), (1, 96, 64, 5, 33),
-           (2, 96, 64, 17, 78), (1, 32, 32, 5, 40), (1, 16, 64, 4, 7), (3, 96, 64, 36, 60), (12, 96, 64, 144, 240)]
+           (2, 96, 64, 17, 78), (1, 32, 32, 5, 40), (1, 16, 64, 4, 7), (3, 96, 64, 36, 60), (12, 96, 64, 144, 240),
+           (1, 32, 32, 5, 33), (1, 48, 32, 4, 40)]
 
 
 def _deconv_case(ecm, B, Ci, Co, H, W, bias):
@@ -105,7 +106,7 @@ def test_outside_contract_raises(ecm):
 
 
 # ------------------------------------------------------------------------------------------------ guard bands
-@pytest.mark.parametrize("B,Ci,Co,H,W", [(1, 96, 64, 5, 33), (2, 32, 32, 1, 1)])
+@pytest.mark.parametrize("B,Ci,Co,H,W", [(1, 96, 64, 5, 33), (2, 32, 32, 1, 1), (1, 32, 32, 5, 33)])
 def test_guard_bands_deconv2d_bf16(ecm, B, Ci, Co, H, W):
     x, w, b = _R(B, Ci, H, W, seed=1, dtype=BF), _R(Ci, Co, 3, 3, seed=2, scale=0.1), _R(Co, seed=3)
     with torch.no_grad(), guarded(ecm) as g:

@@ -41,7 +41,8 @@ def _within_f32(got, want, label):
 
 # ------------------------------------------------------------------------------------------------ kernel parity
 # (B, Ci, Co, (H, W), k, stride, dilation): every layer kind of the five encoder variants at 8 images of 576x960 (maps 576x960,
-# 288x480, 144x240, SPP branches down to 2x3) and of 384x1248 (96x312), then awkward sizes (w = 78, 33, 1, odd h)
+# 288x480, 144x240, SPP branches down to 2x3) and of 384x1248 (96x312), then awkward sizes (w = 78, 33, 1, odd h), then a single
+# 16-channel chunk (the chunk loop without a prefetch) with 2-byte and with 16-byte row loads, 32 and 64 channels per workgroup
 _CONV = [(8, 32, 32, (576, 960), 3, 1, 1), (8, 32, 32, (288, 480), 3, 1, 1), (8, 64, 64, (144, 240), 3, 1, 1),
          (8, 64, 128, (144, 240), 3, 1, 1), (8, 128, 128, (144, 240), 3, 1, 1), (8, 320, 128, (144, 240), 3, 1, 1),
          (8, 384, 128, (144, 240), 3, 1, 1),
@@ -53,7 +54,8 @@ _CONV = [(8, 32, 32, (576, 960), 3, 1, 1), (8, 32, 32, (288, 480), 3, 1, 1), (8,
          (8, 128, 128, (96, 312), 3, 1, 2), (8, 64, 64, (96, 312), 3, 1, 1), (8, 32, 32, (384, 1248), 3, 2, 1),
          (1, 32, 32, (7, 78), 3, 1, 1), (1, 64, 128, (24, 78), 3, 1, 4), (2, 128, 128, (5, 33), 3, 1, 2),
          (1, 32, 64, (9, 33), 3, 2, 1), (2, 64, 128, (3, 1), 3, 2, 1), (1, 128, 32, (1, 1), 1, 1, 1), (1, 64, 128, (5, 33), 1, 2, 1),
-         (1, 384, 128, (13, 312), 3, 1, 1), (1, 32, 32, (1, 1), 3, 1, 1), (2, 128, 32, (11, 78), 1, 1, 1)]
+         (1, 384, 128, (13, 312), 3, 1, 1), (1, 32, 32, (1, 1), 3, 1, 1), (2, 128, 32, (11, 78), 1, 1, 1),
+         (1, 16, 32, (5, 33), 3, 1, 1), (1, 16, 32, (4, 40), 1, 1, 1), (1, 16, 64, (5, 33), 3, 2, 1)]
 
 
 @pytest.mark.parametrize("B,Ci,Co,hw,k,stride,dil", _CONV)
@@ -68,7 +70,8 @@ def test_conv2d_bf16_parity(ecm, B, Ci, Co, hw, k, stride, dil):
 
 
 @pytest.mark.parametrize("B,Ci,Co,hw,k", [(8, 32, 32, (576, 960), 3), (8, 128, 32, (144, 240), 1), (8, 32, 32, (384, 1248), 3),
-                                          (1, 32, 32, (7, 78), 3), (2, 128, 32, (5, 33), 1), (1, 32, 32, (1, 1), 3)])
+                                          (1, 32, 32, (7, 78), 3), (2, 128, 32, (5, 33), 1), (1, 32, 32, (1, 1), 3),
+                                          (1, 16, 32, (5, 33), 3)])
 def test_conv2d_bf16_fp32_out_parity(ecm, B, Ci, Co, hw, k):
     x = _R(B, Ci, *hw, seed=3, dtype=BF)
     w = _R(Co, Ci, k, k, seed=4, scale=(2.0 / (k * k * Co)) ** 0.5)
@@ -124,7 +127,8 @@ def test_bf16_conv_outside_contract_raises(ecm):
 # ------------------------------------------------------------------------------------------------ guard bands
 @pytest.mark.parametrize("B,Ci,Co,hw,k,stride,dil", [(1, 32, 32, (5, 78), 3, 1, 1), (2, 64, 128, (3, 33), 3, 1, 4),
                                                      (1, 32, 64, (7, 33), 3, 2, 1), (1, 128, 32, (2, 3), 1, 1, 1),
-                                                     (2, 64, 128, (5, 40), 1, 2, 1), (1, 128, 128, (9, 40), 3, 1, 2)])
+                                                     (2, 64, 128, (5, 40), 1, 2, 1), (1, 128, 128, (9, 40), 3, 1, 2),
+                                                     (1, 16, 32, (5, 33), 3, 1, 1)])
 @pytest.mark.parametrize("out", [BF, torch.float32])
 def test_guard_bands_conv2d_bf16(ecm, B, Ci, Co, hw, k, stride, dil, out):
     x, w = _R(B, Ci, *hw, seed=1, dtype=BF), _R(Co, Ci, k, k, seed=2, scale=0.1)

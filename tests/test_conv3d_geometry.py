@@ -1,0 +1,166 @@
+"""The 3-D convolution path table of tests/test_hip_conv3d_fp64.py, checked without a GPU: its restatement of the host-side
+dispatch uses the constants, thresholds and template arguments of csrc/conv3d.hip, conv_wino.hip, conv3d_wgrad.hip, deconv3d.hip,
+conv3d_c1.hip and ops.py as they stand in the sources (a retune must not silently move the cases off the paths they were chosen
+for), every path class has a case, and the Winograd restatement that enters the unit is the convolution itself."""
+import os
+import re
+
+import torch
+
+import test_hip_conv3d_fp64 as T
+from conftest import ROOT
+
+PKG = os.path.join(ROOT, "explicit-context-mapping-for-stereo-matching_amd")
+
+
+def _read(*parts):
+    with open(os.path.join(PKG, *parts)) as f:
+        return f.read()
+
+
+def _ints(src, pattern, what):
+    m = re.findall(pattern, src, re.M)
+    assert len(m) == 1, f"{what}: {len(m)} matches"
+    return tuple(int(v) for v in (m[0] if isinstance(m[0], tuple) else (m[0],)))
+
+
+def _constexpr(src, name, what):
+    return _ints(src, r"^constexpr int [^;]*\b" + name + r" = (\d+)\b", f"{name} in {what}")[0]
+
+
+def _body(src, head):
+    """The text of the function whose definition starts with `head`, up to the first line that is a lone closing brace."""
+    i = src.index(head)
+    return src[i:src.index("\n}\n", i)]
+
+
+def test_direct_forward_dispatch_is_that_of_the_source():
+    src = _read("csrc", "conv3d.hip")
+    assert _constexpr(src, "TW", "conv3d.hip") == T.TW
+    body = _body(src, 'extern "C" int ecm_conv3d_k3_fwd(')
+    assert "if (Ci % 4 != 0 || Co < 1 || Co > 64 || (stride != 1 && stride != 2)) return ECM_EUNSUP;" in body
+    assert "const bool two = Co > 32;" in body
+    assert "(long long)B * ((Do + 1) / 2) * ((Ho + 7) / 8) * ((Wo + TW - 1) / TW);" in body
+    assert _ints(body, r"const bool small = big_blocks < (\d+);", "the small threshold") == (T.SMALL_BLOCKS,)
+    got = [tuple(map(int, m)) for m in re.findall(r"launch_conv<(\d+), (\d+), (\d+), (\d+), (\d+)>\(", body)]
+    # the source's order: stride 1 then 2, one then two channel tiles, `small ? a : b`
+    want = [T.FWD_INST[(s, two, small)] for s in (1, 2) for two in (False, True) for small in (True, False)]
+    assert got == want
+    assert "if (stride == 1) {" in body and body.count("small ?") == 4 and body.count("if (!two) return small") == 2
+    launch = _body(src, "int launch_conv(")
+    assert "tiles_d = (Do + TD - 1) / TD, tiles_h = (Ho + TH - 1) / TH, tiles_w = (Wo + TW - 1) / TW;" in launch
+    xcd = _body(_read("csrc", "common.h"), "__device__ __forceinline__ int ecm_xcd_tile(")
+    assert "x * q + (x < r ? x : r) + (id >> 3)" in xcd
+
+
+def test_weight_gradient_dispatch_is_that_of_the_source():
+    src = _read("csrc", "conv3d_wgrad.hip")
+    assert (_constexpr(src, "CT", "conv3d_wgrad.hip"), _constexpr(src, "TWV", "conv3d_wgrad.hip")) == (T.CT, T.TWV)
+    body = _body(src, 'extern "C" int ecm_conv3d_k3_wgrad(')
+    assert "if (stride == 1) return launch_wgrad<%d, %d, %d, %d>(" % T.WGRAD_INST["s1"] in body
+    assert "    return launch_wgrad<%d, %d, %d, %d>(" % T.WGRAD_INST["s2"] in body
+    assert len(re.findall(r"launch_wgrad<", body)) == 2
+    wino = _body(src, 'extern "C" int ecm_conv_wino_wgrad(')
+    assert "if (kd == 3) return launch_wgrad_wino<%d, %d, %d>(" % T.WGRAD_INST["wino"] in wino
+    workers = _body(src, "inline int wgrad_workers(")
+    assert "int occ = 1" in workers and "((Ci + CT - 1) / CT) * ((Co + CT - 1) / CT)" in workers
+    assert _ints(workers, r"long long p = (\d+) \* occ / ytiles;", "wgrad_workers") == (T.WGRAD_WORKERS,)
+    assert "if (p < 1) p = 1;" in workers and "if (p > ntiles) p = ntiles;" in workers
+    assert src.count("wgrad_workers(Ci, Co, ntiles, KD == 3 ? 1 : 2);") == 2 and T.WGRAD_OCC3D == 1
+    # tile counts: TWV columns; the Winograd form tiles the (stride-1) volume itself
+    assert "tiles_d = (Do + TD - 1) / TD, tiles_h = (Ho + TH - 1) / TH, tiles_w = (Wo + TWV - 1) / TWV;" in _body(src, "int launch_wgrad(")
+    assert "tiles_d = (D + TD - 1) / TD, tiles_h = (H + TH - 1) / TH, tiles_w = (W + TWV - 1) / TWV;" in _body(src, "int launch_wgrad_wino(")
+    # the persistent schedule worker_runs restates
+    for line in ("if ((gridDim.x & 7u) == 0u) {", "const unsigned start = xcd * q + (xcd < rr ? xcd : rr);",
+                 "tile0 = start + (blockIdx.x >> 3);", "tile_end = start + q + (xcd < rr ? 1u : 0u);", "tile_step = gridDim.x >> 3;",
+                 "for (unsigned tile = tile0; tile < tile_end; tile += tile_step) {"):
+        assert line in src, line
+    assert T.worker_runs(64, 90)[:8] == [2] * 8 and sorted(set(T.worker_runs(64, 90))) == [1, 2] and sum(T.worker_runs(64, 90)) == 90
+    assert T.worker_runs(42, 48) == [2] * 6 + [1] * 36 and T.worker_runs(16, 18).count(2) == 2
+
+
+def test_winograd_dispatch_is_that_of_the_source():
+    src = _read("csrc", "conv_wino.hip")
+    assert _ints(src, r"^constexpr int WINO_CIC3 = (\d+), WINO_CIC2 = \d+;", "WINO_CIC3") == (T.WINO_CIC3,)
+    assert "if (kd == 3) return launch_wino<%d, %d, %d, WINO_CIC3>(" % T.WINO_INST[:3] in src
+    launch = _body(src, "int launch_wino(")
+    assert "tiles_wt = (W + 1) / 2, ntile = ((H + 1) / 2) * tiles_wt;" in launch
+    assert _ints(launch, r"const int tblocks = \(ntile \+ (\d+) \* TR - 1\) / \((\d+) \* TR\);", "tile block") == (T.WINO_BLOCK,) * 2
+    assert "const int groups = (Co + 31) / 32, nchunks = (Ci + CIC - 1) / CIC;" in launch
+    assert "if (W < 2) return ECM_EUNSUP;" in src
+    ops = _read("ops.py")
+    assert "    return WINOGRAD and x.shape[-1] >= 2 and vol * 128 <= 0x80000000\n" in _body(ops + "\n}\n", "def _wino_ok(x):")
+    assert "    return w.shape[0] == 1 and stride == 1 and w.shape[1] <= 32 and w.shape[1] % 8 == 0\n" in ops
+    assert "    if stride == 1 and _wino_ok(x) and WINOGRAD_WGRAD:\n        return _wino_wgrad(x, gy, Co, Ci, 3, w)" in ops
+    assert T.wino_ok((4, 6, 2)) and not T.wino_ok((4, 6, 1)) and not T.wino_ok((4, 6, 8), False) and not T.wino_ok((256, 256, 257))
+    assert T.is_c1(1, 32, 1) and T.is_c1(1, 8, 1) and not T.is_c1(1, 12, 1) and not T.is_c1(1, 40, 1) and not T.is_c1(1, 32, 2)
+
+
+def test_deconv_and_c1_constants_are_those_of_the_sources():
+    src = _read("csrc", "deconv3d.hip")
+    assert _constexpr(src, "TW", "deconv3d.hip") == T.TW
+    assert _ints(src, r"static constexpr int TD = (\d+), TH = (\d+), NTAPS = 9 \* KD;", "DeconvCfg") == (T.DECONV_TD, T.DECONV_TH)
+    body = _body(src, 'extern "C" int ecm_deconv3d_k3s2_fwd(')
+    assert "if (Co > 32) return launch_deconv<%d, %d>(" % T.DECONV_INST[True] in body
+    assert "    return launch_deconv<%d, %d>(" % T.DECONV_INST[False] in body
+    assert "if (Ci % 4 != 0 || Co < 1 || Co > 64) return ECM_EUNSUP;" in body
+    assert "tiles_d = (D + Cfg::TD - 1) / Cfg::TD, tiles_h = (H + Cfg::TH - 1) / Cfg::TH, tiles_w = (W + TW - 1) / TW;" in src
+    c1 = _read("csrc", "conv3d_c1.hip")
+    got = {n: _constexpr(c1, n, "conv3d_c1.hip") for n in ("VT_W", "VT_H", "VT_D", "DTH", "DTW", "GTD", "GTH", "GTW")}
+    assert got == {n: getattr(T, n) for n in got}
+    assert _ints(c1, r"inline int c1_workers\(long long ntiles\) \{ return \(int\)\(ntiles < (\d+) \? ntiles : (\d+)\); \}",
+                 "c1_workers") == (T.C1_WORKERS,) * 2
+    assert "((D + GTD - 1) / GTD) * ((H + GTH - 1) / GTH) * ((W + GTW - 1) / GTW);" in c1
+    assert "for (unsigned tile = blockIdx.x; tile < (unsigned)ntiles; tile += gridDim.x) {" in c1
+    assert "if (valu && Ci % 2 == 0) return launch_c1_fwd_v<false>(" in c1
+
+
+def test_restated_dispatch_on_known_shapes():
+    """The figures the sources and the issue quote: the step's 48 x 144 x 240 volume takes the large tiles, the hourglass's
+    1/16 level the small one; 64 -> 64 weight gradients run 64 workers; 612 tiles of the 32 -> 1 layer meet 512 workers."""
+    assert T.direct_fwd(4, 32, 32, (48, 144, 240), 1)["inst"] == (1, 1, 4, 8, 4)
+    assert T.direct_fwd(4, 32, 64, (48, 144, 240), 2)["inst"] == (2, 2, 2, 8, 2)
+    assert T.direct_fwd(4, 64, 64, (12, 36, 60), 1)["inst"] == (2, 1, 1, 4, 4)
+    g = T.direct_fwd(4, 32, 32, (49, 9, 33), 1)
+    assert not g["small"] and g["nblk"] == 4 * 13 * 2 * 2 and g["ragged"] == (True, True, True)
+    assert T.direct_fwd(3, 32, 32, (49, 9, 33), 1)["small"]                     # 300 blocks: below the threshold
+    g = T.wgrad_geom("s1", 2, 64, 64, (10, 17, 33))
+    assert (g["P"], g["ntiles"]) == (64, 90)
+    g = T.wgrad_geom("wino", 2, 40, 72, (5, 10, 50))
+    assert (g["ytiles"], g["P"], g["ntiles"]) == (6, 42, 48)
+    assert T.wgrad_geom("s1", 1, 128, 128, (5, 9, 33))["P"] == 16
+    g = T.c1_geom(6, 8, (33, 17, 33))
+    assert g["wgrad_tiles"] == 612 and g["wgrad_P"] == 512 and g["wgrad_runs"].count(2) == 100
+    g = T.wino_geom(1, 2, 8, (3, 5, 6))
+    assert (g["tiles_wt"], g["ntile"], g["tblocks"], g["nchunks"]) == (3, 9, 1, 1)
+
+
+def test_every_path_class_has_a_case():
+    assert T.missing_classes() == []
+    reached = {(fam, g["inst"]) for c in T.CASES.values() for _, fam, g in T.launches(c) if "inst" in g}
+    assert {i for f, i in reached if f == "direct"} == set(T.FWD_INST.values())
+    assert {i for f, i in reached if f == "wgrad"} == set(T.WGRAD_INST.values())
+    assert {i for f, i in reached if f == "deconv"} == set(T.DECONV_INST.values())
+    names = {c for c in T.CASES.values()}
+    assert len(names) == len(T.CASES), "two cases share one specification"
+
+
+def test_the_check_can_fail(monkeypatch):
+    """A retuned threshold moves the large-tile cases onto the small tile, and missing_classes() says so."""
+    monkeypatch.setattr(T, "SMALL_BLOCKS", 512)
+    missing = T.missing_classes()
+    assert any("(1, 1, 4, 8, 4)" in m for m in missing) and any("(2, 2, 2, 8, 2)" in m for m in missing)
+
+
+def test_winograd_restatement_is_the_convolution_in_fp64():
+    """The third candidate of the unit evaluates the same operation: the check of the GPU module, run here too."""
+    for shape in T.RESTATEMENT_SHAPES:
+        T.test_winograd_restatement_is_the_convolution(shape)
+    x, w = T.seeded("c3.rs.x", 1, 2, 2, 4, 5), T.seeded("c3.rs.w", 3, 2, 3, 3, 3)
+    assert T.wino_fwd(x, w).dtype == torch.float32 and T.wino_wgrad(x, T.wino_fwd(x, w)).shape == w.shape
+
+
+def test_chain_restatement_is_the_convolution_in_fp64():
+    """The summation-order candidate of the direct kernel's unit evaluates the same operation: the check of the GPU module, here too."""
+    for stride in (1, 2):
+        T.test_chain_restatement_is_the_convolution(stride)

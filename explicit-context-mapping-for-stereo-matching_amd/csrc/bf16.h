@@ -10,6 +10,3 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));     // 16 bytes as a
 
 __device__ __forceinline__ float bf2f(u16 v) { return __builtin_bit_cast(float, (unsigned)v << 16); }
 __device__ __forceinline__ u16 f2bf(float v) { return __builtin_bit_cast(u16, (__bf16)v); }
-
-// row of the 32x32 accumulator tile that register i of a lane in half `half` (= lane >> 5) holds; the column is lane & 31
-__host__ __device__ constexpr int mfma32_row(int i, int half) { return (i & 3) + 8 * (i >> 2) + 4 * half; }

@@ -50,6 +50,9 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 __device__ __forceinline__ float leaky(float x) { return x > 0.f ? x : 0.01f * x; }   // nn.LeakyReLU default slope
 
+// row of the 32x32 accumulator tile that register i of a lane in half `half` (= lane >> 5) holds; the column is lane & 31
+__host__ __device__ constexpr int mfma32_row(int i, int half) { return (i & 3) + 8 * (i >> 2) + 4 * half; }
+
 // GroupNorm's per-channel affine map y = fma(x, a, sh): the coefficients are formed the same way wherever they are needed
 // (gn3d.hip's kernels, the classifier tail's fused normalisation in conv3d_c1.hip), so that every kernel writes the same bits
 // and the ReLU mask recomputed in the backward pass is bit-identical to the forward decision.

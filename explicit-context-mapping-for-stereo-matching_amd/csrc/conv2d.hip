@@ -4,11 +4,8 @@
 //   * the class-indexed convolutions of the collapsed cost volume + dres0.0 (cmfsm.py:667-684; see costvol_conv.hip):
 //     P = 3x3, 32 -> 15*32 on the reference features and Q = sheared 3x5, 32 -> 6*32 on the left-padded target features;
 //   * every stride-1 data gradient (the same kernel on the flipped / transposed weights).
-// Same GEMM view and staging as conv3d.hip (its KD = 1 instantiations remain the 32/64-channel fast path):
-//   D[co][pixel] += sum_k A[co][k] B[k][pixel],  k = (tap, ci);  A = weights from LDS (global->LDS DMA, double buffered),
-//   B = 32 consecutive x of one row of the staged halo tile (NCHW as it stands is the operand layout), register-pipelined
-//   through buffer descriptors whose range check supplies the zero padding.
-// New here: output channels beyond one workgroup's COT*32 go to blockIdx.y ("co groups", packed weights grouped to match);
+// GEMM view and staging: fp32_conv_stage.h; the kernel and its dispatch: conv2d_kernel.h.
+// Output channels beyond one workgroup's COT*32 go to blockIdx.y ("co groups", packed weights grouped to match);
 // kernel shape KH x KW, stride, dilation and the (possibly asymmetric) padding are template / run-time parameters; input
 // channel counts that are not a multiple of the chunk (the 3-channel stem) read zeros for the missing planes.
 #include "conv2d_kernel.h"

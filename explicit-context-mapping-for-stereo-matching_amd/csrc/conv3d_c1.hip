@@ -273,7 +273,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_c1_fwd(const float* __restrict_
         for (int r = 0; r < 2; ++r)
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int tap = (i & 3) + 8 * (i >> 2) + 4 * half;
+                const int tap = mfma32_row(i, half);
                 if (tap < 27) Ts[tap * MPOS + (wave * 2 + r) * 32 + l31] = acc[r][i];
             }
         __syncthreads();
@@ -492,7 +492,7 @@ __global__ __launch_bounds__(256) void conv3d_c1_wgrad(const float* __restrict__
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-        const int ci = (i & 3) + 8 * (i >> 2) + 4 * half;
+        const int ci = mfma32_row(i, half);
         Ps[wave * 1024 + ci * 32 + l31] = acc[i];
     }
     __syncthreads();

@@ -352,7 +352,7 @@ __global__ __launch_bounds__(256, KD == 3 ? 1 : 2) void conv3d_wgrad_mfma(const 
             const int j = t / KD, kd = t % KD;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int co = co0 + (i & 3) + 8 * (i >> 2) + 4 * half;
+                const int co = co0 + mfma32_row(i, half);
                 if (co < Co && ci < Ci) pw[((size_t)((wave * 4 + j) * KD + kd) * Co + co) * Ci + ci] = acc[t][i];
             }
         }
@@ -367,7 +367,7 @@ __global__ __launch_bounds__(256, KD == 3 ? 1 : 2) void conv3d_wgrad_mfma(const 
         const int ci = ci0 + l31;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int co = co0 + (i & 3) + 8 * (i >> 2) + 4 * half;
+            const int co = co0 + mfma32_row(i, half);
             if (co < Co && ci < Ci) pp[((size_t)co * Ci + ci) * NTAPS + tap] = acc[t][i];
         }
     }

@@ -386,7 +386,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino_mfma(const float* __restrict
     for (int q = 0; q < NPR; ++q)
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int co = (i & 3) + 8 * (i >> 2) + 4 * half;
+            const int co = mfma32_row(i, half);
             const float m0 = acc[0][q][i], m1 = acc[1][q][i], m2 = acc[2][q][i], m3 = acc[3][q][i];
             const f32x2e tb = {m0 + m1 + m2, m1 - m2 - m3};
             *reinterpret_cast<f32x2e*>(Ts + ((((q * 4 + wave) * 32 + co) * 32 + l31) * 2)) = tb;

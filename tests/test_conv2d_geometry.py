@@ -1,5 +1,5 @@
 """The 2-D convolution path table of tests/test_hip_conv2d_fp64.py, checked without a GPU: its restatement of the host-side
-dispatch uses the constants, thresholds and template arguments of csrc/conv2d_kernel.h, the seven conv2d_case_*.hip,
+dispatch uses the constants, thresholds and template arguments of csrc/conv2d_kernel.h, fp32_conv_stage.h, the seven conv2d_case_*.hip,
 conv3d_wgrad.hip (2-D part), conv_wino.hip (KD 1), deconv3d.hip (KD 1), conv2d_c1.hip and ops.py as they stand in the sources (a
 retune must not silently move the cases off the paths they were chosen for), every path class has a case, the restatements that
 enter the unit are the convolution itself, and the operands of the conv2d_c1_relu cases leave at most 0.1 % of the outputs within
@@ -12,14 +12,14 @@ import torch
 
 import test_hip_conv2d_fp64 as T
 from conftest import ROOT
-from test_conv3d_geometry import _body, _constexpr, _ints, _read
+from test_conv3d_geometry import _body, _constexpr, _ints, _read, stage_constants_exist_once
 
 PKG = os.path.join(ROOT, "explicit-context-mapping-for-stereo-matching_amd")
 
 
 def test_conv2d_mfma_dispatch_is_that_of_the_source():
     src = _read("csrc", "conv2d_kernel.h")
-    assert _constexpr(src, "TW", "conv2d_kernel.h") == T.TW
+    assert stage_constants_exist_once() == T.TW
     assert "static constexpr int TH = 4 * NT;" in src
     plan = _body(src, "inline C2Plan c2_plan(")
     assert "p.cot = Co <= 32 ? 1 : Co <= 64 ? 2 : (kh * kw != 1 && Co % 96 == 0 && Co % 128 != 0) ? 3 : 4;" in plan
@@ -47,7 +47,8 @@ def test_conv2d_mfma_dispatch_is_that_of_the_source():
     assert disp.count("C2_GO(") == 3 + 2 + 2 + 1 + 2 + 1                # (+ 1: the #define)
     launch = _body(src, "int launch_c2(")
     assert "tiles_h = (Ho + Cfg::TH - 1) / Cfg::TH, tiles_w = (Wo + TW - 1) / TW;" in launch
-    assert "dim3((unsigned)nblk, (unsigned)groups)" in launch
+    assert "(long long)B * tiles_h * tiles_w, (unsigned)groups, 256," in launch           # the co groups are the grid's y extent
+    assert "hipLaunchKernelGGL(kern, dim3((unsigned)nblk, ngrp), dim3(nthr), lds, st, args...);" in _read("csrc", "fp32_conv_stage.h")
     assert "int bid = ecm_xcd_tile(blockIdx.x, gridDim.x);" in src and "if (oh >= Ho || ow >= Wo) continue;" in src
     assert "if (co < Co) yp[(size_t)co * HWo] = acc[r][ct][i];" in src
 
@@ -131,7 +132,7 @@ def test_weight_gradient_dispatch_is_that_of_the_source():
 
 def test_deconv_and_c1_constants_are_those_of_the_sources():
     src = _read("csrc", "deconv3d.hip")
-    assert _constexpr(src, "TW", "deconv3d.hip") == T.TW
+    assert stage_constants_exist_once() == T.TW
     assert _ints(src, r"static constexpr int TD = (\d+), TH = (\d+), NTAPS = 9 \* KD;", "DeconvCfg") == (1, T.DECONV_TH)
     for fn, tail in (("ecm_deconv2d_k3s2_fwd", ""), ("ecm_deconv2d_k3s2_bias_fwd", ", true")):
         body = _body(src, 'extern "C" int %s(' % fn)

@@ -1,6 +1,6 @@
 """The 3-D convolution path table of tests/test_hip_conv3d_fp64.py, checked without a GPU: its restatement of the host-side
-dispatch uses the constants, thresholds and template arguments of csrc/conv3d.hip, conv_wino.hip, conv3d_wgrad.hip, deconv3d.hip,
-conv3d_c1.hip and ops.py as they stand in the sources (a retune must not silently move the cases off the paths they were chosen
+dispatch uses the constants, thresholds and template arguments of csrc/conv3d.hip, fp32_conv_stage.h, conv_wino.hip,
+conv3d_wgrad.hip, deconv3d.hip, conv3d_c1.hip and ops.py as they stand in the sources (a retune must not silently move the cases off the paths they were chosen
 for), every path class has a case, and the Winograd restatement that enters the unit is the convolution itself."""
 import os
 import re
@@ -28,6 +28,32 @@ def _constexpr(src, name, what):
     return _ints(src, r"^constexpr int [^;]*\b" + name + r" = (\d+)\b", f"{name} in {what}")[0]
 
 
+def stage_constants_exist_once():
+    """TW and the staging geometry live in fp32_conv_stage.h alone: the three kernels that are built on it define none of them."""
+    stage = _read("csrc", "fp32_conv_stage.h")
+    users = [_read("csrc", f) for f in ("conv3d.hip", "deconv3d.hip", "conv2d_kernel.h")]
+    for u in users:
+        assert '#include "fp32_conv_stage.h"' in u
+    for pattern in (r"constexpr int TW\b", r"typedef float f32x16\b", r"constexpr int NPOS =", r"constexpr int PP =", r"constexpr int NX =",
+                    r"constexpr int NWQ =", r"constexpr int XS_FLOATS =", r"constexpr int WS_FLOATS =", r"constexpr int LDS_BYTES =",
+                    r"0x80000000u", r"__builtin_amdgcn_global_load_lds\(", r"__builtin_amdgcn_raw_buffer_load_b32\(", r"s_waitcnt vmcnt\(0\)",
+                    r"ecm_allow_lds\(", r"hipLaunchKernelGGL\(kern,"):
+        assert len(re.findall(pattern, stage)) == 1, pattern
+        for u in users:
+            assert not re.search(pattern, u), pattern
+    for u in users:                                                     # kernel and launcher read the one LDS_BYTES
+        assert len(re.findall(r"Cfg::Stage::LDS_BYTES", u)) == 1 and len(re.findall(r"stage_run<G, (true|false), (true|false)>\(smem, tid,", u)) == 1
+    common = _read("csrc", "common.h")
+    assert len(re.findall(r"constexpr int mfma32_row\(", common)) == 1 and "mfma32_row" not in _read("csrc", "bf16.h")
+    srcs = [_read("csrc", f) for f in sorted(os.listdir(os.path.join(PKG, "csrc"))) if f.endswith((".hip", ".h"))]
+    assert sum(len(re.findall(r"8 \* \(i >> 2\)", s)) for s in srcs) == 1       # the map is spelled out in mfma32_row alone
+    return _constexpr(stage, "TW", "fp32_conv_stage.h")
+
+
+def test_stage_constants_exist_once():
+    assert stage_constants_exist_once() == T.TW
+
+
 def _body(src, head):
     """The text of the function whose definition starts with `head`, up to the first line that is a lone closing brace."""
     i = src.index(head)
@@ -36,7 +62,7 @@ def _body(src, head):
 
 def test_direct_forward_dispatch_is_that_of_the_source():
     src = _read("csrc", "conv3d.hip")
-    assert _constexpr(src, "TW", "conv3d.hip") == T.TW
+    assert stage_constants_exist_once() == T.TW
     body = _body(src, 'extern "C" int ecm_conv3d_k3_fwd(')
     assert "if (Ci % 4 != 0 || Co < 1 || Co > 64 || (stride != 1 && stride != 2)) return ECM_EUNSUP;" in body
     assert "const bool two = Co > 32;" in body
@@ -98,7 +124,7 @@ def test_winograd_dispatch_is_that_of_the_source():
 
 def test_deconv_and_c1_constants_are_those_of_the_sources():
     src = _read("csrc", "deconv3d.hip")
-    assert _constexpr(src, "TW", "deconv3d.hip") == T.TW
+    assert stage_constants_exist_once() == T.TW
     assert _ints(src, r"static constexpr int TD = (\d+), TH = (\d+), NTAPS = 9 \* KD;", "DeconvCfg") == (T.DECONV_TD, T.DECONV_TH)
     body = _body(src, 'extern "C" int ecm_deconv3d_k3s2_fwd(')
     assert "if (Co > 32) return launch_deconv<%d, %d>(" % T.DECONV_INST[True] in body

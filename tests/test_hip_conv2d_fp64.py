@@ -54,7 +54,7 @@ pytestmark = pytest.mark.gpu
 
 
 # ---- the host-side dispatch, restated (tests/test_conv2d_geometry.py pins every constant to its source) -------------------------
-TW = 32                                 # conv2d_kernel.h / deconv3d.hip: output columns per tile
+TW = 32                                 # fp32_conv_stage.h: output columns per tile (conv2d_kernel.h, deconv3d.hip)
 TWV, CT = 16, 32                        # conv3d_wgrad.hip: output pixels per tile row, channel tile
 C2_MIN_BLOCKS = 1536                    # c2_min_blocks(), default
 # dispatch_c2<KH, KW, STRIDE, DIL, COTS>: bit (1 << cot) set = the case is instantiated for that many channel tiles
@@ -185,7 +185,7 @@ def deconv_geom(B, Ci, Co, H, W, Ho, Wo, bias):
     """ecm_deconv2d_k3s2_fwd / _bias_fwd on x [B, Ci, H, W] -> [B, Co, Ho, Wo] (each extent 2n or 2n - 1)."""
     assert Ci % 4 == 0 and 1 <= Co <= 64 and 2 * H - 1 <= Ho <= 2 * H and 2 * W - 1 <= Wo <= 2 * W, "ECM_EUNSUP"
     return dict(inst=(2 if Co > 32 else 1, DECONV_CIC, 1) + ((True,) if bias else ()), nblk=B * cdiv(H, DECONV_TH) * cdiv(W, TW),
-                parity=(Ho % 2, Wo % 2), ragged=(H % DECONV_TH != 0, W % TW != 0), bias=bias)
+                parity=(Ho % 2, Wo % 2), ragged=(H % DECONV_TH != 0, W % TW != 0), bias=bias, chunks=Ci // DECONV_CIC)
 
 
 def c1_strips(H):
@@ -306,6 +306,7 @@ DECODER = {
     "db_96_64": Case("deconvb", 1, 96, 64, 6, 33),
     "db_8_40": Case("deconvb", 2, 8, 40, 7, 9),
     "db_persistent": Case("deconvb", 2, 96, 64, 41, 120),               # 6 channel tiles: P = 85, 96 tiles; gb over 2 chunks of 16384
+    "db_4_32_one_chunk": Case("deconvb", 1, 4, 32, 5, 33),              # Ci = CIC: the chunk loop without a prefetch; H, W ragged
     "ch_scalar": Case("chsum", 2, 5, 0, 7, 9),                          # HW % 4 != 0: scalar loads, one chunk
     "ch_chunks": Case("chsum", 1, 3, 0, 131, 127),                      # 16637 elements: a second chunk of 253
     # ops.conv2d_c1_relu: 64 x 32 tiles, 4 channels per step, strips of 4 tiles in the weight gradient
@@ -459,6 +460,11 @@ def missing_classes():
         want["stride-2 3x3 data gradient: H, W parity %s" % (par,)] = any(g["parity"] == par for g in dg)
     want["stride-2 3x3 data gradient: H % 4 and W % 32 ragged"] = any(all(g["ragged"]) for g in dg)
     want["ops.deconv2d_k3s2_bias: H % 4 and W % 32 ragged"] = any(all(g["ragged"]) for q, g in dec if g["bias"])
+    for n in (1, 2, 3):         # the regimes of the shared chunk loop (fp32_conv_stage.h): no prefetch, one, a prefetch of a prefetch
+        want["launch_deconv<.,4,1>: %s chunk(s) of CIC" % (n if n < 3 else ">= 3")] = any(g["chunks"] == n if n < 3 else g["chunks"] >= 3 for q, g in dec)
+        for kk, cic in ((9, 4), (1, 8)):
+            want["conv2d_mfma %s, CIC %d: %s chunk(s)" % ("3x3" if kk == 9 else "1x1", cic, n if n < 3 else ">= 3")] = any(
+                g["case"][0] * g["case"][1] == kk and g["inst"][2] == cic and (g["chunks"] == n if n < 3 else g["chunks"] >= 3) for g in c2)
     zi = [g["zero_insert"] for g in c2 if "zero_insert" in g]
     for par in (0, 1):
         want["stride-2 1x1 data gradient: H %s" % ("odd" if par else "even")] = any(z[0] == par for z in zi)

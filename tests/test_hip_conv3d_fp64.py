@@ -51,7 +51,7 @@ def cdiv(a, b):
 
 
 # ---- the host-side dispatch, restated (tests/test_conv3d_geometry.py pins every constant to its source) -------------------------
-TW = 32                         # conv3d.hip / deconv3d.hip: output columns per tile
+TW = 32                         # fp32_conv_stage.h: output columns per tile (conv3d.hip, deconv3d.hip)
 TWV, CT = 16, 32                # conv3d_wgrad.hip: output voxels per tile row, channel tile
 SMALL_BLOCKS = 384              # ecm_conv3d_k3_fwd: fewer 2x8x32 blocks than this -> the 1x4x32 tile
 # (stride, Co > 32, small) -> launch_conv<CO_TILES, STRIDE, TD, TH, CIC>
@@ -138,7 +138,7 @@ def deconv_geom(B, Ci, Co, in_dims, o_dims):
     assert Ci % 4 == 0 and 1 <= Co <= 64 and all(2 * n - 1 <= o <= 2 * n for n, o in zip(in_dims, o_dims)), "ECM_EUNSUP"
     D, H, W = in_dims
     return dict(inst=DECONV_INST[Co > 32], nblk=B * cdiv(D, DECONV_TD) * cdiv(H, DECONV_TH) * cdiv(W, TW),
-                parity=tuple(o % 2 for o in o_dims), ragged=(H % DECONV_TH != 0, W % TW != 0))
+                parity=tuple(o % 2 for o in o_dims), ragged=(H % DECONV_TH != 0, W % TW != 0), chunks=Ci // DECONV_CIC)
 
 
 def c1_geom(B, Ci, dims):
@@ -208,6 +208,7 @@ DECONV = {
     "t_64_32_ragged": Case("deconv", 2, 64, 32, (3, 5, 35)),
     "t_8_40": Case("deconv", 1, 8, 40, (3, 5, 33)),
     "t_persistent": Case("deconv", 3, 64, 64, (5, 9, 18)),                # role-exchanged <2,1,4,3>: P = 64, 90 tiles
+    "t_4_32_one_chunk": Case("deconv", 1, 4, 32, (2, 5, 33)),             # Ci = CIC: the chunk loop without a prefetch; H, W ragged
 }
 C1 = {
     # the 32 -> 1 layer: conv3d_c1_fwd_v<false>, conv3d_c1_dgrad, conv3d_c1_wgrad
@@ -333,6 +334,8 @@ def missing_classes():
             want["deconv: %s output %s" % (n, "2n - 1" if par else "2n")] = any(g["parity"][i] == par for _, g in dec)
     want["deconv: ragged against 4 x 32"] = any(all(g["ragged"]) for _, g in dec)
     want["deconv forward (ops.deconv3d_k3s2)"] = any(q == "y" for q, _ in dec)
+    for n in (1, 2, 3):         # the regimes of the shared chunk loop (fp32_conv_stage.h): no prefetch, one, a prefetch of a prefetch
+        want["deconv: %s chunk(s) of CIC" % (n if n < 3 else ">= 3")] = any(g["chunks"] == n if n < 3 else g["chunks"] >= 3 for _, g in dec)
     # 32 -> 1
     for ci in (8, 16, 24, 32):
         want["c1: Ci = %d, forward ragged" % ci] = any(c.Ci == ci and is_c1(c.Co, c.Ci, c.stride) and any(c1_geom(c.B, c.Ci, c.dims)["fwd_ragged"])

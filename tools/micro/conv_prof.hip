@@ -19,13 +19,13 @@ int main(int argc, char** argv) {
         const double fl = 2.0 * 27 * Ci * Co * (double)Do * Ho * Wo * B;
         printf("rc=%d  %.3f ms  %.1f TFLOP/s\n", rc, ms, fl / ms / 1e9);
     }
-    unsigned long long prof[32];
+    unsigned long long prof[16];                      // [wave][mark], fp32_conv_stage.h
     hipMemcpyFromSymbol(prof, HIP_SYMBOL(cv_prof), sizeof(prof));
-    const char* names[7] = {"setup + first prefetch", "barrier A", "LDS stores (+vmcnt)", "barrier B", "prefetch issue", "MFMA loop", "epilogue"};
+    const char* names[4] = {"setup + first prefetch", "commit (barriers, LDS stores)", "prefetch issue + MFMA loop", "epilogue"};
     for (int w = 0; w < 4; w += 3) {
-        unsigned long long tot = 0; for (int i = 0; i < 7; ++i) tot += prof[w * 8 + i];
+        unsigned long long tot = 0; for (int i = 0; i < 4; ++i) tot += prof[w * 4 + i];
         printf("wave %d total %llu cycles\n", w, tot);
-        for (int i = 0; i < 7; ++i) printf("   %-26s %10llu  %5.1f%%\n", names[i], prof[w * 8 + i], 100.0 * prof[w * 8 + i] / tot);
+        for (int i = 0; i < 4; ++i) printf("   %-30s %10llu  %5.1f%%\n", names[i], prof[w * 4 + i], 100.0 * prof[w * 4 + i] / tot);
     }
     return 0;
 }

@@ -134,12 +134,13 @@ def soft_argmin(cost: torch.Tensor) -> torch.Tensor:
 # ----------------------------------------------------------------------------
 # a3: eight-related context mapping  (cmfsm.py:304-358, 391-428, 431-593)
 # ----------------------------------------------------------------------------
-def offset_tables(scale: int = 4):
-    """The nine [1,2,s,s] tables of matrix_generation (cmfsm.py:391-428), indices 0..8."""
+def offset_tables(scale: int = 4, dtype: torch.dtype = torch.float32):
+    """The nine [1,2,s,s] tables of matrix_generation (cmfsm.py:391-428), indices 0..8, in `dtype` (the reference's are
+    fp32; an fp64 evaluation of the functions below passes its inputs' dtype)."""
     s = scale
-    half = torch.cat([torch.arange(-(s // 2), 0), torch.arange(1, s // 2 + 1)]).float()   # [-2,-1,1,2]
+    half = torch.cat([torch.arange(-(s // 2), 0), torch.arange(1, s // 2 + 1)]).to(dtype)   # [-2,-1,1,2]
     centre = torch.stack([half.view(1, s).expand(s, s), half.view(s, 1).expand(s, s)], 0)  # ch0 varies in x, ch1 in y
-    up = torch.arange(1, s + 1).float()
+    up = torch.arange(1, s + 1).to(dtype)
     tabs = [centre.clone() for _ in range(9)]
     tabs[1][0] = (s - up + 1).view(1, s).expand(s, s)       # :410
     tabs[2][0] = up.view(1, s).expand(s, s)                 # :411
@@ -191,15 +192,15 @@ def ecm_weights_eight(lr, hr, sd, key="mapping_matrix.similarity1"):
     s = W // lr.shape[-1]
     if s % 2 != 0:
         raise ValueError("odd scale (reference calls exit(), cmfsm.py:448-449)")
-    tabs = [t.repeat(B, 1, H // s, W // s) for t in offset_tables(s)]          # :454-462
+    tabs = [t.repeat(B, 1, H // s, W // s) for t in offset_tables(s, hr.dtype)]          # :454-462
     lr_up = nn_upsample(lr, s)                                                  # :465-468
     logits = []
     for dy, dx, t in EIGHT_NEIGHBOURS:
         ry, rx, sy, sx = _slices(dy, dx, s, H, W)
-        rep = torch.cat([lr_up[:, :, sy, sx], hr[:, :, ry, rx], tabs[t][:, :, sy, sx]], 1)   # e.g. :484
-        val = similarity_mlp(rep, sd, key)
         full = torch.full((B, 1, H, W), PAD_LOGIT, dtype=hr.dtype)             # padding1/2 :451-452
-        full[:, :, ry, rx] = val
+        if full[:, :, ry, rx].numel():                                         # (one cell row / column: no such neighbour anywhere)
+            rep = torch.cat([lr_up[:, :, sy, sx], hr[:, :, ry, rx], tabs[t][:, :, sy, sx]], 1)   # e.g. :484
+            full[:, :, ry, rx] = similarity_mlp(rep, sd, key)
         logits.append(full)
     return F.softmax(torch.cat(logits, 1), dim=1)                               # :551-552
 
@@ -411,15 +412,15 @@ SIX_RIGHT = ((0, 0, 0), (0, 1, 1), (0, -1, 2))
 def _six_planes(lr, hr, sd, key, neighbours):
     B, C, H, W = hr.shape
     s = W // lr.shape[-1]
-    tabs = [t.repeat(B, 1, H // s, W // s) for t in offset_tables(s)]        # generic even scale (:455-470)
+    tabs = [t.repeat(B, 1, H // s, W // s) for t in offset_tables(s, hr.dtype)]        # generic even scale (:455-470)
     lr_up = nn_upsample(lr, s)
     logits = []
     for dy, dx, t in neighbours:
         ry, rx, sy, sx = _slices(dy, dx, s, H, W)
-        rep = torch.cat([lr_up[:, :, sy, sx], hr[:, :, ry, rx], tabs[t][:, :, sy, sx]], 1)
-        val = similarity_mlp(rep, sd, key, final_act=True)                    # relu3, cmfsm_sub_8.py:318,342
         full = torch.zeros(B, 1, H, W, dtype=hr.dtype)                         # zero padding participates in the softmax
-        full[:, :, ry, rx] = val
+        if full[:, :, ry, rx].numel():                                         # (one cell row / column: no such neighbour anywhere)
+            rep = torch.cat([lr_up[:, :, sy, sx], hr[:, :, ry, rx], tabs[t][:, :, sy, sx]], 1)
+            full[:, :, ry, rx] = similarity_mlp(rep, sd, key, final_act=True)  # relu3, cmfsm_sub_8.py:318,342
         logits.append(full)
     allp = torch.cat(logits, 1)
     return F.softmax(allp, dim=1) * allp

@@ -117,6 +117,7 @@ def test_aggregate9(ecm, B, h, w, s, NH):
 
 
 # ------------------------------------------------------------------ a3
+# (a3 / a4 / a8-a11 here are smoke-level comparisons with the fp32 oracle; the sharp check of every path against fp64 is tests/test_hip_context_fp64.py)
 def _mlp(sd):
     return [sd[f"mapping_matrix.similarity1.conv{i}.weight"] for i in range(4)]
 

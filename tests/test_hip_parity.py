@@ -42,6 +42,7 @@ def close_grad(a, b, rel=1e-4):
 
 
 # ------------------------------------------------------------------ a1
+# (a smoke-level comparison with the fp32 oracle; the sharp check of every kernel path against fp64 is tests/test_hip_costvol_fp64.py)
 @pytest.mark.parametrize("B,C,h,w,D", [(1, 4, 5, 12, 6), (2, 8, 4, 24, 20), (1, 32, 8, 12, 48), (2, 32, 16, 60, 48),
                                        (1, 3, 7, 13, 5), (1, 2, 3, 1100, 9), (1, 2, 40, 64, 64)])
 def test_costvol_fwd_bwd(ecm, B, C, h, w, D):
@@ -184,6 +185,7 @@ def test_ecm_module_tuple(ecm, cmfsm_sd):
 
 
 # ------------------------------------------------------------------ a1 + a5 fused: first conv on the concat volume
+# (a smoke-level comparison with the fp32 oracle; the sharp check of every kernel path against fp64 is tests/test_hip_costvol_fp64.py)
 @pytest.mark.parametrize("B,h,w,D", [(1, 8, 16, 6), (2, 6, 36, 12), (1, 5, 9, 2), (1, 4, 12, 20), (1, 8, 64, 48), (1, 3, 5, 3)])
 def test_costvol_conv3d_split(ecm, B, h, w, D):
     """conv3d(concat volume) computed as class-indexed 2-D convolutions (no 4-D volume) == the plain composition."""
@@ -436,6 +438,7 @@ def test_full_model_golden(ecm, cmfsm_sd):
         assert d.max() <= 2e-2 and d.mean() <= 1e-3, (name, d.max(), d.mean())
 
 
+# (a smoke-level comparison on random data; the decision boundaries and the reduction-grid edges are in tests/test_hip_metrics_fp64.py)
 @pytest.mark.parametrize("B,H,W", [(1, 16, 32), (2, 37, 53), (4, 256, 512)])
 def test_stereo_loss3(ecm, B, H, W):
     """Fused loss + metrics kernel == the harness restatement (train.py:162,172-174; train_kitti.py:213-216)."""

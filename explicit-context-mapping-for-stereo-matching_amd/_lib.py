@@ -85,6 +85,8 @@ PROTOTYPES = {
     "ecm_frame_prep_packed": (_I, [_P, _P, _I] + [_P] * 4 + [_I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P]),
     "ecm_eval_epe_scratch_bytes": (_LL, [_LL]),
     "ecm_eval_epe": (_I, [_P, _P, _P, _P, _LL] + [_I] * 7 + [_F, _P]),
+    "ecm_eval_kitti_scratch_bytes": (_LL, [_I, _I, _I]),
+    "ecm_eval_kitti": (_I, [_P, _P, _P, _P, _P, _LL, _I, _I, _I, _F, _P]),
     "ecm_disp_to_u16": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _I, _F, _P]),
     "ecm_gn3d_cluster_mode": (_I, [_I]),
     "ecm_gn3d_poll_ms": (_I, [_I]),

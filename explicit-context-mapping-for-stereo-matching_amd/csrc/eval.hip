@@ -7,8 +7,12 @@
 //     and the mean absolute error of `output3` under each.  The reference gathers o[mask] six times (a host sync each).
 //   * KITTI submission image, test_kitti.py:163-168 -- output3 * 256 -> uint16 (C cast: truncation), un-pad
 //     `pre[0, -h:, -w:]` (the loader pads at the TOP and LEFT, KITTI.py:99-108).  Integer output: bit-exact.
+//   * KITTI validation, eval_kitti.py:84-103 -- output3 on the whole (top/left padded) frame, no crop, d > 0 masks
+//         mask = 0 < d < maxdisp;   mask_non = mask_true = mask and x - d >= 0
+//     the three masked mean errors and the 3-px / 5 % error rate of the batch, and the same eight columns per image.
 // One streaming pass each; EPE sums go through per-workgroup partials and a fixed-order final sum in double.
 #include "common.h"
+#include <cstdint>
 
 namespace {
 
@@ -83,6 +87,148 @@ __global__ __launch_bounds__(256) void disp_to_u16(const float* __restrict__ pre
     out[((size_t)b * Ho + y) * Wo + x] = v;
 }
 
+// ---- KITTI validation (eval_kitti.py:84-103) --------------------------------------------------------------------------------
+// A workgroup walks spans of KSPAN consecutive pixels of ONE sample (blockIdx.y), so the per-sample rows and the batch row come
+// from the same partials: KP words per (sample, workgroup) -- two fp32 error sums (mask, mask_non) and three integer counts
+// (mask, mask_non, good).  mask_true is mask_non in the reference, so its column is a copy and costs no accumulator.
+constexpr int KT = 256, KSPAN = KT * 8, KITTI_MAX_BLOCKS = 256, KP = 5;
+
+__device__ __forceinline__ unsigned wave_sum_u(unsigned v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+__device__ __forceinline__ void kitti_pixel(float p, float d, unsigned x, float maxdisp, float& s, float& s_non, unsigned& n,
+                                            unsigned& n_non, unsigned& n_good) {
+    const float e = fabsf(p - d);
+    const bool m = d < maxdisp && 0.f < d;
+    if (m) { s += e; n += 1u; n_good += (e < 3.f || e < 0.05f * d) ? 1u : 0u; }      // a NaN error is in the sum, never good
+    const float local = (float)x;                                                   // eval_kitti.py:84: the column as a float
+    if (m && local - d >= 0.f) { s_non += e; n_non += 1u; }
+}
+
+// VEC: W % 4 == 0 and both bases 16-byte aligned, so a float4 never straddles a row or a sample.  hw = H * W < 2^31.
+template <bool VEC>
+__global__ __launch_bounds__(KT) void eval_kitti_partial(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                         unsigned* __restrict__ part, unsigned hw, unsigned W, float maxdisp) {
+    __shared__ float sf[2][KT / 64];
+    __shared__ unsigned sc[3][KT / 64];
+    const float* p = pred + (size_t)blockIdx.y * hw;
+    const float* g = gt + (size_t)blockIdx.y * hw;
+    float s = 0.f, s_non = 0.f;
+    unsigned n = 0, n_non = 0, n_good = 0;
+    for (unsigned s0 = blockIdx.x * KSPAN; s0 < hw; s0 += gridDim.x * KSPAN) {
+        if (VEC) {
+#pragma unroll
+            for (int k = 0; k < KSPAN / (4 * KT); ++k) {
+                const unsigned i = s0 + (k * KT + threadIdx.x) * 4;
+                if (i < hw) {
+                    const float4 pv = *reinterpret_cast<const float4*>(p + i), dv = *reinterpret_cast<const float4*>(g + i);
+                    const unsigned x = i % W;
+                    kitti_pixel(pv.x, dv.x, x, maxdisp, s, s_non, n, n_non, n_good);
+                    kitti_pixel(pv.y, dv.y, x + 1, maxdisp, s, s_non, n, n_non, n_good);
+                    kitti_pixel(pv.z, dv.z, x + 2, maxdisp, s, s_non, n, n_non, n_good);
+                    kitti_pixel(pv.w, dv.w, x + 3, maxdisp, s, s_non, n, n_non, n_good);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < KSPAN / KT; ++k) {
+                const unsigned i = s0 + k * KT + threadIdx.x;
+                if (i < hw) kitti_pixel(p[i], g[i], i % W, maxdisp, s, s_non, n, n_non, n_good);
+            }
+        }
+    }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    s = wave_sum(s); s_non = wave_sum(s_non);
+    n = wave_sum_u(n); n_non = wave_sum_u(n_non); n_good = wave_sum_u(n_good);
+    if (lane == 0) { sf[0][wave] = s; sf[1][wave] = s_non; sc[0][wave] = n; sc[1][wave] = n_non; sc[2][wave] = n_good; }
+    __syncthreads();
+    if (threadIdx.x < KP) {
+        unsigned v;
+        if (threadIdx.x < 2) {
+            float f = 0.f;
+            for (int w = 0; w < KT / 64; ++w) f += sf[threadIdx.x][w];
+            v = __float_as_uint(f);
+        } else {
+            v = 0;
+            for (int w = 0; w < KT / 64; ++w) v += sc[threadIdx.x - 2][w];
+        }
+        part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * KP + threadIdx.x] = v;
+    }
+}
+
+// eval_kitti.py:101-103 keeps its two sums as fp32 sums of ones and forms 100 - good / total * 100 in fp32; the same three
+// roundings here (uncontracted), from the exact counts.  0 / 0 -> NaN.
+__device__ __forceinline__ float kitti_err3(unsigned long long good, unsigned long long total) {
+#pragma clang fp contract(off)
+    const float q = (float)good / (float)total;
+    const float q100 = q * 100.f;
+    return 100.f - q100;
+}
+
+// [loss, loss_non, loss_true, loss_3, n_mask, n_non, n_true, n_good]
+__device__ __forceinline__ void kitti_row(float* __restrict__ out, double s, double s_non, unsigned long long n,
+                                          unsigned long long n_non, unsigned long long n_good) {
+    const float m = (float)(s / (double)n), m_non = (float)(s_non / (double)n_non);      // empty mask -> NaN
+    out[0] = m; out[1] = m_non; out[2] = m_non; out[3] = kitti_err3(n_good, n);
+    out[4] = (float)n; out[5] = (float)n_non; out[6] = (float)n_non; out[7] = (float)n_good;
+}
+
+// One workgroup of min(B, 16) waves; a wave takes samples wave, wave + nwaves, ...: lane l adds the partials of workgroups
+// l, l + 64, ... (sums in fp64, counts in 64-bit integers), then a fixed-order butterfly as in loss.hip.  Thread 0 then adds
+// the per-sample totals in sample order: no atomics, the same bits every run.
+__global__ __launch_bounds__(1024) void eval_kitti_final(const unsigned* __restrict__ part, int nbx, int B, float* __restrict__ out8,
+                                                         float* __restrict__ per_sample, unsigned long long* tot) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nwaves = blockDim.x >> 6;
+    for (int b = wave; b < B; b += nwaves) {
+        double s = 0, s_non = 0;
+        unsigned long long c[3] = {0, 0, 0};
+        for (int blk = lane; blk < nbx; blk += 64) {
+            const unsigned* q = part + ((size_t)b * nbx + blk) * KP;
+            s += (double)__uint_as_float(q[0]);
+            s_non += (double)__uint_as_float(q[1]);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) c[k] += q[2 + k];
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            s += __shfl_xor(s, off, 64);
+            s_non += __shfl_xor(s_non, off, 64);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) c[k] += __shfl_xor(c[k], off, 64);
+        }
+        if (lane == 0) {
+            if (per_sample) kitti_row(per_sample + (size_t)b * 8, s, s_non, c[0], c[1], c[2]);
+            unsigned long long* t = tot + (size_t)b * KP;
+            t[0] = (unsigned long long)__double_as_longlong(s);
+            t[1] = (unsigned long long)__double_as_longlong(s_non);
+            t[2] = c[0]; t[3] = c[1]; t[4] = c[2];
+        }
+    }
+    __syncthreads();                       // the totals written above are visible to thread 0 (same workgroup)
+    if (threadIdx.x != 0) return;
+    double s = 0, s_non = 0;
+    unsigned long long c[3] = {0, 0, 0};
+    for (int b = 0; b < B; ++b) {
+        const unsigned long long* t = tot + (size_t)b * KP;
+        s += __longlong_as_double((long long)t[0]);
+        s_non += __longlong_as_double((long long)t[1]);
+        c[0] += t[2]; c[1] += t[3]; c[2] += t[4];
+    }
+    kitti_row(out8, s, s_non, c[0], c[1], c[2]);
+}
+
+inline int kitti_blocks(long long hw) {
+    const long long b = (hw + KSPAN - 1) / KSPAN;
+    return (int)(b > KITTI_MAX_BLOCKS ? KITTI_MAX_BLOCKS : b);
+}
+
+inline long long kitti_part_bytes(int B, long long hw) {      // the partials, rounded up to the 8-byte totals behind them
+    return ((long long)B * kitti_blocks(hw) * KP * (long long)sizeof(unsigned) + 7) / 8 * 8;
+}
+
 }  // namespace
 
 extern "C" long long ecm_eval_epe_scratch_bytes(long long n) {
@@ -115,5 +261,30 @@ extern "C" int ecm_disp_to_u16(const float* pred, unsigned short* out, int B, in
         for (int i = 0; i < nb; ++i) { sz.h[i] = h[b0 + i]; sz.w[i] = w[b0 + i]; }
         hipLaunchKernelGGL(disp_to_u16, dim3((Wo + 255) / 256, Ho, nb), dim3(256), 0, st, pred, out, sz, Hp, Wp, Ho, Wo, scale, b0);
     }
+    return ECM_LAUNCH_RESULT();
+}
+
+extern "C" long long ecm_eval_kitti_scratch_bytes(int B, int H, int W) {
+    if (B < 1 || H < 1 || W < 1) return 0;
+    return kitti_part_bytes(B, (long long)H * W) + (long long)B * KP * (long long)sizeof(unsigned long long);
+}
+
+extern "C" int ecm_eval_kitti(const float* pred, const float* gt, float* out8, float* per_sample, void* scratch,
+                              long long scratch_bytes, int B, int H, int W, float maxdisp, void* stream) {
+    ECM_CHECK_ARG(pred && gt && out8 && scratch && B >= 1 && H >= 1 && W >= 1);
+    ECM_CHECK_ARG(reinterpret_cast<uintptr_t>(scratch) % 8 == 0);
+    const long long hw = (long long)H * W;
+    if (hw > 0x7fffffffLL || B > 65535) return ECM_EUNSUP;        // 32-bit pixel index inside a sample; blockIdx.y is the sample
+    if (scratch_bytes < ecm_eval_kitti_scratch_bytes(B, H, W)) return ECM_ESCRATCH;
+    const int nbx = kitti_blocks(hw);
+    unsigned* part = static_cast<unsigned*>(scratch);
+    unsigned long long* tot = reinterpret_cast<unsigned long long*>(static_cast<char*>(scratch) + kitti_part_bytes(B, hw));
+    hipStream_t st = ecm_stream(stream);
+    const bool vec = W % 4 == 0 && reinterpret_cast<uintptr_t>(pred) % 16 == 0 && reinterpret_cast<uintptr_t>(gt) % 16 == 0;
+    if (vec)
+        hipLaunchKernelGGL(eval_kitti_partial<true>, dim3(nbx, B), dim3(KT), 0, st, pred, gt, part, (unsigned)hw, (unsigned)W, maxdisp);
+    else
+        hipLaunchKernelGGL(eval_kitti_partial<false>, dim3(nbx, B), dim3(KT), 0, st, pred, gt, part, (unsigned)hw, (unsigned)W, maxdisp);
+    hipLaunchKernelGGL(eval_kitti_final, dim3(1), dim3(64 * (B < 16 ? B : 16)), 0, st, part, nbx, B, out8, per_sample, tot);
     return ECM_LAUNCH_RESULT();
 }

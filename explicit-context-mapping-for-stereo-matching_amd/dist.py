@@ -234,6 +234,91 @@ def masked_smooth_l1_x3_with_count(preds, gt, maxdisp: int = 192):
     return loss, metrics[1]
 
 
+KITTI_COLUMNS = ("loss", "loss_non", "loss_true", "loss_3", "n_mask", "n_non", "n_true", "n_good")
+_LOG_ROWS = 64
+
+
+def kitti_dataset_metrics(table: torch.Tensor):
+    """Dataset-level KITTI metrics from a per-sample table [N,8] (ops.eval_kitti's columns): every masked pixel of every image
+    weighs the same.  Per-image error sums are recovered as mean * count in double (counts are exact below 2^24 pixels per
+    image); an image with an empty mask contributes nothing.  -> dict of floats over KITTI_COLUMNS."""
+    t = table.detach().cpu().double()
+    n, n_non, n_true, n_good = (float(t[:, k].sum()) for k in (4, 5, 6, 7))
+
+    def mean(col, cnt, total):
+        keep = t[:, cnt] > 0
+        return float((t[keep, col] * t[keep, cnt]).sum()) / total if total > 0 else float("nan")
+
+    return {"loss": mean(0, 4, n), "loss_non": mean(1, 5, n_non), "loss_true": mean(2, 6, n_true),
+            "loss_3": 100.0 - n_good / n * 100.0 if n > 0 else float("nan"),
+            "n_mask": n, "n_non": n_non, "n_true": n_true, "n_good": n_good}
+
+
+def _all_gather_rows(table: torch.Tensor):
+    """Concatenate every rank's [n_r, 8] table in rank order (the ranks may hold different numbers of samples)."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
+    world = dist.get_world_size()
+    n = torch.tensor([table.shape[0]], dtype=torch.int64, device=dev)
+    ns = [torch.zeros_like(n) for _ in range(world)]
+    dist.all_gather(ns, n)
+    ns = [int(v) for v in ns]
+    pad = torch.zeros(max(max(ns), 1), table.shape[1], dtype=table.dtype, device=dev)
+    pad[:table.shape[0]] = table
+    rows = [torch.empty_like(pad) for _ in range(world)]
+    dist.all_gather(rows, pad)
+    return torch.cat([r[:k] for r, k in zip(rows, ns)]).cpu()
+
+
+def evaluate_kitti(model: torch.nn.Module, batches, maxdisp: int = 192):
+    """The validation loop of eval_kitti.py:75-115 with its metrics on the device.  `batches` yields (left, right, disparity, ...)
+    as the reference's loader does (frames already padded to 384 x 1248, e.g. by ops.frame_prep_kitti_eval); the model runs under
+    model.eval() and torch.no_grad(), and one ops.eval_kitti per batch writes output3's metrics into the next row of a device
+    log -- no `o[mask]` gathers, no `.item()` per batch.  The host synchronises once, when the log is read at the end.
+    Predictions are fp32 under every ops.inference_dtype, so this runs unchanged inside ops.inference_dtype(torch.bfloat16).
+
+    -> dict:
+      error_rec, error_rec_non, error_rec_3   the reference's per-batch lists (Python floats, as its `.item()` gives them),
+      error_rec_true                          loss_true per batch (the reference computes it and drops it),
+      error, error_non, error_3, error_true   np.mean of those lists, as eval_kitti.py:112-114 forms them,
+      log                                     float32 [n_batches, 8], columns KITTI_COLUMNS,
+      per_sample                              float32 [n_samples, 8], the same columns for each image, in order.
+    The reference's figures are means of per-batch means: they depend on the batching (a smaller last batch weighs as much as
+    a full one, and a batch with few valid pixels as much as a dense one).
+
+    An addition to the reference: with an initialised process group, `batches` is this rank's shard; the per-sample tables of
+    all ranks are all-gathered (rank order) into `per_sample_all`, and `dataset` holds kitti_dataset_metrics of it -- every
+    valid pixel of the validation set weighted equally, independent of batching and sharding, identical on every rank.  The
+    lists and their means above stay this rank's own.  (Without a process group `dataset` is computed from `per_sample`.)"""
+    import numpy as np
+    from . import ops
+    model.eval()
+    logs, tables, nb = [], [], 0
+    with torch.no_grad():
+        for left, right, disparity, *_ in batches:
+            left, right, disparity = (t if t.is_cuda else t.cuda(non_blocking=True) for t in (left, right, disparity))
+            if nb % _LOG_ROWS == 0:
+                logs.append(torch.full((_LOG_ROWS, 8), float("nan"), device=disparity.device))
+            outputs = model(left, right)
+            output3 = outputs[2] if isinstance(outputs, (tuple, list)) else outputs
+            _, table = ops.eval_kitti(output3, disparity, maxdisp, out=logs[-1][nb % _LOG_ROWS], per_sample=True)
+            tables.append(table)
+            nb += 1
+    if nb == 0:
+        raise RuntimeError("evaluate_kitti: no batches")
+    log = torch.cat(logs)[:nb].cpu()                      # the one host synchronisation
+    per_sample = torch.cat(tables).cpu()
+    res = {"log": log, "per_sample": per_sample}
+    for key, col in (("", 0), ("_non", 1), ("_true", 2), ("_3", 3)):
+        res["error_rec" + key] = log[:, col].tolist()
+        res["error" + key] = np.mean(res["error_rec" + key])
+    if dist.is_available() and dist.is_initialized():
+        res["per_sample_all"] = _all_gather_rows(per_sample)
+        res["dataset"] = kitti_dataset_metrics(res["per_sample_all"])
+    else:
+        res["dataset"] = kitti_dataset_metrics(per_sample)
+    return res
+
+
 class GraphedForward:
     """Inference through one captured HIP graph: the eval forward of a model is a fixed sequence of ~400 kernel launches
     (encoder + hot path, all on this library's kernels), which at batch 1 is partly launch-bound; capturing it once and

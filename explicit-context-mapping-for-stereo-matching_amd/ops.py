@@ -1420,9 +1420,22 @@ def _frame_prep(frames, crop_y0, crop_x0, th, tw, split, tail, mean, std, want_i
     return (left, right, disp, image) if want_image else (left, right, disp)
 
 
-def eval_epe(pred, gt, crop_h=540, crop_w=960, maxdisp=192):
+def _out_row(out, n, device):
+    """The `out=` operand of the evaluation ops: None -> a fresh float32[n] on `device`; else a contiguous fp32 view of n floats
+    there (e.g. a row of a preallocated [n_batches, n] log) that the kernel writes in place."""
+    if out is None:
+        return torch.empty(n, device=device, dtype=torch.float32)
+    _chk(out)
+    _need(out.numel() == n and out.is_contiguous() and out.device == device,
+          lambda: f"out: want a contiguous float32 view of {n} elements on {device}, got {tuple(out.shape)} "
+                  f"(strides {out.stride()}) on {out.device}")
+    return out
+
+
+def eval_epe(pred, gt, crop_h=540, crop_w=960, maxdisp=192, out=None):
     """SceneFlow evaluation of test.py:69-94 on the device: pred [B,1,Hp,Wp] or [B,Hp,Wp] (output3), gt [B,Hg,Wg];
-    -> float32[6] = (epe, epe_non, epe_true, n, n_non, n_true), both tensors cropped to [:crop_h, :crop_w]."""
+    -> float32[6] = (epe, epe_non, epe_true, n, n_non, n_true), both tensors cropped to [:crop_h, :crop_w].
+    out: a contiguous float32 device view of 6 elements to write instead (a row of a log); it is returned."""
     _chk(pred, gt)
     if pred.dim() == 4:
         pred = pred.squeeze(1)
@@ -1431,11 +1444,33 @@ def eval_epe(pred, gt, crop_h=540, crop_w=960, maxdisp=192):
     Bg, Hg, Wg = gt.shape
     if B != Bg:
         raise RuntimeError(f"prediction / ground-truth batch sizes differ: {B} vs {Bg}")
-    out = torch.empty(6, device=pred.device, dtype=torch.float32)
+    out = _out_row(out, 6, pred.device)
     n = B * int(crop_h) * int(crop_w)
     _call_scratch(pred.device, "ecm_eval_epe_scratch_bytes", (C.c_longlong(n),), "ecm_eval_epe", _p(pred), _p(gt), _p(out),
                   _SCRATCH, B, Hp, Wp, Hg, Wg, int(crop_h), int(crop_w), C.c_float(maxdisp), _stream())
     return out
+
+
+def eval_kitti(pred, gt, maxdisp=192, out=None, per_sample=False):
+    """KITTI validation of eval_kitti.py:84-103 on the device, whole frame, no crop: pred [B,1,H,W] or [B,H,W] (output3),
+    gt [B,H,W] -> float32[8] = (loss, loss_non, loss_true, loss_3, n_mask, n_non, n_true, n_good) with mask = 0 < gt < maxdisp,
+    mask_non = mask_true = mask and x - gt >= 0 (identical in the reference), loss_3 the 3-px / 5 % error rate in percent.
+    An empty mask gives NaN.  per_sample=True: -> (row, table [B,8]) with the same columns for each image alone.
+    out: a contiguous float32 device view of 8 elements to write instead (a row of a [n_batches, 8] log); it is returned.
+    Nothing here synchronises with the host."""
+    _chk(pred, gt)
+    if pred.dim() == 4:
+        _need(pred.shape[1] == 1, lambda: f"eval_kitti: pred {tuple(pred.shape)}: want [B,1,H,W] or [B,H,W]")
+        pred = pred.squeeze(1)
+    _need(pred.dim() == 3 and pred.shape == gt.shape and pred.numel() > 0,
+          lambda: f"eval_kitti: pred {tuple(pred.shape)} / gt {tuple(gt.shape)}: want the same non-empty [B,H,W]")
+    pred, gt = pred.contiguous(), gt.contiguous()        # any 4-byte alignment: the kernel picks its load width
+    B, H, W = pred.shape
+    out = _out_row(out, 8, pred.device)
+    table = torch.empty(B, 8, device=pred.device, dtype=torch.float32) if per_sample else None
+    _call_scratch(pred.device, "ecm_eval_kitti_scratch_bytes", (B, H, W), "ecm_eval_kitti", _p(pred), _p(gt), _p(out), _p(table),
+                  _SCRATCH, B, H, W, C.c_float(maxdisp), _stream())
+    return (out, table) if per_sample else out
 
 
 def disparity_to_uint16(pred, h, w, scale=256.0):

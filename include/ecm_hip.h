@@ -367,6 +367,22 @@ long long ecm_eval_epe_scratch_bytes(long long n);
 int ecm_eval_epe(const float* pred, const float* gt, float* out6, void* scratch, long long scratch_bytes, int B,
                  int Hp, int Wp, int Hg, int Wg, int crop_h, int crop_w, float maxdisp, void* stream);
 
+/* KITTI validation (eval_kitti.py:84-103): pred [B,H,W] (= output3 squeezed) against gt [B,H,W] on the whole frame, no crop;
+ * x = column index as a float, every comparison and |pred - gt| in fp32:
+ *   mask = 0 < gt < maxdisp;   mask_non = mask_true = mask and x - gt >= 0   (the reference writes these two identically:
+ *   both columns are kept so that a caller's log has the reference's names, and they always hold the same values);
+ *   good = |pred - gt| < 3 or |pred - gt| < 0.05f * gt, under mask.
+ * out8 (device) = [loss, loss_non, loss_true, loss_3, n_mask, n_non, n_true, n_good]: the three masked means of |pred - gt|
+ * (fp32 partial sums, final sum in double), loss_3 = 100 - n_good / n_mask * 100 in fp32 as the reference forms it, and the
+ * counts, accumulated as integers and written as floats.  An empty mask gives NaN for its mean and for loss_3, like the
+ * reference's mean of an empty selection and its 0 / 0.  A NaN prediction under the mask makes the means NaN and is not good.
+ * per_sample (device, [B,8], may be NULL) = the same eight columns of each image alone -- an addition: the reference has
+ * only the batch row.  Uses 16-byte loads when W % 4 == 0 and pred, gt are 16-byte aligned; any 4-byte alignment works.
+ * No atomics: bit-reproducible.  B, H, W >= 1, else ECM_EINVAL; H * W >= 2^31 or B > 65535: ECM_EUNSUP. */
+long long ecm_eval_kitti_scratch_bytes(int B, int H, int W);
+int ecm_eval_kitti(const float* pred, const float* gt, float* out8, float* per_sample, void* scratch, long long scratch_bytes,
+                   int B, int H, int W, float maxdisp, void* stream);
+
 /* KITTI submission image (test_kitti.py:163-168): out[b,y,x] = (uint16)(pred[b, Hp-h[b]+y, Wp-w[b]+x] * scale) for
  * y < h[b], x < w[b] (the loader padded at the top and left), 0 elsewhere; scale = 256.  The cast is numpy's on the
  * reference's host: truncation toward zero, low 16 bits of the 32-bit integer, 0 for NaN / out-of-int32-range values.

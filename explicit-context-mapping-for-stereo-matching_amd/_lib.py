@@ -116,6 +116,10 @@ PROTOTYPES = {
     "ecm_deconv2d_bf16_pack_weight": (_I, [_P, _P, _I, _I, _P]),             # cmf.py:236-239
     "ecm_deconv2d_k3s2_bias_bf16_fwd": (_I, [_P, _P, _P, _P] + [_I] * 5 + [_P]),   # cmf.py:236-239
     "ecm_conv2d_c1_bf16_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),    # cmf.py:259-264
+    "ecm_conv3d_split_packed_elems": (_LL, [_I, _I]),                        # cmfsm.py:244-268
+    "ecm_conv3d_split_pack_weight": (_I, [_P, _P, _I, _I, _I, _P]),          # cmfsm.py:244-268
+    "ecm_conv3d_k3s2_split_fwd": (_I, [_P, _P, _P] + [_I] * 6 + [_P]),       # cmfsm.py:244-258
+    "ecm_deconv3d_k3s2_split_fwd": (_I, [_P, _P, _P] + [_I] * 9 + [_P]),     # cmfsm.py:262-268
 }
 
 _lib = None

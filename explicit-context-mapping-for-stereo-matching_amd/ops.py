@@ -792,10 +792,13 @@ class Conv3dK3(torch.autograd.Function):
             y = _c1_fwd(x, w)
         elif stride == 1 and _wino_ok(x):
             y = _wino_run(x, _wino_pack_fwd(ctx, x, w, 3, grad_mode), w.shape[0], 3)
+        elif stride == 2 and _split_use("conv_fwd", x, w.shape[1], w.shape[0]):
+            y = _split_conv_fwd(x, _pack_split(w, False), w.shape[0])
         else:
             y = _conv_fwd(x, _pack_conv(w), w.shape[0], stride)
         ctx.save_for_backward(x, w)
         ctx.stride = stride
+        ctx.split_dgrad = stride == 2 and not ctx.c1 and _split_use("conv_dgrad", x, w.shape[0], w.shape[1])
         return _fork_out(y, x, fork)
 
     @staticmethod
@@ -818,6 +821,8 @@ class Conv3dK3(torch.autograd.Function):
                 return _wino_run(gy, _wino_pack_b(ctx, w, 3), Ci, 3, addend=gskip)
             elif ctx.stride == 1:
                 g = _conv_fwd(gy, _pack_conv(w, True), Ci, 1)
+            elif ctx.split_dgrad:
+                g = _split_deconv_fwd(gy, _pack_split(w, True), Ci, x.shape[2:])
             else:
                 g = _deconv_fwd(gy, _pack_deconv(w), Ci, x.shape[2:])
             return _fork_grad(g, gskip)
@@ -1087,8 +1092,12 @@ class Deconv3dK3S2(torch.autograd.Function):
         ctx.side_ok = w.is_contiguous()
         x, w = _c(x), _c(w)
         B, Ci, D, H, W = x.shape
-        y = _deconv_fwd(x, _pack_deconv(w), w.shape[1], (2 * D, 2 * H, 2 * W))
+        if _split_use("deconv_fwd", x, w.shape[0], w.shape[1]):
+            y = _split_deconv_fwd(x, _pack_split(w, True), w.shape[1], (2 * D, 2 * H, 2 * W))
+        else:
+            y = _deconv_fwd(x, _pack_deconv(w), w.shape[1], (2 * D, 2 * H, 2 * W))
         ctx.save_for_backward(x, w)
+        ctx.split_dgrad = _split_use("deconv_dgrad", x, w.shape[1], w.shape[0])
         return y
 
     @staticmethod
@@ -1098,8 +1107,12 @@ class Deconv3dK3S2(torch.autograd.Function):
         Ci, Co = w.shape[0], w.shape[1]
         # gw[ci,co,k] = sum x[ci,i] gy[co,2i+k-1]: the conv-wgrad with x:=gy (big), gy:=x, "Co":=Ci, "Ci":=Co
         # gx[ci,i] = sum_{co,k} gy[co,2i+k-1] w[ci,co,k]: a stride-2 conv with w read as Conv3d [Cout=Ci,Cin=Co]
+        def dfn():
+            if ctx.split_dgrad:
+                return _split_conv_fwd(gy, _pack_split(w, False), Ci)
+            return _conv_fwd(gy, _pack_conv(w), Ci, 2)
         gx, gw = _launch_pair((lambda: _wgrad(gy, x, Ci, Co, 2, w if ctx.side_ok else None)) if ctx.needs_input_grad[1] else None,
-                              (lambda: _conv_fwd(gy, _pack_conv(w), Ci, 2)) if ctx.needs_input_grad[0] else None)
+                              dfn if ctx.needs_input_grad[0] else None)
         return gx, gw
 
 
@@ -1667,6 +1680,96 @@ def _deconv3d_bf16(x, w):
     Co = w.shape[1]
     y = torch.empty(B, Co, 2 * D, 2 * H, 2 * W, device=x.device, dtype=torch.bfloat16)
     _lib.call("ecm_deconv3d_k3s2_bf16_fwd", _p(x), _p(_pack_bf16(w, True)), _p(y), B, Ci, Co, D, H, W, _stream())
+    return y
+
+
+# ---- opt-in split-bf16 products for the stride-2 3-D convolutions ------------------------------------------------------------
+# Inside `with split_products("bf16x3"):` the stride-2 family (the hourglass's conv1/conv3 and its two transposed
+# convolutions, cmfsm.py:244-281) runs csrc/split_bf16.hip: every fp32 operand is split into three bf16 terms and the six
+# leading cross products accumulate in fp32 on the bf16 matrix cores.  Tensors stay fp32, the result is fp32-equivalent (the
+# fp64 yardstick of the fp32 kernels, tests/test_hip_split_bf16_fp64.py) and the autograd Functions are the usual ones, so the
+# block works with grad enabled -- unlike the bf16 regions above, which change the numerics and are inference only.
+# The setting is process-wide like WINOGRAD, nests and restores.  It is read when a layer's FORWARD runs and rides on the
+# autograd node, so a backward pass started after the block has closed still takes the data-gradient kernels the forward chose.
+# What does not fit the split kernels keeps the fp32 kernels without an error: stride 1, channel counts outside {32, 64}, volumes
+# whose byte offsets pass 2^31, and a kind that is not selected.  That fallback is not a quiet change of numerics: both paths
+# meet the same bound.  Weight gradients always stay on the fp32 kernels; bf16 volumes still take the bf16 path.
+# Packed split weights are cached under frozen_weights() like every other layout (keys "split_conv" / "split_deconv").
+SPLIT_MODES = ("fp32", "bf16x3")
+# the kinds `split_products("bf16x3")` turns on when none are named; a kind measured slower than its fp32 kernel at the bench
+# geometry is left out (tools/split_bf16_time.py, profiles/r10_split_bf16_time.json)
+SPLIT_ALL_KINDS = frozenset({"conv_fwd", "conv_dgrad", "deconv_fwd", "deconv_dgrad"})
+# As measured in round 10 NO kind is faster than its fp32 kernel over the two layers it serves (0.68-0.81x on the 32 <-> 64 level,
+# 0.74-1.20x on the 64 -> 64 level), so the default set is empty and `split_products("bf16x3")` changes nothing until kinds are named.
+SPLIT_DEFAULT_KINDS = frozenset()
+_SPLIT_MODE = "bf16x3" if _os.environ.get("ECM_SPLIT_BF16", "0") == "1" else "fp32"
+_SPLIT_KINDS = SPLIT_DEFAULT_KINDS
+
+
+@_contextlib.contextmanager
+def split_products(mode, kinds=None):
+    """"fp32" (the default; a no-op) or "bf16x3": inside the block the stride-2 3-D convolutions of fp32 volumes run the
+    split-bf16 kernels, forward and data gradient, with or without grad.  kinds: which of SPLIT_ALL_KINDS to turn on
+    (default SPLIT_DEFAULT_KINDS, which holds the kinds measured faster than fp32 -- none so far).  Nests and restores the previous setting on exit; ECM_SPLIT_BF16=1 makes "bf16x3" the
+    process default."""
+    global _SPLIT_MODE, _SPLIT_KINDS
+    if mode not in SPLIT_MODES:
+        raise ValueError(f"split_products: {mode!r} is not supported (one of {SPLIT_MODES})")
+    kinds = SPLIT_DEFAULT_KINDS if kinds is None else frozenset(kinds)
+    if not kinds <= SPLIT_ALL_KINDS:
+        raise ValueError(f"split_products: unknown kinds {sorted(kinds - SPLIT_ALL_KINDS)} (of {sorted(SPLIT_ALL_KINDS)})")
+    prev = (_SPLIT_MODE, _SPLIT_KINDS)
+    _SPLIT_MODE, _SPLIT_KINDS = mode, kinds
+    try:
+        yield
+    finally:
+        _SPLIT_MODE, _SPLIT_KINDS = prev
+
+
+def split_products_on():
+    """True inside a split_products("bf16x3") block (or under ECM_SPLIT_BF16=1 outside any block)."""
+    return _SPLIT_MODE == "bf16x3"
+
+
+def split_supported(Ci, Co, big_voxels):
+    """Do the split kernels take this layer?  Ci, Co: the kernel's input and output channels; big_voxels: D*H*W of the larger
+    of its two volumes (byte offsets inside one sample must stay below 2^31)."""
+    return Ci in (32, 64) and Co in (32, 64) and max(Ci, Co) * int(big_voxels) * 4 < 0x7fffffff
+
+
+def _split_use(kind, x, Ci, Co):
+    """Does this launch take the split kernel?  x: the layer's forward input (the small grid of a transposed convolution)."""
+    if _SPLIT_MODE != "bf16x3" or kind not in _SPLIT_KINDS or x.dtype != torch.float32:
+        return False
+    vox = x.shape[2] * x.shape[3] * x.shape[4]
+    return split_supported(Ci, Co, vox * 8 if kind.startswith("deconv") else vox)
+
+
+def _pack_split(w, transposed):
+    """Split-bf16 weight image [Ci/8][3][28][Co][8] of a 3x3x3 weight read as a convolution (w [Co,Ci,27]) or, transposed, as a
+    transposed convolution (w [Ci,Co,27]) -- the operands _pack_conv(w) and _pack_deconv(w) build for the fp32 kernels."""
+    Ci, Co = (w.shape[0], w.shape[1]) if transposed else (w.shape[1], w.shape[0])
+
+    def build():
+        wc = _c(w.detach())
+        packed = torch.empty(_lib.query("ecm_conv3d_split_packed_elems", Ci, Co), device=w.device, dtype=torch.bfloat16)
+        _lib.call("ecm_conv3d_split_pack_weight", _p(wc), _p(packed), Ci, Co, int(transposed), _stream())
+        return packed
+    return _cached_pack(w, "split_deconv" if transposed else "split_conv", build)
+
+
+def _split_conv_fwd(x, packed, Co):
+    B, Ci, D, H, W = x.shape
+    y = torch.empty(B, Co, (D - 1) // 2 + 1, (H - 1) // 2 + 1, (W - 1) // 2 + 1, device=x.device, dtype=x.dtype)
+    _lib.call("ecm_conv3d_k3s2_split_fwd", _p(x), _p(packed), _p(y), B, Ci, Co, D, H, W, _stream())
+    return y
+
+
+def _split_deconv_fwd(x, packed, Co, out_dhw):
+    B, Ci, D, H, W = x.shape
+    Do, Ho, Wo = out_dhw
+    y = torch.empty(B, Co, Do, Ho, Wo, device=x.device, dtype=x.dtype)
+    _lib.call("ecm_deconv3d_k3s2_split_fwd", _p(x), _p(packed), _p(y), B, Ci, Co, D, H, W, Do, Ho, Wo, _stream())
     return y
 
 

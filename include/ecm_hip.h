@@ -454,6 +454,26 @@ int ecm_deconv2d_k3s2_bias_bf16_fwd(const unsigned short* x, const unsigned shor
 int ecm_conv2d_c1_bf16_fwd(const unsigned short* x, const float* w, const float* bias, float* y, int B, int Ci, int H, int W,
                            void* stream);
 
+/* ---- opt-in split-bf16 products for the stride-2 3-D convolutions (ops.split_products; split_bf16.hip) ------------------
+ * Forward and data gradient of the hourglass's stride-2 family: Conv3d k3 p1 s2 (conv1 / conv3, cmfsm.py:244-258) and
+ * ConvTranspose3d k3 s2 p1 op1 (conv5 / conv6, cmfsm.py:262-268); each is the other's adjoint, so the two entries serve all
+ * four.  Volumes and results are contiguous fp32 NCDHW.  Every fp32 operand is split by truncation into three bf16 terms
+ * (x = x1 + x2 + x3, exact for |x| >= 2^-110; a non-finite x is (x, 0, 0)) and the six leading cross products accumulate in
+ * fp32 on the bf16 matrix cores: fp32-equivalent results.  No atomics: bit-reproducible.
+ * Weight image: [Ci/8][3 terms][28 tap slots][Co][8] bf16 (unsigned short = the bit pattern), split once by the pack entry --
+ * transposed = 0: Conv3d w [Co,Ci,3,3,3] read as a convolution; transposed = 1: ConvTranspose3d w [Ci,Co,3,3,3] read as a
+ * transposed convolution (taps grouped by output phase).  Ci % 8 == 0 (0 elements otherwise).
+ * Ci, Co in {32, 64} and byte offsets inside one sample below 2^31; anything else returns ECM_EUNSUP. */
+long long ecm_conv3d_split_packed_elems(int Ci, int Co);
+int ecm_conv3d_split_pack_weight(const float* w, unsigned short* packed, int Ci, int Co, int transposed, void* stream);
+/* cmfsm.py:244-258: y [B,Co,Do,Ho,Wo], Do = (D-1)/2+1.  Also the data gradient of ecm_deconv3d_k3s2_split_fwd. */
+int ecm_conv3d_k3s2_split_fwd(const float* x, const unsigned short* wpacked, float* y,
+                              int B, int Ci, int Co, int D, int H, int W, void* stream);
+/* cmfsm.py:262-268: y [B,Co,Do,Ho,Wo] with each output extent 2n (output_padding 1) or 2n-1 (the data gradient of
+ * ecm_conv3d_k3s2_split_fwd on an odd extent). */
+int ecm_deconv3d_k3s2_split_fwd(const float* x, const unsigned short* wpacked, float* y,
+                                int B, int Ci, int Co, int D, int H, int W, int Do, int Ho, int Wo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

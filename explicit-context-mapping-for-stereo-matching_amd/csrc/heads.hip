@@ -10,9 +10,11 @@ __constant__ int kDy[9] = {0, 0, 0, -1, 1, -1, -1, 1, 1};
 __constant__ int kDx[9] = {0, -1, 1, 0, 0, -1, 1, -1, 1};
 
 // ---- soft-argmin, heads fused: logits_k = c_0 + ... + c_k ----------------------------------
-template <int NH>
+// LSE: also lse[k,b,p] = m + ln s, the normaliser of head k's column, for aggregate9_stats_fwd
+template <int NH, bool LSE = false>
 __global__ __launch_bounds__(256) void softargmin_fwd(const float* __restrict__ c0, long long hs,
-                                                      float* __restrict__ disp, int B, int D, int hw) {
+                                                      float* __restrict__ disp, float* __restrict__ lse, int B, int D,
+                                                      int hw) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;     // b*hw + p
     if (i >= (long long)B * hw) return;
     const int b = (int)(i / hw), p = (int)(i - (long long)b * hw);
@@ -42,7 +44,10 @@ __global__ __launch_bounds__(256) void softargmin_fwd(const float* __restrict__ 
         }
     }
 #pragma unroll
-    for (int k = 0; k < NH; ++k) disp[(size_t)k * B * hw + i] = t[k] / s[k];
+    for (int k = 0; k < NH; ++k) {
+        disp[(size_t)k * B * hw + i] = t[k] / s[k];
+        if constexpr (LSE) lse[(size_t)k * B * hw + i] = m[k] + logf(s[k]);
+    }
 }
 
 // d disp_k / d logit_k[d] = p_k[d] (d - disp_k);  g c_j = sum_{k>=j} g logit_k
@@ -210,13 +215,32 @@ __global__ __launch_bounds__(256) void aggregate9_bwd_d(const float* __restrict_
         default: return ECM_EUNSUP;                                                    \
     }
 
+template <int NH>
+static constexpr auto softargmin_lse_fwd = softargmin_fwd<NH, true>;
+
+// the plain head (lse == nullptr) and the one that also stores the normaliser: one grid
+static int launch_softargmin_fwd(const float* c0, long long head_stride, float* disp, float* lse, int nheads, int B, int D,
+                                 int hw, void* stream) {
+    const long long n = (long long)B * hw;
+    dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (lse) {
+        DISPATCH_NH(softargmin_lse_fwd, grid, block, 0, ecm_stream(stream), c0, head_stride, disp, lse, B, D, hw)
+    } else {
+        DISPATCH_NH(softargmin_fwd, grid, block, 0, ecm_stream(stream), c0, head_stride, disp, lse, B, D, hw)
+    }
+    return ECM_LAUNCH_RESULT();
+}
+
 extern "C" int ecm_softargmin_heads_fwd(const float* c0, long long head_stride, float* disp, int nheads, int B, int D,
                                         int hw, void* stream) {
     ECM_CHECK_ARG(c0 && disp && B > 0 && D > 0 && hw > 0);
-    const long long n = (long long)B * hw;
-    dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    DISPATCH_NH(softargmin_fwd, grid, block, 0, ecm_stream(stream), c0, head_stride, disp, B, D, hw)
-    return ECM_LAUNCH_RESULT();
+    return launch_softargmin_fwd(c0, head_stride, disp, nullptr, nheads, B, D, hw, stream);
+}
+
+extern "C" int ecm_softargmin_heads_lse_fwd(const float* c0, long long head_stride, float* disp, float* lse, int nheads,
+                                            int B, int D, int hw, void* stream) {
+    ECM_CHECK_ARG(c0 && disp && lse && B > 0 && D > 0 && hw > 0);
+    return launch_softargmin_fwd(c0, head_stride, disp, lse, nheads, B, D, hw, stream);
 }
 
 extern "C" int ecm_softargmin_heads_bwd(const float* c0, long long head_stride, const float* gdisp, float* gc0,

@@ -23,6 +23,25 @@ struct Online {            // online softmax-weighted mean of D
     __device__ __forceinline__ float result() const { return t / s; }
 };
 
+// Statistics of the distribution a finished Online describes, accumulated by a SECOND walk over the
+// same logits: the spread about the finished mean (never sum p D^2 - mean^2), and u = sum e (v - m) for the entropy
+// ln s - u / s.  e = exp(v - m) <= 1 with the maximum contributing exactly 1, so s >= 1, u <= 0 and the peak is 1 / s.
+struct Centred {
+    float m, mu, var, u;
+    __device__ __forceinline__ void init(const Online& o) { m = o.m; mu = o.result(); var = 0.f; u = 0.f; }
+    __device__ __forceinline__ void push(float v, float d) {
+        const float x = v - m, e = expf(x), c = d - mu;
+        var = fmaf(e * c, c, var);
+        u = fmaf(e, x, u);
+    }
+    // stats [NH,3,B,H,W]: o points at (k, 0, b, pixel), plane = B*H*W
+    __device__ __forceinline__ void store(const Online& on, float* __restrict__ o, size_t plane) const {
+        o[0] = sqrtf(var / on.s);
+        o[plane] = 1.f / on.s;
+        o[2 * plane] = logf(on.s) - u / on.s;
+    }
+};
+
 __device__ __forceinline__ void wave_fence() {
     // LDS operations of ONE wave execute in issue order; this keeps the compiler from moving them across the point
     // (a later lane-shifted read must see an earlier store of the neighbouring lane)
@@ -57,10 +76,14 @@ __device__ __forceinline__ void fuse5(const float* __restrict__ c, long long hs,
     }
 }
 
-template <int NH>
+// STATS: a second pass over the same logits for stats [NH,3,B,H,W] (std, peak, entropy).  The loop body below is the only
+// place the logits are formed, so the two instantiations cannot drift apart; without STATS the pass loop runs once and the
+// kernel is the one it was.
+template <int NH, bool STATS = false>
 __global__ __launch_bounds__(256) void volume_mapping_fwd(const float* __restrict__ c, long long hs,
                                                           const float* __restrict__ m5p, const float* __restrict__ mt3p,
-                                                          float* __restrict__ out, int B, int Dl, int h, int w, int s) {
+                                                          float* __restrict__ out, float* __restrict__ stats, int B, int Dl,
+                                                          int h, int w, int s) {
     const int H = h * s, W = w * s;
     const long long HW = (long long)H * W;
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -76,29 +99,43 @@ __global__ __launch_bounds__(256) void volume_mapping_fwd(const float* __restric
     const size_t bbase = (size_t)b * Dl * h * w;
     float Fp[NH], Fc[NH], Fn[NH];
     Online acc[NH];
+    Centred cen[NH];
 #pragma unroll
-    for (int k = 0; k < NH; ++k) { Fp[k] = 0.f; acc[k].init(); }
-    fuse5<NH>(c, hs, bbase, 0, h, w, cy, cx, m5, Fc);
-    for (int j = 0; j < Dl; ++j) {
-        const bool has_next = j + 1 < Dl;
-        if (has_next) fuse5<NH>(c, hs, bbase, j + 1, h, w, cy, cx, m5, Fn);
-        for (int q = 0; q < s; ++q) {
-            const int D = j * s + q;
-            float t0 = 1.f, tr = 1.f, tl = 1.f;                        // ones_like initialisation (cmfsm_sub_16.py:782-784)
-            if (X >= D) { t0 = mt[X - D]; tr = mt[HW + X - D]; tl = mt[2 * HW + X - D]; }
+    for (int k = 0; k < NH; ++k) acc[k].init();
+    for (int pass = 0; pass < (STATS ? 2 : 1); ++pass) {
 #pragma unroll
-            for (int k = 0; k < NH; ++k) {
-                float v = Fc[k] * t0;
-                if (has_next) v = fmaf(Fn[k], tl, v);                  // [:, :-s] += fused[:, s:] * T_l[:, :-s]   (:797)
-                if (j > 0) v = fmaf(Fp[k], tr, v);                     // [:, s:]  += fused[:, :-s] * T_r[:, s:]   (:798)
-                acc[k].push(v, (float)D);
+        for (int k = 0; k < NH; ++k) Fp[k] = 0.f;
+        fuse5<NH>(c, hs, bbase, 0, h, w, cy, cx, m5, Fc);
+        for (int j = 0; j < Dl; ++j) {
+            const bool has_next = j + 1 < Dl;
+            if (has_next) fuse5<NH>(c, hs, bbase, j + 1, h, w, cy, cx, m5, Fn);
+            for (int q = 0; q < s; ++q) {
+                const int D = j * s + q;
+                float t0 = 1.f, tr = 1.f, tl = 1.f;                    // ones_like initialisation (cmfsm_sub_16.py:782-784)
+                if (X >= D) { t0 = mt[X - D]; tr = mt[HW + X - D]; tl = mt[2 * HW + X - D]; }
+#pragma unroll
+                for (int k = 0; k < NH; ++k) {
+                    float v = Fc[k] * t0;
+                    if (has_next) v = fmaf(Fn[k], tl, v);              // [:, :-s] += fused[:, s:] * T_l[:, :-s]   (:797)
+                    if (j > 0) v = fmaf(Fp[k], tr, v);                 // [:, s:]  += fused[:, :-s] * T_r[:, s:]   (:798)
+                    if (STATS && pass) cen[k].push(v, (float)D);
+                    else acc[k].push(v, (float)D);
+                }
             }
-        }
 #pragma unroll
-        for (int k = 0; k < NH; ++k) { Fp[k] = Fc[k]; Fc[k] = Fn[k]; }
+            for (int k = 0; k < NH; ++k) { Fp[k] = Fc[k]; Fc[k] = Fn[k]; }
+        }
+        if (pass == 0) {                                              // read by the second pass only
+#pragma unroll
+            for (int k = 0; k < NH; ++k) cen[k].init(acc[k]);
+        }
     }
 #pragma unroll
     for (int k = 0; k < NH; ++k) out[((size_t)k * B + b) * HW + r] = acc[k].result();
+    if constexpr (STATS) {
+#pragma unroll
+        for (int k = 0; k < NH; ++k) cen[k].store(acc[k], stats + ((size_t)k * 3 * B + b) * HW + r, (size_t)B * HW);
+    }
 }
 
 // PyTorch upsample_trilinear3d source index, align_corners=False
@@ -111,10 +148,10 @@ __device__ __forceinline__ void src_index(int dst, float scale, int in_size, int
     l1 = src - (float)i0;
 }
 
-template <int NH>
+template <int NH, bool STATS = false>                                  // STATS and the pass loop: as volume_mapping_fwd
 __global__ __launch_bounds__(256) void trilinear_softargmin_fwd(const float* __restrict__ c, long long hs,
-                                                                float* __restrict__ out, int B, int Dl, int h, int w,
-                                                                int Do, int H, int W) {
+                                                                float* __restrict__ out, float* __restrict__ stats, int B,
+                                                                int Dl, int h, int w, int Do, int H, int W) {
     const long long HW = (long long)H * W;
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * HW) return;
@@ -138,38 +175,53 @@ __global__ __launch_bounds__(256) void trilinear_softargmin_fwd(const float* __r
         for (int k = 0; k < NH; ++k) G[k] = w00 * a[k] + w01 * bq[k] + w10 * cq[k] + w11 * d[k];
     };
     float GA[NH], GB[NH];
-    int jA = -1, jB = -1;
     Online acc[NH];
+    Centred cen[NH];
 #pragma unroll
     for (int k = 0; k < NH; ++k) acc[k].init();
     const float dscale = (float)Dl / (float)Do;
-    for (int D = 0; D < Do; ++D) {
-        int d0, d1;
-        float ld;
-        src_index(D, dscale, Dl, d0, d1, ld);
-        if (d0 != jA) {
-            if (d0 == jB) {
+    for (int pass = 0; pass < (STATS ? 2 : 1); ++pass) {
+        int jA = -1, jB = -1;
+        for (int D = 0; D < Do; ++D) {
+            int d0, d1;
+            float ld;
+            src_index(D, dscale, Dl, d0, d1, ld);
+            if (d0 != jA) {
+                if (d0 == jB) {
 #pragma unroll
-                for (int k = 0; k < NH; ++k) GA[k] = GB[k];
-            } else {
-                plane(d0, GA);
+                    for (int k = 0; k < NH; ++k) GA[k] = GB[k];
+                } else {
+                    plane(d0, GA);
+                }
+                jA = d0;
             }
-            jA = d0;
-        }
-        if (d1 != jB) {
-            if (d1 == jA) {
+            if (d1 != jB) {
+                if (d1 == jA) {
 #pragma unroll
-                for (int k = 0; k < NH; ++k) GB[k] = GA[k];
-            } else {
-                plane(d1, GB);
+                    for (int k = 0; k < NH; ++k) GB[k] = GA[k];
+                } else {
+                    plane(d1, GB);
+                }
+                jB = d1;
             }
-            jB = d1;
-        }
 #pragma unroll
-        for (int k = 0; k < NH; ++k) acc[k].push((1.f - ld) * GA[k] + ld * GB[k], (float)D);
+            for (int k = 0; k < NH; ++k) {
+                const float v = (1.f - ld) * GA[k] + ld * GB[k];
+                if (STATS && pass) cen[k].push(v, (float)D);
+                else acc[k].push(v, (float)D);
+            }
+        }
+        if (pass == 0) {                                              // read by the second pass only
+#pragma unroll
+            for (int k = 0; k < NH; ++k) cen[k].init(acc[k]);
+        }
     }
 #pragma unroll
     for (int k = 0; k < NH; ++k) out[((size_t)k * B + b) * HW + r] = acc[k].result();
+    if constexpr (STATS) {
+#pragma unroll
+        for (int k = 0; k < NH; ++k) cen[k].store(acc[k], stats + ((size_t)k * 3 * B + b) * HW + r, (size_t)B * HW);
+    }
 }
 
 
@@ -515,22 +567,63 @@ __global__ __launch_bounds__(256) void trilinear_bwd_reduce_y(const float* __res
         default: return ECM_EUNSUP;                                                    \
     }
 
+template <int NH>
+static constexpr auto volume_mapping_stats_fwd = volume_mapping_fwd<NH, true>;
+template <int NH>
+static constexpr auto trilinear_softargmin_stats_fwd = trilinear_softargmin_fwd<NH, true>;
+
+// the plain heads (stats == nullptr) and the ones that also write the statistics: one grid each
+static int launch_volume_mapping_fwd(const float* c0, long long head_stride, const float* m5, const float* mt3, float* disp,
+                                     float* stats, int nheads, int B, int Dl, int h, int w, int s, void* stream) {
+    const long long n = (long long)B * h * s * w * s;
+    dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (stats) {
+        DISPATCH_NH(volume_mapping_stats_fwd, grid, block, 0, ecm_stream(stream), c0, head_stride, m5, mt3, disp, stats, B, Dl, h,
+                    w, s)
+    } else {
+        DISPATCH_NH(volume_mapping_fwd, grid, block, 0, ecm_stream(stream), c0, head_stride, m5, mt3, disp, stats, B, Dl, h, w, s)
+    }
+    return ECM_LAUNCH_RESULT();
+}
+
+static int launch_trilinear_fwd(const float* c0, long long head_stride, float* disp, float* stats, int nheads, int B, int Dl,
+                                int h, int w, int Do, int H, int W, void* stream) {
+    const long long n = (long long)B * H * W;
+    dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (stats) {
+        DISPATCH_NH(trilinear_softargmin_stats_fwd, grid, block, 0, ecm_stream(stream), c0, head_stride, disp, stats, B, Dl, h, w,
+                    Do, H, W)
+    } else {
+        DISPATCH_NH(trilinear_softargmin_fwd, grid, block, 0, ecm_stream(stream), c0, head_stride, disp, stats, B, Dl, h, w, Do, H,
+                    W)
+    }
+    return ECM_LAUNCH_RESULT();
+}
+
 extern "C" int ecm_volume_mapping_fwd(const float* c0, long long head_stride, const float* m5, const float* mt3,
                                       float* disp, int nheads, int B, int Dl, int h, int w, int s, void* stream) {
     ECM_CHECK_ARG(c0 && m5 && mt3 && disp && B > 0 && Dl > 0 && h > 0 && w > 0 && s > 0);
-    const long long n = (long long)B * h * s * w * s;
-    dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    DISPATCH_NH(volume_mapping_fwd, grid, block, 0, ecm_stream(stream), c0, head_stride, m5, mt3, disp, B, Dl, h, w, s)
-    return ECM_LAUNCH_RESULT();
+    return launch_volume_mapping_fwd(c0, head_stride, m5, mt3, disp, nullptr, nheads, B, Dl, h, w, s, stream);
+}
+
+extern "C" int ecm_volume_mapping_stats_fwd(const float* c0, long long head_stride, const float* m5, const float* mt3,
+                                            float* disp, float* stats, int nheads, int B, int Dl, int h, int w, int s,
+                                            void* stream) {
+    ECM_CHECK_ARG(c0 && m5 && mt3 && disp && stats && B > 0 && Dl > 0 && h > 0 && w > 0 && s > 0);
+    return launch_volume_mapping_fwd(c0, head_stride, m5, mt3, disp, stats, nheads, B, Dl, h, w, s, stream);
 }
 
 extern "C" int ecm_trilinear_softargmin_fwd(const float* c0, long long head_stride, float* disp, int nheads, int B, int Dl,
                                             int h, int w, int Do, int H, int W, void* stream) {
     ECM_CHECK_ARG(c0 && disp && B > 0 && Dl > 0 && h > 0 && w > 0 && Do > 0 && H > 0 && W > 0);
-    const long long n = (long long)B * H * W;
-    dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    DISPATCH_NH(trilinear_softargmin_fwd, grid, block, 0, ecm_stream(stream), c0, head_stride, disp, B, Dl, h, w, Do, H, W)
-    return ECM_LAUNCH_RESULT();
+    return launch_trilinear_fwd(c0, head_stride, disp, nullptr, nheads, B, Dl, h, w, Do, H, W, stream);
+}
+
+extern "C" int ecm_trilinear_softargmin_stats_fwd(const float* c0, long long head_stride, float* disp, float* stats,
+                                                  int nheads, int B, int Dl, int h, int w, int Do, int H, int W,
+                                                  void* stream) {
+    ECM_CHECK_ARG(c0 && disp && stats && B > 0 && Dl > 0 && h > 0 && w > 0 && Do > 0 && H > 0 && W > 0);
+    return launch_trilinear_fwd(c0, head_stride, disp, stats, nheads, B, Dl, h, w, Do, H, W, stream);
 }
 
 extern "C" long long ecm_volume_mapping_bwd_scratch_bytes(int nheads, int B, int Dl, int h, int w, int s) {

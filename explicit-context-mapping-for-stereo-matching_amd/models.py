@@ -14,6 +14,7 @@ Deliberate deviations (documented in DESIGN.md):
 """
 from __future__ import annotations
 
+import collections
 import math
 import os as _os
 
@@ -591,6 +592,18 @@ class six_related_context_mapping(nn.Module):
         return tuple(m5[:, n:n + 1] for n in range(5)), tuple(mt3[:, n:n + 1] for n in range(3))
 
 
+# What _ECMNet.predict returns: per requested head, the disparity and the standard deviation (pixels), peak probability and
+# entropy (nats) of the distribution whose mean it is; each field a tuple of [B,1,H,W] tensors.
+Prediction = collections.namedtuple("Prediction", "disparity std peak entropy")
+
+_NO_DISTRIBUTION = {
+    "five": "the full-resolution disparity of this head is a sum of low-resolution disparities weighted by softmax * logit planes: "
+            "signed weights that do not sum to one, so it is not the mean of any distribution over disparities",
+    "srr": "a refinement decoder follows the soft-argmin heads: the full-resolution disparity is the decoder's output, and no "
+           "distribution over disparities exists there",
+}
+
+
 class _ECMNet(nn.Module):
     """Shared skeleton of the registered architectures: encoder -> cost volume -> dres0/1 -> 1 or 3 hourglasses ->
     classifiers (`_aggregate`) -> head (`hot_path`).  Subclasses set ENCODER, HOURGLASSES and HEAD exactly as their reference
@@ -682,6 +695,37 @@ class _ECMNet(nn.Module):
         lr, _, hr = self.feature_extraction(torch.cat([left, right], 0))      # one encoder pass for both images
         return self.hot_path(lr[:B], hr[:B], lr[B:], hr[B:], out_hw=left.shape[-2:])
 
+    def head_stats(self, left, right):
+        """One forward up to the head, then the head with its statistics: (disp, std, peak, entropy), each [NH,B,H,W] for the
+        NH classifiers of the net, and the head's operands (what ops.*_stats was called with), for predict()."""
+        B = left.shape[0]
+        lr, _, hr = self.feature_extraction(torch.cat([left, right], 0))
+        lr_l, hr_l, lr_r, hr_r = lr[:B], hr[:B], lr[B:], hr[B:]
+        scale = hr_l.shape[-1] // lr_l.shape[-1]
+        planes = self.mapping_matrix.planes(lr_l, hr_l, lr_r, hr_r) if self.HEAD == "volume" else None
+        c = torch.stack(self._aggregate(lr_l, lr_r, self.maxdisp // scale), 0)
+        if self.HEAD == "volume":
+            args = (c, planes[0], planes[1], scale)
+            return ops.volume_mapping_stats(*args), args
+        args = (c, self.maxdisp, *left.shape[-2:])
+        return ops.trilinear_softargmin_stats(*args), args
+
+    def predict(self, left, right, heads=None):
+        """One inference forward that also says how sure each disparity is: a Prediction whose .disparity, .std, .peak and
+        .entropy are tuples of [B,1,H,W], one entry per head in `heads` (default: all three; the one-hourglass nets repeat
+        their single head as forward does).  .disparity is bit-identical to forward's under torch.no_grad().  All classifiers
+        run whatever `heads` says -- head k's logits are c_0 + ... + c_k -- and the head kernel is launched for all of them:
+        a launch for fewer heads is another template instantiation, which need not round like forward's.  Forward only."""
+        if self.HEAD in _NO_DISTRIBUTION:                                # before any device work
+            raise NotImplementedError(f"{type(self).__name__}.predict: {_NO_DISTRIBUTION[self.HEAD]}")
+        heads = (0, 1, 2) if heads is None else tuple(int(k) for k in heads)
+        if not heads or any(k < 0 or k > 2 for k in heads):
+            raise ValueError(f"predict: heads {heads}: a non-empty selection of 0, 1, 2")
+        with torch.no_grad():
+            fields, _ = self.head_stats(left, right)
+        last = fields[0].shape[0] - 1
+        return Prediction(*(tuple(f[min(k, last)].unsqueeze(1) for k in heads) for f in fields))
+
 
 class cmfsm(_ECMNet):
     """cmfsm.py:594-774.  forward(left, right) -> (pred1, pred2, pred3), each [B,1,H,W] in pixels."""
@@ -704,6 +748,15 @@ class cmfsm(_ECMNet):
             ops.pace_side_streams()        # host run-ahead bound: the previous step's side-stream weight gradients have finished
         lr, _, hr = self.feature_extraction(torch.cat([left, right], 0), head=B)      # hr: the left images' map only
         return self.hot_path(lr[:B], hr, lr[B:])
+
+    def head_stats(self, left, right):
+        B = left.shape[0]
+        lr, _, hr = self.feature_extraction(torch.cat([left, right], 0), head=B)
+        lr_l, lr_r = lr[:B], lr[B:]
+        scale = hr.shape[-1] // lr_l.shape[-1]
+        w9 = self.mapping_matrix.weights(lr_l, hr)
+        args = (torch.stack(self._aggregate(lr_l, lr_r, self.maxdisp // scale), 0), w9, scale)
+        return ops.ecm_aggregate9_stats(*args), args
 
 
 class cmfsm_sub_8(_ECMNet):

@@ -439,6 +439,71 @@ def trilinear_softargmin(c, Do, H, W):
     return TrilinearSoftArgmin.apply(c, int(Do), int(H), int(W))
 
 
+# ------------------------------------------------------------------------------------ per-pixel uncertainty of the heads
+# DESIGN.md section 15.  Forward only: each op returns (disp, std, peak, entropy), every one [NH,B,H,W] and outside any graph;
+# disp is bit-identical to the plain head's, the other three describe the distribution whose mean it is.
+def _stats_planes(disp, stats):
+    return disp, stats[:, 0], stats[:, 1], stats[:, 2]
+
+
+@torch.no_grad()
+def ecm_aggregate9_stats(c, w9, scale):
+    """The eight-neighbour head (softargmin_heads + ecm_aggregate9) on c [NH,B,D,h,w] raw classifier outputs and w9 [B,9,H,W],
+    with the statistics of each HR pixel's mixture of its valid neighbours' low-resolution distributions."""
+    scale = int(scale)
+    _chk(c, w9)
+    _need(c.dim() == 5 and c.numel() > 0 and scale >= 1, lambda: f"ecm_aggregate9_stats: c {tuple(c.shape)}, scale {scale}: want [heads,B,D,h,w]")
+    c, w9 = _c(c.detach()), _c(w9.detach())
+    NH, B, D, h, w = c.shape
+    H, W = h * scale, w * scale
+    _need(tuple(w9.shape) == (B, 9, H, W),
+          lambda: f"ecm_aggregate9_stats: w9 {tuple(w9.shape)} for c {tuple(c.shape)} at scale {scale}: want [B,9,h*scale,w*scale]")
+    d = torch.empty(NH, B, h, w, device=c.device, dtype=c.dtype)
+    lse = torch.empty(NH, B, h, w, device=c.device, dtype=c.dtype)
+    disp = torch.empty(NH, B, H, W, device=c.device, dtype=c.dtype)
+    stats = torch.empty(NH, 3, B, H, W, device=c.device, dtype=c.dtype)
+    hs = C.c_longlong(B * D * h * w)
+    _lib.call("ecm_softargmin_heads_lse_fwd", _p(c), hs, _p(d), _p(lse), NH, B, D, h * w, _stream())
+    _lib.call("ecm_aggregate9_fwd", _p(d), _p(w9), _p(disp), NH, B, h, w, scale, _stream())
+    _lib.call("ecm_aggregate9_stats_fwd", _p(c), hs, _p(lse), _p(w9), _p(stats), NH, B, D, h, w, scale, _stream())
+    return _stats_planes(disp, stats)
+
+
+@torch.no_grad()
+def volume_mapping_stats(c, m5, mt3, scale):
+    """volume_mapping with the statistics of its softmax over the Dl * scale fused logits."""
+    scale = int(scale)
+    _chk(c, m5, mt3)
+    _need(c.dim() == 5 and scale >= 1 and c.numel() > 0, lambda: f"volume_mapping_stats: c {tuple(c.shape)}, scale {scale}")
+    c, m5, mt3 = _c(c.detach()), _c(m5.detach()), _c(mt3.detach())
+    NH, B, Dl, h, w = c.shape
+    H, W = h * scale, w * scale
+    _need(tuple(m5.shape) == (B, 5, H, W) and tuple(mt3.shape) == (B, 3, H, W),
+          lambda: f"volume_mapping_stats: m5 {tuple(m5.shape)} / mt3 {tuple(mt3.shape)} for c {tuple(c.shape)} at scale {scale}: "
+                  "want [B,5,h*scale,w*scale] and [B,3,h*scale,w*scale]")
+    disp = torch.empty(NH, B, H, W, device=c.device, dtype=c.dtype)
+    stats = torch.empty(NH, 3, B, H, W, device=c.device, dtype=c.dtype)
+    _lib.call("ecm_volume_mapping_stats_fwd", _p(c), C.c_longlong(B * Dl * h * w), _p(m5), _p(mt3), _p(disp), _p(stats), NH, B,
+              Dl, h, w, scale, _stream())
+    return _stats_planes(disp, stats)
+
+
+@torch.no_grad()
+def trilinear_softargmin_stats(c, Do, H, W):
+    """trilinear_softargmin with the statistics of its softmax over the Do interpolated logits."""
+    Do, H, W = int(Do), int(H), int(W)
+    _chk(c)
+    _need(c.dim() == 5 and c.numel() > 0 and Do >= 1 and H >= 1 and W >= 1,
+          lambda: f"trilinear_softargmin_stats: c {tuple(c.shape)} -> ({Do}, {H}, {W})")
+    c = _c(c.detach())
+    NH, B, Dl, h, w = c.shape
+    disp = torch.empty(NH, B, H, W, device=c.device, dtype=c.dtype)
+    stats = torch.empty(NH, 3, B, H, W, device=c.device, dtype=c.dtype)
+    _lib.call("ecm_trilinear_softargmin_stats_fwd", _p(c), C.c_longlong(B * Dl * h * w), _p(disp), _p(stats), NH, B, Dl, h, w,
+              Do, H, W, _stream())
+    return _stats_planes(disp, stats)
+
+
 # ------------------------------------------------------------------------------------ a5-a7 conv / deconv / GN
 def _pack_conv(w, flip_transpose=False):
     Co, Ci = w.shape[0], w.shape[1]

@@ -51,6 +51,10 @@ int ecm_softargmin_heads_fwd(const float* c0, long long head_stride, float* disp
 /* gc[head] (same packing as c) from gdisp [nheads,B,hw]; recomputes the softmax. */
 int ecm_softargmin_heads_bwd(const float* c0, long long head_stride, const float* gdisp, float* gc0,
                              int nheads, int B, int D, int hw, void* stream);
+/* ABI 8: ecm_softargmin_heads_fwd that also writes lse[k,b,p] = max_d logits_k + ln sum_d exp(logits_k - max), [nheads,B,hw]:
+ * softmax_d(logits_k) = exp(logits_k[d] - lse).  disp is bit-identical to ecm_softargmin_heads_fwd's. */
+int ecm_softargmin_heads_lse_fwd(const float* c0, long long head_stride, float* disp, float* lse,
+                                 int nheads, int B, int D, int hw, void* stream);
 /* disparityregression.forward alone (cmfsm.py:120-123): out[b,p] = sum_d x[b,d,p]*d */
 int ecm_disparity_regression_fwd(const float* x, float* out, int B, int D, int hw, void* stream);
 
@@ -61,6 +65,12 @@ int ecm_aggregate9_fwd(const float* d, const float* w9, float* out,
                        int nheads, int B, int h, int w, int s, void* stream);
 int ecm_aggregate9_bwd(const float* d, const float* w9, const float* gout, float* gd, float* gw9,
                        int nheads, int B, int h, int w, int s, void* stream);
+/* ABI 8: per-pixel uncertainty of ecm_aggregate9_fwd's output.  The HR pixel's distribution is the
+ * mixture p(d) = sum_n w9[n] p_n(d) / sum_n w9[n] over the neighbours ecm_aggregate9_fwd does not skip, p_n the LR softmax of
+ * cell+n over d < D (c0 / head_stride as in ecm_softargmin_heads_fwd, lse from ecm_softargmin_heads_lse_fwd).
+ * stats: [nheads,3,B,H,W] = s * standard deviation of p about its own mean (full-resolution pixels), max_d p, entropy (nats). */
+int ecm_aggregate9_stats_fwd(const float* c0, long long head_stride, const float* lse, const float* w9, float* stats,
+                             int nheads, int B, int D, int h, int w, int s, void* stream);
 
 /* ---- a3: eight-related context-mapping weights (cmfsm.py:431-593, 304-358, 391-428) ----------
  * lr: [B,32,h,w]; hr: [B,32,H,W]; W0 [32,66], W1 [16,32], W2 [8,16], W3 [1,8] (1x1 conv weights, no bias);
@@ -99,6 +109,10 @@ int ecm_context_weights_bwd(const float* lr, const float* hr, const float* W0, c
  * c: raw classifier outputs [nheads][B,Dl,h,w] (head k uses c_0+...+c_k); disp: [nheads,B,H,W]. */
 int ecm_volume_mapping_fwd(const float* c0, long long head_stride, const float* m5, const float* mt3, float* disp,
                            int nheads, int B, int Dl, int h, int w, int s, void* stream);
+/* ABI 8: the same kernel body, which also writes stats [nheads,3,B,H,W] = standard deviation (pixels), peak and entropy
+ * (nats) of the softmax over D whose mean is disp; disp is bit-identical to ecm_volume_mapping_fwd's. */
+int ecm_volume_mapping_stats_fwd(const float* c0, long long head_stride, const float* m5, const float* mt3, float* disp,
+                                 float* stats, int nheads, int B, int Dl, int h, int w, int s, void* stream);
 /* Gradients of c (same packing), m5 and mt3 from gdisp [nheads,B,H,W]; s must be a power of two <= 64.  Deterministic:
  * every sum is taken in a fixed order (per-row partial sums in `scratch`, gathered by a second kernel; no float atomics),
  * every output element is written exactly once. */
@@ -111,6 +125,9 @@ int ecm_volume_mapping_bwd(const float* c0, long long head_stride, const float* 
  * logits to [Do,H,W], softmax over Do, regression.  c as above (cumulative over heads); disp: [nheads,B,H,W]. */
 int ecm_trilinear_softargmin_fwd(const float* c0, long long head_stride, float* disp,
                                  int nheads, int B, int Dl, int h, int w, int Do, int H, int W, void* stream);
+/* ABI 8: with stats [nheads,3,B,H,W] as ecm_volume_mapping_stats_fwd; disp bit-identical to ecm_trilinear_softargmin_fwd's. */
+int ecm_trilinear_softargmin_stats_fwd(const float* c0, long long head_stride, float* disp, float* stats,
+                                       int nheads, int B, int Dl, int h, int w, int Do, int H, int W, void* stream);
 /* Deterministic (per-pixel plane gradients in `scratch`, then separable fixed-order reductions along x and y). */
 long long ecm_trilinear_softargmin_bwd_scratch_bytes(int nheads, int B, int Dl, int h, int w, int H, int W);
 int ecm_trilinear_softargmin_bwd(const float* c0, long long head_stride, const float* gdisp, float* gc0,

@@ -1640,7 +1640,8 @@ def check_async_errors(clear=True):
 
 # ---- opt-in bf16 inference of the 3-D aggregation stack ----------------------------------------------------------------------
 # Inside `with aggregation_dtype(torch.bfloat16):` the models run dres0's second convolution through the classifiers' 32 -> 1
-# layers on bf16 volumes (csrc/bf16_infer.hip: bf16 operands on the matrix cores, fp32 accumulation, one rounding per output).
+# layers on bf16 volumes (csrc/bf16_infer.hip on the body of csrc/bf16_conv3d.h: bf16 operands on the matrix cores, fp32
+# accumulation, one rounding per output).
 # The setting is process-wide like WINOGRAD (nn.DataParallel replicas run in other threads), inference only (nothing here has
 # a backward: a 3-D op reached with grad enabled raises), and the fp32 path outside the block is untouched.  The ops below
 # dispatch on the dtype of the volume; weights stay fp32 parameters, packed to bf16 images per call (cached under
@@ -1703,16 +1704,32 @@ def _chk_bf16(*ts):
             raise RuntimeError(f"ecm bf16 ops take bfloat16 CUDA volumes (got {t.dtype} on {t.device})")
 
 
-def _pack_bf16(w, transposed):
-    """bf16 weight image [Ci/8][28][Co][8] of a Conv3d weight [Co,Ci,3,3,3] or (transposed) a ConvTranspose3d one [Ci,Co,3,3,3]."""
+# the two families of csrc/bf16_conv3d.h: (size query, pack entry) and the stem of their frozen_weights() cache keys
+_BF16_PACK = (("ecm_conv3d_bf16_packed_elems", "ecm_conv3d_bf16_pack_weight"), "bf16")
+_SPLIT_PACK = (("ecm_conv3d_split_packed_elems", "ecm_conv3d_split_pack_weight"), "split")
+
+
+def _pack_taps(w, transposed, entries, stem):
+    """bf16 weight image [Ci/8][terms][28][Co][8] of a 3x3x3 weight read as a convolution (w [Co,Ci,27]) or, transposed, as a
+    transposed convolution (w [Ci,Co,27]): one term for _BF16_PACK, the three split terms for _SPLIT_PACK -- the operands
+    _pack_conv(w) and _pack_deconv(w) build for the fp32 kernels."""
     Ci, Co = (w.shape[0], w.shape[1]) if transposed else (w.shape[1], w.shape[0])
+    elems, pack = entries
 
     def build():
         wc = _c(w.detach())
-        packed = torch.empty(_lib.query("ecm_conv3d_bf16_packed_elems", Ci, Co), device=w.device, dtype=torch.bfloat16)
-        _lib.call("ecm_conv3d_bf16_pack_weight", _p(wc), _p(packed), Ci, Co, int(transposed), _stream())
+        packed = torch.empty(_lib.query(elems, Ci, Co), device=w.device, dtype=torch.bfloat16)
+        _lib.call(pack, _p(wc), _p(packed), Ci, Co, int(transposed), _stream())
         return packed
-    return _cached_pack(w, "bf16_deconv" if transposed else "bf16_conv", build)
+    return _cached_pack(w, stem + ("_deconv" if transposed else "_conv"), build)
+
+
+def _pack_bf16(w, transposed):
+    return _pack_taps(w, transposed, *_BF16_PACK)
+
+
+def _pack_split(w, transposed):
+    return _pack_taps(w, transposed, *_SPLIT_PACK)
 
 
 def _conv3d_bf16(x, w, stride, fork):
@@ -1750,8 +1767,9 @@ def _deconv3d_bf16(x, w):
 
 # ---- opt-in split-bf16 products for the stride-2 3-D convolutions ------------------------------------------------------------
 # Inside `with split_products("bf16x3"):` the stride-2 family (the hourglass's conv1/conv3 and its two transposed
-# convolutions, cmfsm.py:244-281) runs csrc/split_bf16.hip: every fp32 operand is split into three bf16 terms and the six
-# leading cross products accumulate in fp32 on the bf16 matrix cores.  Tensors stay fp32, the result is fp32-equivalent (the
+# convolutions, cmfsm.py:244-281) runs csrc/split_bf16.hip (the same body, csrc/bf16_conv3d.h): every fp32 operand is split
+# into three bf16 terms and the six leading cross products accumulate in fp32 on the bf16 matrix cores.  Tensors stay fp32, the
+# result is fp32-equivalent (the
 # fp64 yardstick of the fp32 kernels, tests/test_hip_split_bf16_fp64.py) and the autograd Functions are the usual ones, so the
 # block works with grad enabled -- unlike the bf16 regions above, which change the numerics and are inference only.
 # The setting is process-wide like WINOGRAD, nests and restores.  It is read when a layer's FORWARD runs and rides on the
@@ -1808,19 +1826,6 @@ def _split_use(kind, x, Ci, Co):
         return False
     vox = x.shape[2] * x.shape[3] * x.shape[4]
     return split_supported(Ci, Co, vox * 8 if kind.startswith("deconv") else vox)
-
-
-def _pack_split(w, transposed):
-    """Split-bf16 weight image [Ci/8][3][28][Co][8] of a 3x3x3 weight read as a convolution (w [Co,Ci,27]) or, transposed, as a
-    transposed convolution (w [Ci,Co,27]) -- the operands _pack_conv(w) and _pack_deconv(w) build for the fp32 kernels."""
-    Ci, Co = (w.shape[0], w.shape[1]) if transposed else (w.shape[1], w.shape[0])
-
-    def build():
-        wc = _c(w.detach())
-        packed = torch.empty(_lib.query("ecm_conv3d_split_packed_elems", Ci, Co), device=w.device, dtype=torch.bfloat16)
-        _lib.call("ecm_conv3d_split_pack_weight", _p(wc), _p(packed), Ci, Co, int(transposed), _stream())
-        return packed
-    return _cached_pack(w, "split_deconv" if transposed else "split_conv", build)
 
 
 def _split_conv_fwd(x, packed, Co):

@@ -419,7 +419,7 @@ int ecm_stereo_loss_bwd(const float* p1, const float* p2, const float* p3, const
                         const float* gloss, float* g1, float* g2, float* g3, long long n, float maxdisp,
                         float w1, float w2, float w3, void* stream);
 
-/* ---- opt-in bf16 inference of the 3-D aggregation stack (ops.aggregation_dtype; bf16_infer.hip) ------------------------
+/* ---- opt-in bf16 inference of the 3-D aggregation stack (ops.aggregation_dtype; bf16_infer.hip on bf16_conv3d.h) -------
  * (Its GroupNorm is the two-stage forward above: ecm_gn3d_stats_bf16, ecm_gn3d_apply_bf16 / _f32_bf16.)
  * Forward only.  Volumes are contiguous bf16 NCDHW (unsigned short = the bf16 bit pattern), weights and GroupNorm
  * parameters fp32; products accumulate in fp32 and every output is rounded once to bf16 (round to nearest even, NaN stays
@@ -471,7 +471,7 @@ int ecm_deconv2d_k3s2_bias_bf16_fwd(const unsigned short* x, const unsigned shor
 int ecm_conv2d_c1_bf16_fwd(const unsigned short* x, const float* w, const float* bias, float* y, int B, int Ci, int H, int W,
                            void* stream);
 
-/* ---- opt-in split-bf16 products for the stride-2 3-D convolutions (ops.split_products; split_bf16.hip) ------------------
+/* ---- opt-in split-bf16 products for the stride-2 3-D convolutions (ops.split_products; split_bf16.hip on bf16_conv3d.h) -
  * Forward and data gradient of the hourglass's stride-2 family: Conv3d k3 p1 s2 (conv1 / conv3, cmfsm.py:244-258) and
  * ConvTranspose3d k3 s2 p1 op1 (conv5 / conv6, cmfsm.py:262-268); each is the other's adjoint, so the two entries serve all
  * four.  Volumes and results are contiguous fp32 NCDHW.  Every fp32 operand is split by truncation into three bf16 terms

@@ -53,11 +53,12 @@ def _within_ulp(got, want32, label):
 
 # ------------------------------------------------------------------------------------------------ kernel parity
 # (B, Ci, Co, (D, H, W), stride): the stack's layers at 576x960 (D' = 48) and its 1/2 and 1/4 hourglass levels, plus awkward
-# shapes (w = 78: rows of 156 bytes, D' = 12, batch 1, odd sizes after a stride-2 layer)
+# shapes (w = 78: rows of 156 bytes, D' = 12, batch 1, odd sizes after a stride-2 layer; stride 2 onto one output-channel tile,
+# eight chunks, odd extents)
 _CONV = [(4, 32, 32, (48, 144, 240), 1), (4, 32, 64, (48, 144, 240), 2), (4, 64, 64, (24, 72, 120), 1),
          (4, 64, 64, (24, 72, 120), 2), (4, 64, 64, (12, 36, 60), 1),
          (1, 32, 32, (12, 24, 78), 1), (1, 32, 64, (12, 24, 78), 2), (1, 64, 64, (6, 12, 39), 1), (1, 64, 64, (6, 12, 39), 2),
-         (2, 32, 32, (3, 5, 33), 1), (1, 64, 64, (1, 1, 1), 2)]
+         (2, 32, 32, (3, 5, 33), 1), (1, 64, 64, (1, 1, 1), 2), (1, 64, 32, (3, 5, 35), 2)]
 
 
 @pytest.mark.parametrize("B,Ci,Co,dims,stride", _CONV)
@@ -145,7 +146,8 @@ def test_f32_to_bf16_keeps_nan(ecm):
 
 
 # ------------------------------------------------------------------------------------------------ guard bands
-@pytest.mark.parametrize("B,Ci,Co,dims,stride", [(1, 32, 32, (3, 5, 78), 1), (1, 32, 64, (5, 7, 39), 2), (2, 64, 64, (2, 3, 33), 2)])
+@pytest.mark.parametrize("B,Ci,Co,dims,stride", [(1, 32, 32, (3, 5, 78), 1), (1, 32, 64, (5, 7, 39), 2), (2, 64, 64, (2, 3, 33), 2),
+                                                 (1, 64, 32, (3, 5, 35), 2)])
 def test_guard_bands_conv3d_bf16(ecm, B, Ci, Co, dims, stride):
     x, w = _R(B, Ci, *dims, seed=1, dtype=BF), _R(Co, Ci, 3, 3, 3, seed=2, scale=0.1)
     with torch.no_grad(), guarded(ecm) as g:

@@ -9,28 +9,50 @@ import torch
 
 from conftest import ROOT
 
-SRC = os.path.join(ROOT, "explicit-context-mapping-for-stereo-matching_amd", "csrc", "split_bf16.hip")
+CSRC = os.path.join(ROOT, "explicit-context-mapping-for-stereo-matching_amd", "csrc")
+SRC = os.path.join(CSRC, "split_bf16.hip")
+BODY = os.path.join(CSRC, "bf16_conv3d.h")           # the implicit-GEMM body split_bf16.hip and bf16_infer.hip share
 NEW_ENTRIES = ("ecm_conv3d_split_packed_elems", "ecm_conv3d_split_pack_weight", "ecm_conv3d_k3s2_split_fwd",
                "ecm_deconv3d_k3s2_split_fwd")
 
-# ---- the tile constants, restated; test_constants_match_the_source pins them to split_bf16.hip ---------------------------------
+# ---- the tile constants, restated; test_constants_match_the_source pins them to split_bf16.hip (TW, NSLOT: bf16_conv3d.h) -------
 TW, NSLOT, NTERM, CONV_SLOTS = 32, 28, 3, 27
 S2_TD, S2_TH, DC_TD, DC_TH = 2, 2, 4, 4
 LIMIT = 2.0 ** -110             # |x| >= LIMIT: x1 + x2 + x3 == x exactly (the header comment's guaranteed range)
 
 
-def _src_const(name):
-    m = re.search(r"\b%s = (\d+)" % name, open(SRC).read())
+def _src_const(name, path=SRC):
+    m = re.search(r"\b%s = (\d+)" % name, open(path).read())
     assert m, name
     return int(m.group(1))
 
 
 def test_constants_match_the_source():
-    for name, val in (("TW", TW), ("NSLOT", NSLOT), ("NTERM", NTERM), ("CONV_SLOTS", CONV_SLOTS), ("S2_TD", S2_TD), ("S2_TH", S2_TH),
-                      ("DC_TD", DC_TD), ("DC_TH", DC_TH)):
+    for name, val in (("TW", TW), ("NSLOT", NSLOT)):
+        assert _src_const(name, BODY) == val, name
+    for name, val in (("NTERM", NTERM), ("CONV_SLOTS", CONV_SLOTS), ("S2_TD", S2_TD), ("S2_TH", S2_TH), ("DC_TD", DC_TD), ("DC_TH", DC_TH)):
         assert _src_const(name) == val, name
     src = open(SRC).read()
     assert "2^-110" in src and "tests/test_split_bf16_cpu.py" in src      # the documented range, and the pointer to this restatement
+
+
+def test_conv3d_body_exists_once():
+    """The tap geometry, the staging, the MFMA block, the phase switch and the launch live in bf16_conv3d.h alone: the two kernel
+    families built on it hold their operand policy, tile shapes and entries, and split3 is split_bf16.hip's."""
+    body = open(BODY).read()
+    users = [open(os.path.join(CSRC, f)).read() for f in ("bf16_infer.hip", "split_bf16.hip")]
+    for u in users:
+        assert '#include "bf16_conv3d.h"' in u
+    for pattern in (r"constexpr int TW\b", r"constexpr int NSLOT\b", r"constexpr void dc_tap\(", r"struct Geo\b", r"constexpr int tap_off\(",
+                    r"__builtin_amdgcn_make_buffer_rsrc\(", r"__builtin_amdgcn_mfma_f32_32x32x16_bf16\(", r"#define ECM_DC_PHASE\b",
+                    r"ecm_allow_lds\(", r"hipLaunchKernelGGL\(\(conv3d_taps<"):
+        assert len(re.findall(pattern, body)) == 1, pattern
+    for name in ("dc_tap(", "struct Geo", "tap_off(", "make_buffer_rsrc(", "mfma_f32_32x32x16_bf16(", "ECM_DC_PHASE", "ecm_allow_lds(",
+                 "hipLaunchKernelGGL", "__global__", "__syncthreads"):
+        for u in users:
+            assert name not in u, name
+    assert "split3" not in body and "split3" not in users[0]
+    assert len(re.findall(r"__device__ __forceinline__ void split3\(", users[1])) == 1
 
 
 def test_lds_budget():

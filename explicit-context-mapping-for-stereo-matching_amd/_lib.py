@@ -25,6 +25,7 @@ PROTOTYPES = {
     "ecm_disparity_regression_fwd": (_I, [_P, _P, _I, _I, _I, _P]),
     "ecm_aggregate9_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "ecm_aggregate9_stats_fwd": (_I, [_P, _LL, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "ecm_aggregate9_mode_fwd": (_I, [_P, _LL, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "ecm_aggregate9_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "ecm_weights9_scratch_bytes": (_LL, [_I, _I, _I]),
     "ecm_weights9_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _I, _P]),
@@ -35,6 +36,8 @@ PROTOTYPES = {
     "ecm_trilinear_softargmin_fwd": (_I, [_P, _LL, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "ecm_volume_mapping_stats_fwd": (_I, [_P, _LL, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ecm_trilinear_softargmin_stats_fwd": (_I, [_P, _LL, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "ecm_volume_mapping_mode_fwd": (_I, [_P, _LL, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "ecm_trilinear_softargmin_mode_fwd": (_I, [_P, _LL, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "ecm_volume_mapping_bwd_scratch_bytes": (_LL, [_I] * 6),
     "ecm_volume_mapping_bwd": (_I, [_P, _LL, _P, _P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _I, _I, _I, _P]),
     "ecm_trilinear_softargmin_bwd_scratch_bytes": (_LL, [_I] * 7),

@@ -42,6 +42,32 @@ struct Centred {
     }
 };
 
+// The modal estimate of the same distribution, in two walks of its own over the same logits: seek() keeps
+// the first maximum of the logit (strict >: the lowest D wins an exact tie), which is also the argmax of p; push() then sums
+// e = exp(v - m) over all D and, inside the window |D - D*| <= r, e and e (D - D*).  Centred on D*, never a ratio of raw first
+// moments.  A NaN logit never passes seek()'s comparison and turns tot, hence all three planes, into NaN.
+struct Modal {
+    float m, tot, sw, sm;
+    int dstar;
+    __device__ __forceinline__ void init() { m = -INFINITY; dstar = 0; tot = 0.f; sw = 0.f; sm = 0.f; }
+    __device__ __forceinline__ void seek(float v, int D) {
+        if (v > m) { m = v; dstar = D; }
+    }
+    __device__ __forceinline__ void push(float v, int D, int r) {
+        const float e = expf(v - m);
+        const int c = D - dstar;
+        tot += e;
+        if (c >= -r && c <= r) { sw += e; sm = fmaf(e, (float)c, sm); }
+    }
+    // modal [NH,3,B,H,W] = (mode, mass, index): o points at (k, 0, b, pixel), plane = B*H*W
+    __device__ __forceinline__ void store(float* __restrict__ o, size_t plane) const {
+        const bool nan = tot != tot;
+        o[0] = nan ? tot : (float)dstar + sm / sw;
+        o[plane] = nan ? tot : fminf(sw / tot, 1.f);
+        o[2 * plane] = nan ? tot : (float)dstar;
+    }
+};
+
 __device__ __forceinline__ void wave_fence() {
     // LDS operations of ONE wave execute in issue order; this keeps the compiler from moving them across the point
     // (a later lane-shifted read must see an earlier store of the neighbouring lane)
@@ -76,14 +102,16 @@ __device__ __forceinline__ void fuse5(const float* __restrict__ c, long long hs,
     }
 }
 
-// STATS: a second pass over the same logits for stats [NH,3,B,H,W] (std, peak, entropy).  The loop body below is the only
-// place the logits are formed, so the two instantiations cannot drift apart; without STATS the pass loop runs once and the
-// kernel is the one it was.
-template <int NH, bool STATS = false>
+// MODE 1 (STATS): a second pass over the same logits for stats [NH,3,B,H,W] (std, peak, entropy).  MODE 2 (MODAL): two passes
+// into Modal, for modal [NH,3,B,H,W] (mode, mass, index) in the place of stats, window radius `radius`; it writes no disparity.
+// The loop body below is the only place the logits are formed, so the instantiations cannot drift apart; in MODE 0 the pass
+// loop runs once and the kernel is the one it was.
+template <int NH, int MODE = 0>
 __global__ __launch_bounds__(256) void volume_mapping_fwd(const float* __restrict__ c, long long hs,
                                                           const float* __restrict__ m5p, const float* __restrict__ mt3p,
                                                           float* __restrict__ out, float* __restrict__ stats, int B, int Dl,
-                                                          int h, int w, int s) {
+                                                          int h, int w, int s, int radius) {
+    constexpr bool STATS = MODE == 1, MODAL = MODE == 2;
     const int H = h * s, W = w * s;
     const long long HW = (long long)H * W;
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -100,9 +128,12 @@ __global__ __launch_bounds__(256) void volume_mapping_fwd(const float* __restric
     float Fp[NH], Fc[NH], Fn[NH];
     Online acc[NH];
     Centred cen[NH];
+    Modal mod[NH];
 #pragma unroll
     for (int k = 0; k < NH; ++k) acc[k].init();
-    for (int pass = 0; pass < (STATS ? 2 : 1); ++pass) {
+#pragma unroll
+    for (int k = 0; k < NH; ++k) mod[k].init();
+    for (int pass = 0; pass < (MODE ? 2 : 1); ++pass) {
 #pragma unroll
         for (int k = 0; k < NH; ++k) Fp[k] = 0.f;
         fuse5<NH>(c, hs, bbase, 0, h, w, cy, cx, m5, Fc);
@@ -118,7 +149,10 @@ __global__ __launch_bounds__(256) void volume_mapping_fwd(const float* __restric
                     float v = Fc[k] * t0;
                     if (has_next) v = fmaf(Fn[k], tl, v);              // [:, :-s] += fused[:, s:] * T_l[:, :-s]   (:797)
                     if (j > 0) v = fmaf(Fp[k], tr, v);                 // [:, s:]  += fused[:, :-s] * T_r[:, s:]   (:798)
-                    if (STATS && pass) cen[k].push(v, (float)D);
+                    if constexpr (MODAL) {
+                        if (pass) mod[k].push(v, D, radius);
+                        else mod[k].seek(v, D);
+                    } else if (STATS && pass) cen[k].push(v, (float)D);
                     else acc[k].push(v, (float)D);
                 }
             }
@@ -129,6 +163,11 @@ __global__ __launch_bounds__(256) void volume_mapping_fwd(const float* __restric
 #pragma unroll
             for (int k = 0; k < NH; ++k) cen[k].init(acc[k]);
         }
+    }
+    if constexpr (MODAL) {
+#pragma unroll
+        for (int k = 0; k < NH; ++k) mod[k].store(stats + ((size_t)k * 3 * B + b) * HW + r, (size_t)B * HW);
+        return;
     }
 #pragma unroll
     for (int k = 0; k < NH; ++k) out[((size_t)k * B + b) * HW + r] = acc[k].result();
@@ -148,10 +187,11 @@ __device__ __forceinline__ void src_index(int dst, float scale, int in_size, int
     l1 = src - (float)i0;
 }
 
-template <int NH, bool STATS = false>                                  // STATS and the pass loop: as volume_mapping_fwd
+template <int NH, int MODE = 0>                                        // MODE and the pass loop: as volume_mapping_fwd
 __global__ __launch_bounds__(256) void trilinear_softargmin_fwd(const float* __restrict__ c, long long hs,
                                                                 float* __restrict__ out, float* __restrict__ stats, int B,
-                                                                int Dl, int h, int w, int Do, int H, int W) {
+                                                                int Dl, int h, int w, int Do, int H, int W, int radius) {
+    constexpr bool STATS = MODE == 1, MODAL = MODE == 2;
     const long long HW = (long long)H * W;
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * HW) return;
@@ -177,10 +217,13 @@ __global__ __launch_bounds__(256) void trilinear_softargmin_fwd(const float* __r
     float GA[NH], GB[NH];
     Online acc[NH];
     Centred cen[NH];
+    Modal mod[NH];
 #pragma unroll
     for (int k = 0; k < NH; ++k) acc[k].init();
+#pragma unroll
+    for (int k = 0; k < NH; ++k) mod[k].init();
     const float dscale = (float)Dl / (float)Do;
-    for (int pass = 0; pass < (STATS ? 2 : 1); ++pass) {
+    for (int pass = 0; pass < (MODE ? 2 : 1); ++pass) {
         int jA = -1, jB = -1;
         for (int D = 0; D < Do; ++D) {
             int d0, d1;
@@ -207,7 +250,10 @@ __global__ __launch_bounds__(256) void trilinear_softargmin_fwd(const float* __r
 #pragma unroll
             for (int k = 0; k < NH; ++k) {
                 const float v = (1.f - ld) * GA[k] + ld * GB[k];
-                if (STATS && pass) cen[k].push(v, (float)D);
+                if constexpr (MODAL) {
+                    if (pass) mod[k].push(v, D, radius);
+                    else mod[k].seek(v, D);
+                } else if (STATS && pass) cen[k].push(v, (float)D);
                 else acc[k].push(v, (float)D);
             }
         }
@@ -215,6 +261,11 @@ __global__ __launch_bounds__(256) void trilinear_softargmin_fwd(const float* __r
 #pragma unroll
             for (int k = 0; k < NH; ++k) cen[k].init(acc[k]);
         }
+    }
+    if constexpr (MODAL) {
+#pragma unroll
+        for (int k = 0; k < NH; ++k) mod[k].store(stats + ((size_t)k * 3 * B + b) * HW + r, (size_t)B * HW);
+        return;
     }
 #pragma unroll
     for (int k = 0; k < NH; ++k) out[((size_t)k * B + b) * HW + r] = acc[k].result();
@@ -568,34 +619,46 @@ __global__ __launch_bounds__(256) void trilinear_bwd_reduce_y(const float* __res
     }
 
 template <int NH>
-static constexpr auto volume_mapping_stats_fwd = volume_mapping_fwd<NH, true>;
+static constexpr auto volume_mapping_stats_fwd = volume_mapping_fwd<NH, 1>;
 template <int NH>
-static constexpr auto trilinear_softargmin_stats_fwd = trilinear_softargmin_fwd<NH, true>;
+static constexpr auto volume_mapping_mode_fwd = volume_mapping_fwd<NH, 2>;
+template <int NH>
+static constexpr auto trilinear_softargmin_stats_fwd = trilinear_softargmin_fwd<NH, 1>;
+template <int NH>
+static constexpr auto trilinear_softargmin_mode_fwd = trilinear_softargmin_fwd<NH, 2>;
 
-// the plain heads (stats == nullptr) and the ones that also write the statistics: one grid each
+// the plain heads (stats == nullptr), the ones that also write the statistics, and the modal estimate (radius >= 0: `stats` is
+// the modal buffer and disp is not written): one grid each
 static int launch_volume_mapping_fwd(const float* c0, long long head_stride, const float* m5, const float* mt3, float* disp,
-                                     float* stats, int nheads, int B, int Dl, int h, int w, int s, void* stream) {
+                                     float* stats, int nheads, int B, int Dl, int h, int w, int s, int radius, void* stream) {
     const long long n = (long long)B * h * s * w * s;
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    if (stats) {
+    if (radius >= 0) {
+        DISPATCH_NH(volume_mapping_mode_fwd, grid, block, 0, ecm_stream(stream), c0, head_stride, m5, mt3, disp, stats, B, Dl, h,
+                    w, s, radius)
+    } else if (stats) {
         DISPATCH_NH(volume_mapping_stats_fwd, grid, block, 0, ecm_stream(stream), c0, head_stride, m5, mt3, disp, stats, B, Dl, h,
-                    w, s)
+                    w, s, radius)
     } else {
-        DISPATCH_NH(volume_mapping_fwd, grid, block, 0, ecm_stream(stream), c0, head_stride, m5, mt3, disp, stats, B, Dl, h, w, s)
+        DISPATCH_NH(volume_mapping_fwd, grid, block, 0, ecm_stream(stream), c0, head_stride, m5, mt3, disp, stats, B, Dl, h, w, s,
+                    radius)
     }
     return ECM_LAUNCH_RESULT();
 }
 
 static int launch_trilinear_fwd(const float* c0, long long head_stride, float* disp, float* stats, int nheads, int B, int Dl,
-                                int h, int w, int Do, int H, int W, void* stream) {
+                                int h, int w, int Do, int H, int W, int radius, void* stream) {
     const long long n = (long long)B * H * W;
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    if (stats) {
+    if (radius >= 0) {
+        DISPATCH_NH(trilinear_softargmin_mode_fwd, grid, block, 0, ecm_stream(stream), c0, head_stride, disp, stats, B, Dl, h, w,
+                    Do, H, W, radius)
+    } else if (stats) {
         DISPATCH_NH(trilinear_softargmin_stats_fwd, grid, block, 0, ecm_stream(stream), c0, head_stride, disp, stats, B, Dl, h, w,
-                    Do, H, W)
+                    Do, H, W, radius)
     } else {
         DISPATCH_NH(trilinear_softargmin_fwd, grid, block, 0, ecm_stream(stream), c0, head_stride, disp, stats, B, Dl, h, w, Do, H,
-                    W)
+                    W, radius)
     }
     return ECM_LAUNCH_RESULT();
 }
@@ -603,27 +666,42 @@ static int launch_trilinear_fwd(const float* c0, long long head_stride, float* d
 extern "C" int ecm_volume_mapping_fwd(const float* c0, long long head_stride, const float* m5, const float* mt3,
                                       float* disp, int nheads, int B, int Dl, int h, int w, int s, void* stream) {
     ECM_CHECK_ARG(c0 && m5 && mt3 && disp && B > 0 && Dl > 0 && h > 0 && w > 0 && s > 0);
-    return launch_volume_mapping_fwd(c0, head_stride, m5, mt3, disp, nullptr, nheads, B, Dl, h, w, s, stream);
+    return launch_volume_mapping_fwd(c0, head_stride, m5, mt3, disp, nullptr, nheads, B, Dl, h, w, s, -1, stream);
 }
 
 extern "C" int ecm_volume_mapping_stats_fwd(const float* c0, long long head_stride, const float* m5, const float* mt3,
                                             float* disp, float* stats, int nheads, int B, int Dl, int h, int w, int s,
                                             void* stream) {
     ECM_CHECK_ARG(c0 && m5 && mt3 && disp && stats && B > 0 && Dl > 0 && h > 0 && w > 0 && s > 0);
-    return launch_volume_mapping_fwd(c0, head_stride, m5, mt3, disp, stats, nheads, B, Dl, h, w, s, stream);
+    return launch_volume_mapping_fwd(c0, head_stride, m5, mt3, disp, stats, nheads, B, Dl, h, w, s, -1, stream);
+}
+
+// The modal estimate of the two heads: MODE 2 of the kernels above, so the logits are the heads' own.
+// The entry points stand here, beside the launchers; the eight-neighbour head's kernel is head_mode.hip.
+extern "C" int ecm_volume_mapping_mode_fwd(const float* c0, long long head_stride, const float* m5, const float* mt3,
+                                           float* modal, int nheads, int B, int Dl, int h, int w, int s, int radius,
+                                           void* stream) {
+    ECM_CHECK_ARG(c0 && m5 && mt3 && modal && B > 0 && Dl > 0 && h > 0 && w > 0 && s > 0 && radius >= 0);
+    return launch_volume_mapping_fwd(c0, head_stride, m5, mt3, nullptr, modal, nheads, B, Dl, h, w, s, radius, stream);
+}
+
+extern "C" int ecm_trilinear_softargmin_mode_fwd(const float* c0, long long head_stride, float* modal, int nheads, int B,
+                                                 int Dl, int h, int w, int Do, int H, int W, int radius, void* stream) {
+    ECM_CHECK_ARG(c0 && modal && B > 0 && Dl > 0 && h > 0 && w > 0 && Do > 0 && H > 0 && W > 0 && radius >= 0);
+    return launch_trilinear_fwd(c0, head_stride, nullptr, modal, nheads, B, Dl, h, w, Do, H, W, radius, stream);
 }
 
 extern "C" int ecm_trilinear_softargmin_fwd(const float* c0, long long head_stride, float* disp, int nheads, int B, int Dl,
                                             int h, int w, int Do, int H, int W, void* stream) {
     ECM_CHECK_ARG(c0 && disp && B > 0 && Dl > 0 && h > 0 && w > 0 && Do > 0 && H > 0 && W > 0);
-    return launch_trilinear_fwd(c0, head_stride, disp, nullptr, nheads, B, Dl, h, w, Do, H, W, stream);
+    return launch_trilinear_fwd(c0, head_stride, disp, nullptr, nheads, B, Dl, h, w, Do, H, W, -1, stream);
 }
 
 extern "C" int ecm_trilinear_softargmin_stats_fwd(const float* c0, long long head_stride, float* disp, float* stats,
                                                   int nheads, int B, int Dl, int h, int w, int Do, int H, int W,
                                                   void* stream) {
     ECM_CHECK_ARG(c0 && disp && stats && B > 0 && Dl > 0 && h > 0 && w > 0 && Do > 0 && H > 0 && W > 0);
-    return launch_trilinear_fwd(c0, head_stride, disp, stats, nheads, B, Dl, h, w, Do, H, W, stream);
+    return launch_trilinear_fwd(c0, head_stride, disp, stats, nheads, B, Dl, h, w, Do, H, W, -1, stream);
 }
 
 extern "C" long long ecm_volume_mapping_bwd_scratch_bytes(int nheads, int B, int Dl, int h, int w, int s) {

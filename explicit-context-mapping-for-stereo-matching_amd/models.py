@@ -595,6 +595,10 @@ class six_related_context_mapping(nn.Module):
 # What _ECMNet.predict returns: per requested head, the disparity and the standard deviation (pixels), peak probability and
 # entropy (nats) of the distribution whose mean it is; each field a tuple of [B,1,H,W] tensors.
 Prediction = collections.namedtuple("Prediction", "disparity std peak entropy")
+# ... and with predict(mode_radius=r): what to use where those say the mean cannot be trusted: the mean of
+# that distribution inside the window of r pixels about its highest level (`mode`, pixels), the window's share of the
+# distribution (`mass`) and the highest level itself (`index`, pixels).  The first four fields are Prediction's, bit for bit.
+ModalPrediction = collections.namedtuple("ModalPrediction", "disparity std peak entropy mode mass index")
 
 _NO_DISTRIBUTION = {
     "five": "the full-resolution disparity of this head is a sum of low-resolution disparities weighted by softmax * logit planes: "
@@ -604,6 +608,9 @@ _NO_DISTRIBUTION = {
 }
 
 
+_MODE_OP = {"eight": ops.ecm_aggregate9_mode, "volume": ops.volume_mapping_mode, "trilinear": ops.trilinear_softargmin_mode}
+
+
 class _ECMNet(nn.Module):
     """Shared skeleton of the registered architectures: encoder -> cost volume -> dres0/1 -> 1 or 3 hourglasses ->
     classifiers (`_aggregate`) -> head (`hot_path`).  Subclasses set ENCODER, HOURGLASSES and HEAD exactly as their reference
@@ -611,6 +618,7 @@ class _ECMNet(nn.Module):
     hourglass, the skips of the other two); True sums their gradients with one ops.fork kernel, False leaves the sum to
     autograd.  The two orders of summation differ in the last bit, so the attribute is part of each net's definition."""
     ENCODER, HOURGLASSES, HEAD, SIM2, PRE1_FORK = "cmfsm", 3, "eight", False, False
+    LEVEL_SPACING = 1      # full-resolution pixels between two levels of the head's distribution (a mode radius is a multiple)
 
     def __init__(self, maxdisp=192):
         super().__init__()
@@ -710,26 +718,35 @@ class _ECMNet(nn.Module):
         args = (c, self.maxdisp, *left.shape[-2:])
         return ops.trilinear_softargmin_stats(*args), args
 
-    def predict(self, left, right, heads=None):
+    def predict(self, left, right, heads=None, mode_radius=None):
         """One inference forward that also says how sure each disparity is: a Prediction whose .disparity, .std, .peak and
         .entropy are tuples of [B,1,H,W], one entry per head in `heads` (default: all three; the one-hourglass nets repeat
         their single head as forward does).  .disparity is bit-identical to forward's under torch.no_grad().  All classifiers
         run whatever `heads` says -- head k's logits are c_0 + ... + c_k -- and the head kernel is launched for all of them:
-        a launch for fewer heads is another template instantiation, which need not round like forward's.  Forward only."""
+        a launch for fewer heads is another template instantiation, which need not round like forward's.  Forward only.
+        With mode_radius = r (an integer >= 0 in full-resolution pixels, a multiple of LEVEL_SPACING) the result is a
+        ModalPrediction: the same four fields, bit for bit, plus .mode, .mass and .index of the window of r pixels about the
+        highest level of each head's distribution, from one more head kernel on the same logits."""
         if self.HEAD in _NO_DISTRIBUTION:                                # before any device work
             raise NotImplementedError(f"{type(self).__name__}.predict: {_NO_DISTRIBUTION[self.HEAD]}")
         heads = (0, 1, 2) if heads is None else tuple(int(k) for k in heads)
         if not heads or any(k < 0 or k > 2 for k in heads):
             raise ValueError(f"predict: heads {heads}: a non-empty selection of 0, 1, 2")
+        if mode_radius is not None:                                      # also before any device work
+            mode_radius = ops.check_mode_radius(mode_radius, self.LEVEL_SPACING)
         with torch.no_grad():
-            fields, _ = self.head_stats(left, right)
+            fields, args = self.head_stats(left, right)
+            kind = Prediction
+            if mode_radius is not None:
+                kind, fields = ModalPrediction, tuple(fields) + tuple(_MODE_OP[self.HEAD](*args, mode_radius))
         last = fields[0].shape[0] - 1
-        return Prediction(*(tuple(f[min(k, last)].unsqueeze(1) for k in heads) for f in fields))
+        return kind(*(tuple(f[min(k, last)].unsqueeze(1) for k in heads) for f in fields))
 
 
 class cmfsm(_ECMNet):
     """cmfsm.py:594-774.  forward(left, right) -> (pred1, pred2, pred3), each [B,1,H,W] in pixels."""
     ENCODER, HOURGLASSES, HEAD, PRE1_FORK = "cmfsm", 3, "eight", True
+    LEVEL_SPACING = 4      # the levels are the low-resolution disparities; eight_related_context_mapping exists at scale 4 only
 
     def hot_path(self, lr_l, hr_l, lr_r):
         """Everything after the encoder (cmfsm.py:659-774)."""

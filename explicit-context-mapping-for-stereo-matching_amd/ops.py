@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import contextlib as _contextlib
 import ctypes as C
+import numbers
 import os as _os
 
 import torch
@@ -502,6 +503,85 @@ def trilinear_softargmin_stats(c, Do, H, W):
     _lib.call("ecm_trilinear_softargmin_stats_fwd", _p(c), C.c_longlong(B * Dl * h * w), _p(disp), _p(stats), NH, B, Dl, h, w,
               Do, H, W, _stream())
     return _stats_planes(disp, stats)
+
+
+# ------------------------------------------------------------------------------------ modal disparity of the heads
+# DESIGN.md section 16.  Forward only: each op returns (mode, mass, index), every one [NH,B,H,W] and outside any graph, of the
+# distribution p whose mean the head returns: index the highest level of p in full-resolution pixels (lowest on an exact tie),
+# mass the share of p within `radius` pixels of it, mode p's mean inside that window.  The disparity itself is the plain op's.
+def check_mode_radius(radius, scale=1):
+    """radius as an int: a non-negative integer number of full-resolution pixels, a multiple of `scale` where the levels of p
+    are `scale` pixels apart (the eight-neighbour head)."""
+    if isinstance(radius, bool) or not isinstance(radius, numbers.Integral):
+        raise ValueError(f"mode radius {radius!r}: an integer number of full-resolution pixels")
+    radius = int(radius)
+    if radius < 0:
+        raise ValueError(f"mode radius {radius}: must be >= 0")
+    if radius % scale:
+        raise ValueError(f"mode radius {radius}: the levels of this head's distribution are {scale} pixels apart, so the radius "
+                         f"must be a multiple of {scale}")
+    return radius
+
+
+def _mode_planes(modal):
+    return modal[:, 0], modal[:, 1], modal[:, 2]
+
+
+@torch.no_grad()
+def ecm_aggregate9_mode(c, w9, scale, radius):
+    """(mode, mass, index) of each HR pixel's mixture of its valid neighbours' low-resolution distributions (the operands of
+    ecm_aggregate9_stats); radius must be a multiple of scale."""
+    scale = int(scale)
+    _chk(c, w9)
+    _need(c.dim() == 5 and c.numel() > 0 and scale >= 1, lambda: f"ecm_aggregate9_mode: c {tuple(c.shape)}, scale {scale}: want [heads,B,D,h,w]")
+    radius = check_mode_radius(radius, scale)
+    c, w9 = _c(c.detach()), _c(w9.detach())
+    NH, B, D, h, w = c.shape
+    H, W = h * scale, w * scale
+    _need(tuple(w9.shape) == (B, 9, H, W),
+          lambda: f"ecm_aggregate9_mode: w9 {tuple(w9.shape)} for c {tuple(c.shape)} at scale {scale}: want [B,9,h*scale,w*scale]")
+    d = torch.empty(NH, B, h, w, device=c.device, dtype=c.dtype)
+    lse = torch.empty(NH, B, h, w, device=c.device, dtype=c.dtype)
+    modal = torch.empty(NH, 3, B, H, W, device=c.device, dtype=c.dtype)
+    hs = C.c_longlong(B * D * h * w)
+    _lib.call("ecm_softargmin_heads_lse_fwd", _p(c), hs, _p(d), _p(lse), NH, B, D, h * w, _stream())
+    _lib.call("ecm_aggregate9_mode_fwd", _p(c), hs, _p(lse), _p(w9), _p(modal), NH, B, D, h, w, scale, radius, _stream())
+    return _mode_planes(modal)
+
+
+@torch.no_grad()
+def volume_mapping_mode(c, m5, mt3, scale, radius):
+    """(mode, mass, index) of volume_mapping's softmax over the Dl * scale fused logits."""
+    scale = int(scale)
+    _chk(c, m5, mt3)
+    _need(c.dim() == 5 and scale >= 1 and c.numel() > 0, lambda: f"volume_mapping_mode: c {tuple(c.shape)}, scale {scale}")
+    radius = check_mode_radius(radius)
+    c, m5, mt3 = _c(c.detach()), _c(m5.detach()), _c(mt3.detach())
+    NH, B, Dl, h, w = c.shape
+    H, W = h * scale, w * scale
+    _need(tuple(m5.shape) == (B, 5, H, W) and tuple(mt3.shape) == (B, 3, H, W),
+          lambda: f"volume_mapping_mode: m5 {tuple(m5.shape)} / mt3 {tuple(mt3.shape)} for c {tuple(c.shape)} at scale {scale}: "
+                  "want [B,5,h*scale,w*scale] and [B,3,h*scale,w*scale]")
+    modal = torch.empty(NH, 3, B, H, W, device=c.device, dtype=c.dtype)
+    _lib.call("ecm_volume_mapping_mode_fwd", _p(c), C.c_longlong(B * Dl * h * w), _p(m5), _p(mt3), _p(modal), NH, B, Dl, h, w,
+              scale, radius, _stream())
+    return _mode_planes(modal)
+
+
+@torch.no_grad()
+def trilinear_softargmin_mode(c, Do, H, W, radius):
+    """(mode, mass, index) of trilinear_softargmin's softmax over the Do interpolated logits."""
+    Do, H, W = int(Do), int(H), int(W)
+    _chk(c)
+    _need(c.dim() == 5 and c.numel() > 0 and Do >= 1 and H >= 1 and W >= 1,
+          lambda: f"trilinear_softargmin_mode: c {tuple(c.shape)} -> ({Do}, {H}, {W})")
+    radius = check_mode_radius(radius)
+    c = _c(c.detach())
+    NH, B, Dl, h, w = c.shape
+    modal = torch.empty(NH, 3, B, H, W, device=c.device, dtype=c.dtype)
+    _lib.call("ecm_trilinear_softargmin_mode_fwd", _p(c), C.c_longlong(B * Dl * h * w), _p(modal), NH, B, Dl, h, w, Do, H, W,
+              radius, _stream())
+    return _mode_planes(modal)
 
 
 # ------------------------------------------------------------------------------------ a5-a7 conv / deconv / GN

@@ -71,6 +71,17 @@ int ecm_aggregate9_bwd(const float* d, const float* w9, const float* gout, float
  * stats: [nheads,3,B,H,W] = s * standard deviation of p about its own mean (full-resolution pixels), max_d p, entropy (nats). */
 int ecm_aggregate9_stats_fwd(const float* c0, long long head_stride, const float* lse, const float* w9, float* stats,
                              int nheads, int B, int D, int h, int w, int s, void* stream);
+/* ABI 9: the modal disparity of the same mixture p, L = D levels spaced u = s full-resolution pixels.
+ * radius >= 0 is in full-resolution pixels and a multiple of s (else ECM_EINVAL); r = radius / s.
+ * modal: [nheads,3,B,H,W] = (mode, mass, index):
+ *   index = s * D*, D* = argmax_d p(d), the lowest d winning an exact tie (a float plane of exact integers);
+ *   mass  = sum_{d in Wn} p(d), clamped to <= 1, Wn = {d : |d - D*| <= r, 0 <= d < D};
+ *   mode  = s * (D* + sum_{Wn} p(d) (d - D*) / sum_{Wn} p(d)), formed centred on D*.
+ * The border factor sum_valid w9 of the head's output is not applied (as for std above).  A NaN logit in a pixel's valid
+ * neighbourhood makes all three planes NaN there.  Any D works (the levels are staged through LDS in chunks of at most 48);
+ * ECM_EUNSUP for nheads outside 1..3 or B > 65535.  Writes only `modal`: the disparity is ecm_aggregate9_fwd's. */
+int ecm_aggregate9_mode_fwd(const float* c0, long long head_stride, const float* lse, const float* w9, float* modal,
+                            int nheads, int B, int D, int h, int w, int s, int radius, void* stream);
 
 /* ---- a3: eight-related context-mapping weights (cmfsm.py:431-593, 304-358, 391-428) ----------
  * lr: [B,32,h,w]; hr: [B,32,H,W]; W0 [32,66], W1 [16,32], W2 [8,16], W3 [1,8] (1x1 conv weights, no bias);
@@ -113,6 +124,12 @@ int ecm_volume_mapping_fwd(const float* c0, long long head_stride, const float* 
  * (nats) of the softmax over D whose mean is disp; disp is bit-identical to ecm_volume_mapping_fwd's. */
 int ecm_volume_mapping_stats_fwd(const float* c0, long long head_stride, const float* m5, const float* mt3, float* disp,
                                  float* stats, int nheads, int B, int Dl, int h, int w, int s, void* stream);
+/* ABI 9: the modal disparity of that softmax p over the L = Dl*s fused logits, u = 1, r = radius >= 0.
+ * modal: [nheads,3,B,H,W] = (mode, mass, index): index = D* = argmax_D p(D), the lowest D winning an exact tie;
+ * mass = sum_{|D - D*| <= r} p(D) <= 1; mode = D* + sum_W p(D) (D - D*) / sum_W p(D), centred on D*.  A NaN logit in the pixel's
+ * support makes all three NaN.  The parent's operands and refusals; writes only `modal`. */
+int ecm_volume_mapping_mode_fwd(const float* c0, long long head_stride, const float* m5, const float* mt3, float* modal,
+                                int nheads, int B, int Dl, int h, int w, int s, int radius, void* stream);
 /* Gradients of c (same packing), m5 and mt3 from gdisp [nheads,B,H,W]; s must be a power of two <= 64.  Deterministic:
  * every sum is taken in a fixed order (per-row partial sums in `scratch`, gathered by a second kernel; no float atomics),
  * every output element is written exactly once. */
@@ -128,6 +145,10 @@ int ecm_trilinear_softargmin_fwd(const float* c0, long long head_stride, float* 
 /* ABI 8: with stats [nheads,3,B,H,W] as ecm_volume_mapping_stats_fwd; disp bit-identical to ecm_trilinear_softargmin_fwd's. */
 int ecm_trilinear_softargmin_stats_fwd(const float* c0, long long head_stride, float* disp, float* stats,
                                        int nheads, int B, int Dl, int h, int w, int Do, int H, int W, void* stream);
+/* ABI 9: modal [nheads,3,B,H,W] = (mode, mass, index) of the softmax over the Do interpolated logits, defined as for
+ * ecm_volume_mapping_mode_fwd (L = Do, u = 1, r = radius >= 0); writes only `modal`. */
+int ecm_trilinear_softargmin_mode_fwd(const float* c0, long long head_stride, float* modal, int nheads, int B, int Dl,
+                                      int h, int w, int Do, int H, int W, int radius, void* stream);
 /* Deterministic (per-pixel plane gradients in `scratch`, then separable fixed-order reductions along x and y). */
 long long ecm_trilinear_softargmin_bwd_scratch_bytes(int nheads, int B, int Dl, int h, int w, int H, int W);
 int ecm_trilinear_softargmin_bwd(const float* c0, long long head_stride, const float* gdisp, float* gc0,

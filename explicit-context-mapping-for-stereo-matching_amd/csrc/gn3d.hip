@@ -928,28 +928,32 @@ struct GnControl {
     // Two cluster launches that run CONCURRENTLY (two streams of one process) can starve each other: each keeps workgroups
     // resident that wait for cluster members the other launch's waiting workgroups leave no room for -- both then sit in
     // their bounded waits (found in round 4 by replaying two captured graphs on two streams: ~85 launches x 2 s).  Cluster
-    // launches of one process are therefore ORDERED across streams on the host.  As long as every cluster launch of a device
-    // comes from one stream nothing is done.  The first launch from another stream waits for the device to drain once (the
-    // earlier stream may no longer exist -- HIP aborts on a stale handle, so it is never touched again) and switches the
-    // device to multi-stream mode: from then on an event is recorded behind every cluster launch and a launch on a stream
-    // other than the previous one's waits for it.  `launch_mu` keeps [wait, launch, record] atomic between threads.  A
-    // stream that is being captured into a graph never takes the cluster kernels at all (no such ordering can be recorded
-    // against streams outside the capture): it gets the two-stage ones.
+    // launches of one process are therefore ORDERED across streams, through ONE event per device (created at the device's
+    // first cluster launch): every launch makes its stream wait for the event -- i.e. for the previous cluster launch of the
+    // device, whichever stream that was on -- and records the event behind its kernel.  A wait for an event recorded on the
+    // same stream orders nothing the stream did not order already, and one for an event whose recording stream has since been
+    // destroyed is legal: no stream handle is kept or compared, the only one ever touched is the live one being launched on.
+    // Correct and legal, not free: 3-6 us more per cluster launch than without the two calls, ~0.1 % of a training step
+    // (measured).  `launch_mu` keeps [wait, launch, record] atomic between threads.  No event to be had
+    // (creation failed, device index beyond MAX_DEV) = no cluster kernels (two-stage path).  A stream that
+    // is being captured into a graph takes no part in this (no ordering can be recorded against streams outside the capture):
+    // it gets the two-stage kernels, or with mode 4 the cluster kernels on the caller's promise.
     std::mutex launch_mu;
     static constexpr int MAX_DEV = 32;
-    hipStream_t last_stream[MAX_DEV] = {};
-    bool have_last[MAX_DEV] = {};
-    bool multi[MAX_DEV] = {};
     hipEvent_t order_ev[MAX_DEV] = {};
+    bool order_recorded[MAX_DEV] = {};
 };
 GnControl& gn_ctl() { static GnControl c; return c; }
 
+void gn_ctl_env_locked(GnControl& c) {
+    if (c.env_read) return;
+    c.env_read = true;
+    if (const char* m = getenv("ECM_GN_CLUSTER_MODE")) c.mode = atoi(m);
+    if (const char* p = getenv("ECM_GN_POLL_MS")) { const long long ms = atoll(p); if (ms > 0) c.poll_ticks = (unsigned long long)ms * 100000ull; }
+}
+
 int gn_ctl_init_locked(GnControl& c) {
-    if (!c.env_read) {
-        c.env_read = true;
-        if (const char* m = getenv("ECM_GN_CLUSTER_MODE")) c.mode = atoi(m);
-        if (const char* p = getenv("ECM_GN_POLL_MS")) { const long long ms = atoll(p); if (ms > 0) c.poll_ticks = (unsigned long long)ms * 100000ull; }
-    }
+    gn_ctl_env_locked(c);
     if (!c.status_host) {
         void* h = nullptr;
         hipError_t e = hipHostMalloc(&h, 64, hipHostMallocMapped | hipHostMallocPortable);
@@ -964,119 +968,73 @@ int gn_ctl_init_locked(GnControl& c) {
     return 0;
 }
 
-// Launch helpers of the fused kernels; -100 = the shape (or the mode) needs the two-stage path.
-struct FusedLaunch { FusedGeom g; FusedCtl ctl; int rc; };
+// f(std::integral_constant<int, v>) for the run-time v in [0, N): where a flag or a mask becomes a template argument
+template <int N, class F>
+inline int with_const(int v, F&& f) {
+    if constexpr (N > 1) { if (v != N - 1) return with_const<N - 1>(v, f); }
+    return f(std::integral_constant<int, N - 1>{});
+}
 
-inline FusedLaunch fused_prepare(float* scratch, bool preset, int B, int C, long long S, int maxv4, int resident, hipStream_t st) {
-    FusedLaunch L{};
+// The one launcher of the cluster kernels; -100 = the shape, the mode or the device needs the two-stage path.  `resident` caches
+// the kernel's occupancy query (one per instantiation); `launch(grid, ctl, g)` issues the kernel with its own argument list.
+template <class K, class L>
+int launch_fused(K kern, int lds, int maxv4, int& resident, hipStream_t st, float* scratch, bool preset, int B, int C,
+                 long long S, L&& launch) {
     GnControl& c = gn_ctl();
+    FusedCtl ctl{};
     int mode;
     {
         std::lock_guard<std::mutex> lock(c.mu);
-        L.rc = gn_ctl_init_locked(c);
-        if (L.rc) return L;
+        if (const int rc = gn_ctl_init_locked(c)) return rc;
         mode = c.mode;
-        L.ctl.status = c.status_dev;
-        L.ctl.poll_ticks = c.poll_ticks;
+        ctl.status = c.status_dev;
+        ctl.poll_ticks = c.poll_ticks;
     }
-    L.rc = -100;
-    if (mode == 0) return L;
-    L.g = fused_geom(B, C, S, maxv4, resident);
-    if (!L.g.ok) return L;
-    if (mode == 2) L.g.grid -= L.g.grid % L.g.cl;                    // static ids: whole clusters only
-    if (mode == 3) L.g.grid = L.g.cl > 1 ? L.g.cl - 1 : 1;           // fault injection: a cluster can never be complete
-    if (mode == 3 && L.g.cl == 1) return L;
-    {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        bool capturing = false;
-        if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
-        else capturing = cs != hipStreamCaptureStatusNone;
-        // captured: two-stage kernels (see GnControl) -- unless the caller has promised, with mode 4, that graphs holding cluster
-        // launches are never replayed concurrently with each other or with eager GroupNorm work (no ordering can be recorded)
-        if (capturing && mode != 4) return L;
-        int dev = 0;
-        if (!capturing && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < GnControl::MAX_DEV) {   // (launch_mu is held by the caller)
-            if (c.have_last[dev] && c.last_stream[dev] != st) {
-                if (!c.multi[dev]) {
-                    c.multi[dev] = true;
-                    if (hipDeviceSynchronize() != hipSuccess) (void)hipGetLastError();
-                    if (hipEventCreateWithFlags(&c.order_ev[dev], hipEventDisableTiming) != hipSuccess) {
-                        c.order_ev[dev] = nullptr;
-                        (void)hipGetLastError();
-                    }
-                } else if (c.order_ev[dev]) {
-                    if (hipStreamWaitEvent(st, c.order_ev[dev], 0) != hipSuccess) (void)hipGetLastError();
-                }
-            }
-            c.last_stream[dev] = st;
-            c.have_last[dev] = true;
+    if (mode == 0) return -100;                                  // before launch_mu, the LDS attribute and any device query
+    std::lock_guard<std::mutex> order(c.launch_mu);
+    if (lds > 0 && ecm_allow_lds(reinterpret_cast<const void*>(kern), lds) != hipSuccess) { (void)hipGetLastError(); return -100; }
+    if (resident < 0) resident = resident_workgroups(kern, lds);
+    FusedGeom g = fused_geom(B, C, S, maxv4, resident);
+    if (!g.ok) return -100;
+    if (mode == 2) g.grid -= g.grid % g.cl;                      // static ids: whole clusters only
+    if (mode == 3) {                                             // fault injection: a cluster can never be complete
+        if (g.cl == 1) return -100;
+        g.grid = g.cl - 1;
+    }
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
+    // captured: two-stage kernels (see GnControl) -- unless the caller has promised, with mode 4, that graphs holding cluster
+    // launches are never replayed concurrently with each other or with eager GroupNorm work (no ordering can be recorded)
+    const bool capturing = cs != hipStreamCaptureStatusNone;
+    if (capturing && mode != 4) return -100;
+    int dev = -1;
+    if (!capturing) {                                            // behind the device's previous cluster launch (see GnControl)
+        bool ok = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < GnControl::MAX_DEV;
+        if (ok && !c.order_ev[dev]) {
+            hipEvent_t ev = nullptr;
+            ok = hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
+            if (ok) c.order_ev[dev] = ev;
         }
+        if (ok && c.order_recorded[dev]) ok = hipStreamWaitEvent(st, c.order_ev[dev], 0) == hipSuccess;
+        if (!ok) { (void)hipGetLastError(); return -100; }
     }
-    L.ctl.dynamic = mode == 2 ? 0 : 1;
-    L.ctl.slots = reinterpret_cast<unsigned long long*>(scratch);
-    const size_t nslots = (size_t)L.g.nspans * L.g.cl;
-    L.ctl.ticket = reinterpret_cast<unsigned*>(L.ctl.slots + nslots);
-    L.ctl.done = L.ctl.ticket + 4;
-    L.rc = 0;
+    ctl.dynamic = mode == 2 ? 0 : 1;
+    ctl.slots = reinterpret_cast<unsigned long long*>(scratch);
+    const size_t nslots = (size_t)g.nspans * g.cl;
+    ctl.ticket = reinterpret_cast<unsigned*>(ctl.slots + nslots);
+    ctl.done = ctl.ticket + 4;
     if (!preset) {
         // one memset presets the slots to EMPTY, the ticket counter to 0xFFFFFFFF (first draw wraps to ticket 0) and the
         // spans' `done` words; exchange memory kept by the caller (ecm_gn3d_*_p) is in that state already
-        const hipError_t e = hipMemsetAsync(L.ctl.slots, 0xff, nslots * sizeof(unsigned long long) + 16 + (size_t)L.g.nspans * 4, st);
-        L.rc = e == hipSuccess ? 0 : (int)e;
+        const hipError_t e = hipMemsetAsync(ctl.slots, 0xff, nslots * sizeof(unsigned long long) + 16 + (size_t)g.nspans * 4, st);
+        if (e != hipSuccess) return (int)e;
     }
-    return L;
-}
-
-// behind a cluster launch (launch_mu held): in multi-stream mode, the event the next launch on another stream waits for
-inline void fused_launched(hipStream_t st) {
-    GnControl& c = gn_ctl();
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return; }
-    if (cs != hipStreamCaptureStatusNone) return;           // (mode 4: a captured cluster launch takes no part in the ordering)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= GnControl::MAX_DEV || !c.multi[dev]) return;
-    if (!c.order_ev[dev]) {                                 // creation failed earlier: fall back to draining the device
-        (void)hipDeviceSynchronize();
-        return;
+    launch(dim3(g.grid), ctl, g);
+    int rc = ECM_LAUNCH_RESULT();
+    if (!capturing) {
+        if (hipEventRecord(c.order_ev[dev], st) == hipSuccess) c.order_recorded[dev] = true;
+        else if (const int e = ECM_LAUNCH_RESULT(); !rc) rc = e;  // the next launch could not be ordered behind this one
     }
-    if (hipEventRecord(c.order_ev[dev], st) != hipSuccess) (void)hipGetLastError();
-}
-
-template <bool RELU, bool SKIP>
-int launch_fused_fwd(const float* x, const float* gamma, const float* beta, const float* skip, float* y, float* mean_rstd,
-                     float* scratch, bool preset, int B, int C, long long S, float eps, hipStream_t st) {
-    auto kern = gn_fused_fwd<RELU, SKIP>;
-    constexpr int MAXV4 = SKIP ? FWDS_MAXV4 : FWD_MAXV4;
-    constexpr int lds = (STASH_V4 < MAXV4 ? STASH_V4 : MAXV4) * THREADS * 16;
-    static int resident = -1;
-    std::lock_guard<std::mutex> order(gn_ctl().launch_mu);
-    if (lds > 0 && ecm_allow_lds(reinterpret_cast<const void*>(kern), lds) != hipSuccess) return ECM_EINVAL;
-    if (resident < 0) resident = resident_workgroups(kern, lds);
-    const FusedLaunch L = fused_prepare(scratch, preset, B, C, S, MAXV4, resident, st);
-    if (L.rc) return L.rc;
-    hipLaunchKernelGGL(kern, dim3(L.g.grid), dim3(THREADS), lds, st, x, gamma, beta, skip, y, mean_rstd, L.ctl, C,
-                       S, L.g.cpg, L.g.wpc, L.g.nspans, L.g.v4_per_wg, eps);
-    const int rc = ECM_LAUNCH_RESULT();
-    fused_launched(st);
-    return rc;
-}
-
-template <int MASK, int GSKIP>
-int launch_fused_bwd(const float* x, const float* mean_rstd, const float* gamma, const float* beta, const float* y,
-                     const float* gy, float* gx, float* gskip, float* chan, float* scratch, bool preset, int B, int C, long long S,
-                     hipStream_t st) {
-    auto kern = gn_fused_bwd<MASK, GSKIP>;
-    constexpr int lds = bwd_stash_v4(MASK, GSKIP) * THREADS * 16;
-    static int resident = -1;
-    std::lock_guard<std::mutex> order(gn_ctl().launch_mu);
-    if (lds > 0 && ecm_allow_lds(reinterpret_cast<const void*>(kern), lds) != hipSuccess) return ECM_EINVAL;
-    if (resident < 0) resident = resident_workgroups(kern, lds);
-    const FusedLaunch L = fused_prepare(scratch, preset, B, C, S, BWD_MAXV4, resident, st);
-    if (L.rc) return L.rc;
-    hipLaunchKernelGGL(kern, dim3(L.g.grid), dim3(THREADS), lds, st, x, mean_rstd, gamma, beta, y, gy, gx, gskip,
-                       chan, L.ctl, C, S, L.g.cpg, L.g.wpc, L.g.nspans, L.g.v4_per_wg);
-    const int rc = ECM_LAUNCH_RESULT();
-    fused_launched(st);
     return rc;
 }
 
@@ -1100,7 +1058,7 @@ extern "C" int ecm_gn3d_profile(unsigned long long* out4, int reset) {
 extern "C" int ecm_gn3d_cluster_mode(int mode) {
     GnControl& c = gn_ctl();
     std::lock_guard<std::mutex> lock(c.mu);
-    c.env_read = true;                       // an explicit call overrides the environment preset
+    gn_ctl_env_locked(c);                    // an explicit call overrides the environment preset; a query reports it
     const int old = c.mode;
     if (mode >= 0 && mode <= 4) c.mode = mode;
     return old;
@@ -1109,6 +1067,7 @@ extern "C" int ecm_gn3d_cluster_mode(int mode) {
 extern "C" int ecm_gn3d_poll_ms(int ms) {
     GnControl& c = gn_ctl();
     std::lock_guard<std::mutex> lock(c.mu);
+    gn_ctl_env_locked(c);
     const int old = (int)(c.poll_ticks / 100000ull);
     if (ms > 0) c.poll_ticks = (unsigned long long)ms * 100000ull;
     return old;
@@ -1135,11 +1094,16 @@ int gn_fwd_impl(const float* x, const float* gamma, const float* beta, const flo
     if (scratch_bytes < ecm_gn3d_scratch_bytes(B, C, S)) return ECM_ESCRATCH;
     if (const int pe = gn_pending_error()) return pe;
     hipStream_t st = ecm_stream(stream);
-    int rc;
-    if (relu && skip) rc = launch_fused_fwd<true, true>(x, gamma, beta, skip, y, mean_rstd, cluster, preset, B, C, S, eps, st);
-    else if (relu) rc = launch_fused_fwd<true, false>(x, gamma, beta, skip, y, mean_rstd, cluster, preset, B, C, S, eps, st);
-    else if (skip) rc = launch_fused_fwd<false, true>(x, gamma, beta, skip, y, mean_rstd, cluster, preset, B, C, S, eps, st);
-    else rc = launch_fused_fwd<false, false>(x, gamma, beta, skip, y, mean_rstd, cluster, preset, B, C, S, eps, st);
+    int rc = with_const<2>(relu != 0, [&](auto R) { return with_const<2>(skip != nullptr, [&](auto K) {
+        const auto kern = gn_fused_fwd<R(), K()>;
+        constexpr int MAXV4 = K() ? FWDS_MAXV4 : FWD_MAXV4;
+        constexpr int lds = (STASH_V4 < MAXV4 ? STASH_V4 : MAXV4) * THREADS * 16;
+        static int resident = -1;                                // (one per instantiation of this lambda)
+        return launch_fused(kern, lds, MAXV4, resident, st, cluster, preset, B, C, S, [&](dim3 grid, const FusedCtl& ctl, const FusedGeom& g) {
+            hipLaunchKernelGGL(kern, grid, dim3(THREADS), lds, st, x, gamma, beta, skip, y, mean_rstd, ctl, C, S, g.cpg, g.wpc,
+                               g.nspans, g.v4_per_wg, eps);
+        });
+    }); });
     if (rc != -100) return rc;
     rc = launch_stats(x, mean_rstd, scratch, scratch_bytes, B, C, S, eps, stream);
     if (rc) return rc;
@@ -1156,37 +1120,34 @@ int gn_bwd_impl(const float* x, const float* mean_rstd, const float* gamma, cons
     if (const int pe = gn_pending_error()) return pe;
     const int mask = !relu ? 0 : (y ? 1 : 2);
     hipStream_t st = ecm_stream(stream);
-    float* sc = static_cast<float*>(scratch);
-    {
-        float* chan = chan_fused;
-        int rc;
-        if (mask == 0) rc = gskip ? launch_fused_bwd<0, 1>(x, mean_rstd, gamma, beta, y, gy, gx, gskip, chan, cluster, preset, B, C, S, st)
-                                  : launch_fused_bwd<0, 0>(x, mean_rstd, gamma, beta, y, gy, gx, gskip, chan, cluster, preset, B, C, S, st);
-        else if (mask == 1) rc = gskip ? launch_fused_bwd<1, 1>(x, mean_rstd, gamma, beta, y, gy, gx, gskip, chan, cluster, preset, B, C, S, st)
-                                       : launch_fused_bwd<1, 0>(x, mean_rstd, gamma, beta, y, gy, gx, gskip, chan, cluster, preset, B, C, S, st);
-        else rc = gskip ? launch_fused_bwd<2, 1>(x, mean_rstd, gamma, beta, y, gy, gx, gskip, chan, cluster, preset, B, C, S, st)
-                        : launch_fused_bwd<2, 0>(x, mean_rstd, gamma, beta, y, gy, gx, gskip, chan, cluster, preset, B, C, S, st);
+    return with_const<3>(mask, [&](auto M) {
+        constexpr int MASK = M();
+        const int rc = with_const<2>(gskip != nullptr, [&](auto G) {
+            const auto kern = gn_fused_bwd<MASK, G()>;
+            constexpr int lds = bwd_stash_v4(MASK, G()) * THREADS * 16;
+            static int resident = -1;                            // (one per instantiation of this lambda)
+            return launch_fused(kern, lds, BWD_MAXV4, resident, st, cluster, preset, B, C, S, [&](dim3 grid, const FusedCtl& ctl, const FusedGeom& g) {
+                hipLaunchKernelGGL(kern, grid, dim3(THREADS), lds, st, x, mean_rstd, gamma, beta, y, gy, gx, gskip, chan_fused, ctl,
+                                   C, S, g.cpg, g.wpc, g.nspans, g.v4_per_wg);
+            });
+        });
         if (rc == 0) {
-            hipLaunchKernelGGL(gn_bwd_params, dim3((C + 63) / 64), dim3(64), 0, st, chan, ggamma, gbeta, B, C);
+            hipLaunchKernelGGL(gn_bwd_params, dim3((C + 63) / 64), dim3(64), 0, st, chan_fused, ggamma, gbeta, B, C);
             return ECM_LAUNCH_RESULT();
         }
         if (rc != -100) return rc;
-    }
-    const int nchunks = chunks_of(S);
-    float* part = sc;
-    float* chan = part + (size_t)B * C * nchunks * 2;
-    dim3 g1(nchunks, B * C), block(THREADS);
-    if (mask == 0) hipLaunchKernelGGL(gn_bwd_partial<0>, g1, block, 0, st, x, mean_rstd, gamma, beta, y, gy, gskip, part, C, S, nchunks);
-    else if (mask == 1) hipLaunchKernelGGL(gn_bwd_partial<1>, g1, block, 0, st, x, mean_rstd, gamma, beta, y, gy, gskip, part, C, S, nchunks);
-    else hipLaunchKernelGGL(gn_bwd_partial<2>, g1, block, 0, st, x, mean_rstd, gamma, beta, y, gy, gskip, part, C, S, nchunks);
-    hipLaunchKernelGGL(gn_bwd_final_chan, dim3((B * C + 63) / 64), dim3(64), 0, st, part, chan, B * C, nchunks);
-    hipLaunchKernelGGL(gn_bwd_params, dim3((C + 63) / 64), dim3(64), 0, st, chan, ggamma, gbeta, B, C);
-    long long per = (S + THREADS * 4 - 1) / (THREADS * 4);
-    dim3 g2((int)(per < 64 ? per : 64), B * C);
-    if (mask == 0) hipLaunchKernelGGL(gn_bwd_apply<0>, g2, block, 0, st, x, mean_rstd, gamma, beta, y, gy, chan, gx, C, S);
-    else if (mask == 1) hipLaunchKernelGGL(gn_bwd_apply<1>, g2, block, 0, st, x, mean_rstd, gamma, beta, y, gy, chan, gx, C, S);
-    else hipLaunchKernelGGL(gn_bwd_apply<2>, g2, block, 0, st, x, mean_rstd, gamma, beta, y, gy, chan, gx, C, S);
-    return ECM_LAUNCH_RESULT();
+        const int nchunks = chunks_of(S);
+        float* part = static_cast<float*>(scratch);
+        float* chan = part + (size_t)B * C * nchunks * 2;
+        dim3 g1(nchunks, B * C), block(THREADS);
+        hipLaunchKernelGGL(gn_bwd_partial<MASK>, g1, block, 0, st, x, mean_rstd, gamma, beta, y, gy, gskip, part, C, S, nchunks);
+        hipLaunchKernelGGL(gn_bwd_final_chan, dim3((B * C + 63) / 64), dim3(64), 0, st, part, chan, B * C, nchunks);
+        hipLaunchKernelGGL(gn_bwd_params, dim3((C + 63) / 64), dim3(64), 0, st, chan, ggamma, gbeta, B, C);
+        long long per = (S + THREADS * 4 - 1) / (THREADS * 4);
+        dim3 g2((int)(per < 64 ? per : 64), B * C);
+        hipLaunchKernelGGL(gn_bwd_apply<MASK>, g2, block, 0, st, x, mean_rstd, gamma, beta, y, gy, chan, gx, C, S);
+        return ECM_LAUNCH_RESULT();
+    });
 }
 }  // namespace
 

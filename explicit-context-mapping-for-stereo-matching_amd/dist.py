@@ -332,7 +332,8 @@ class GraphedForward:
         """`cluster_groupnorm`: capture the one-pass (cluster) GroupNorm kernels instead of the two-stage ones a capturing
         stream gets by default.  One read pass less per GroupNorm; only for a graph that is never replayed concurrently with
         another graph or with eager GroupNorm work on another stream (two cluster launches in flight together starve each
-        other: csrc/gn3d.hip, GnControl)."""
+        other: csrc/gn3d.hip, GnControl).  A process that has chosen the two-stage kernels (`ops.gn_cluster_mode(0)`: it shares its
+        device) keeps them in the capture as well."""
         assert left.is_cuda and right.is_cuda, "GraphedForward captures a HIP graph: GPU tensors only"
         self.model = model.eval()
         self.left, self.right = left.clone(), right.clone()
@@ -345,13 +346,14 @@ class GraphedForward:
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         from . import ops
-        old = ops.gn_cluster_mode(4) if cluster_groupnorm else None      # matters at capture time only: which kernels are recorded
+        old = ops.gn_cluster_mode(-1)
+        if cluster_groupnorm and old != 0:                   # matters at capture time only: which kernels are recorded
+            ops.gn_cluster_mode(4)
         try:
             with torch.no_grad(), torch.cuda.graph(self.graph):
                 self.out = self.model(self.left, self.right)
         finally:
-            if old is not None:
-                ops.gn_cluster_mode(old)
+            ops.gn_cluster_mode(old)
 
     def __call__(self, left: torch.Tensor, right: torch.Tensor):
         self.left.copy_(left)

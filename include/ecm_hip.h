@@ -328,7 +328,10 @@ int ecm_gn3d_apply_bf16_f32(const unsigned short* x, const float* mean_rstd, con
  *     cluster launches of one process are otherwise ordered across streams by the library -- mode 4 is the caller's promise
  *     that such graphs replay one at a time); any other value only queries.  Returns the previous mode.  Env
  *     ECM_GN_CLUSTER_MODE presets it.
- *   ecm_gn3d_poll_ms(ms): wait bound in milliseconds (default 2000; ms <= 0 only queries).  Returns the previous bound. */
+ *   ecm_gn3d_poll_ms(ms): wait bound in milliseconds (default 2000; ms <= 0 only queries).  Returns the previous bound.  Env
+ *     ECM_GN_POLL_MS presets it.
+ *   Both read their environment preset at the first call of either, or at the first GroupNorm launch, whichever comes first:
+ *   a query as the very first call reports the preset, and a value set by a call is never replaced by the preset later. */
 int ecm_gn3d_cluster_mode(int mode);
 int ecm_gn3d_poll_ms(int ms);
 int ecm_async_status(int clear);

@@ -53,6 +53,45 @@ def test_groupnorm_two_streams_concurrently(ecm):
             torch.testing.assert_close(gx, refs[i][1], rtol=1e-3, atol=1e-4)
 
 
+def test_cluster_launches_survive_stream_lifetimes(ecm):
+    """Cluster launches are ordered across streams through one event per device, never through stream handles: streams that
+    come and go (a new stream may get a destroyed one's handle) change nothing.  Forward + backward on a stream that is then
+    dropped, on a fresh one, on the default stream and on six short-lived ones: every result bit-equal to the first, equal
+    to F.group_norm, and no cluster wait expired."""
+    from test_hip_groupnorm_fp64 import TWO_STAGE, geoms
+    shape = (1, 64, 8, 48, 96)
+    g = geoms(shape, torch.cuda.get_device_properties(0).multi_processor_count)
+    assert TWO_STAGE not in g.values() and g["fwd"][2] == 4, g      # the cluster kernels, 4 workgroups per cluster forward
+    x, gm, bt = _case(11, shape)
+    gy = torch.randn(shape, device="cuda", generator=torch.Generator(device="cuda").manual_seed(12))
+    xr = x.clone().requires_grad_()
+    ref = F.relu(F.group_norm(xr, 32, gm, bt, 1e-5))
+    ref.backward(gy)
+    torch.cuda.synchronize()
+
+    def run(stream):
+        with torch.cuda.stream(stream):
+            xg = x.clone().requires_grad_()
+            y = ecm.ops.group_norm_act(xg, gm, bt, None, True)
+            y.backward(gy)
+        return y.detach(), xg.grad
+
+    a = torch.cuda.Stream()
+    outs = [run(a)]
+    a.synchronize()
+    del a
+    outs.append(run(torch.cuda.Stream()))
+    outs.append(run(torch.cuda.current_stream()))
+    for _ in range(3):
+        for _ in range(2):
+            outs.append(run(torch.cuda.Stream()))
+    ecm.ops.check_async_errors()                       # synchronises; raises if any bounded wait expired
+    for y, gx in outs:
+        assert torch.equal(y, outs[0][0]) and torch.equal(gx, outs[0][1])
+    torch.testing.assert_close(outs[0][0], ref.detach(), rtol=1e-4, atol=1e-5)
+    torch.testing.assert_close(outs[0][1], xr.grad, rtol=1e-3, atol=1e-4)
+
+
 def test_groupnorm_two_stage_mode_matches(ecm):
     """ecm_gn3d_cluster_mode(0) routes to the two-stage kernels (no inter-workgroup waits): same values."""
     x, gm, bt = _case(7, (1, 64, 8, 48, 96))

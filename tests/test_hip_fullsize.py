@@ -152,6 +152,7 @@ def test_graphed_forward_matches_eager(ecm):
         ecm.ops.gn_cluster_mode(old)
     for x, y in zip(got, want):
         assert torch.equal(x, y)
+    want0 = want
     with torch.no_grad():            # ... and against the default (cluster) kernels at the end-to-end tolerance
         want = hot(a, b)
     for x, y in zip(got, want):
@@ -163,6 +164,22 @@ def test_graphed_forward_matches_eager(ecm):
     assert ecm.ops.gn_cluster_mode(-1) == before
     got = [t.clone() for t in gc(a, b)]
     for x, y in zip(got, want):
+        assert torch.equal(x, y)
+    ecm.ops.check_async_errors()
+    # ... but a process that has chosen the two-stage kernels (mode 0: it shares its device) keeps them in such a capture too:
+    # mode 4 is never set, the graph equals the eager mode-0 result bit for bit, and mode 0 is still set afterwards
+    seen = []
+    hook = hot.register_forward_pre_hook(lambda *_: seen.append(ecm.ops.gn_cluster_mode(-1)))
+    old = ecm.ops.gn_cluster_mode(0)
+    try:
+        g0 = dist.GraphedForward(hot, *feats(), cluster_groupnorm=True)
+        assert ecm.ops.gn_cluster_mode(-1) == 0
+        got = [t.clone() for t in g0(a, b)]
+    finally:
+        ecm.ops.gn_cluster_mode(old)
+        hook.remove()
+    assert len(seen) >= 2 and set(seen) == {0}, seen       # warm-up forwards and the captured one
+    for x, y in zip(got, want0):
         assert torch.equal(x, y)
     ecm.ops.check_async_errors()
 

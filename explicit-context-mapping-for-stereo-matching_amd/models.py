@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import collections
 import math
+import numbers
 import os as _os
 
 import torch
@@ -600,6 +601,11 @@ Prediction = collections.namedtuple("Prediction", "disparity std peak entropy")
 # distribution (`mass`) and the highest level itself (`index`, pixels).  The first four fields are Prediction's, bit for bit.
 ModalPrediction = collections.namedtuple("ModalPrediction", "disparity std peak entropy mode mass index")
 
+# What _ECMNet.cross_check returns, each field [B,1,H,W]: one head's disparity of the left view and of
+# the right view (in right-image coordinates), the left-right error (pixels), the failure class (0 consistent, 1 occluded,
+# 2 mismatch, 3 out of view; a float plane) and the left disparity with the failures filled from the background.
+CrossCheck = collections.namedtuple("CrossCheck", "disparity disparity_right error kind filled")
+
 _NO_DISTRIBUTION = {
     "five": "the full-resolution disparity of this head is a sum of low-resolution disparities weighted by softmax * logit planes: "
             "signed weights that do not sum to one, so it is not the mean of any distribution over disparities",
@@ -741,6 +747,24 @@ class _ECMNet(nn.Module):
                 kind, fields = ModalPrediction, tuple(fields) + tuple(_MODE_OP[self.HEAD](*args, mode_radius))
         last = fields[0].shape[0] - 1
         return kind(*(tuple(f[min(k, last)].unsqueeze(1) for k in heads) for f in fields))
+
+    def cross_check(self, left, right, threshold=1.0, rel=0.0, head=2):
+        """The left-right consistency check of one head: two plain inference forwards -- (left, right), and the two images
+        flipped along W and swapped, which gives the right view's disparity mirrored -- and one ops.lr_check kernel on the two
+        planes.  Returns a CrossCheck; .disparity is bit-identical to forward's under torch.no_grad(), .disparity_right to the
+        flipped forward's, flipped back once for the caller (the kernel reads the mirrored plane as it is).  Needs `forward`
+        only, so every registered architecture has it.  threshold (pixels) and rel (a share of the disparity) as in
+        ops.lr_check; head in 0..2."""
+        if isinstance(head, bool) or not isinstance(head, numbers.Integral) or not 0 <= head <= 2:     # before any device work
+            raise ValueError(f"cross_check: head {head!r}: one of 0, 1, 2")
+        threshold, rel = ops.check_lr_tolerances(threshold, rel)
+        with torch.no_grad():
+            out = self(left, right)[head]
+            out_r = self(torch.flip(right, (-1,)), torch.flip(left, (-1,)))[head]
+            if out.dim() == 3:
+                out, out_r = out.unsqueeze(1), out_r.unsqueeze(1)
+            error, kind, filled = ops.lr_check(out, out_r, threshold, rel, mirrored=True)
+            return CrossCheck(out, torch.flip(out_r, (-1,)), error.unsqueeze(1), kind.unsqueeze(1), filled.unsqueeze(1))
 
 
 class cmfsm(_ECMNet):

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import contextlib as _contextlib
 import ctypes as C
+import math
 import numbers
 import os as _os
 
@@ -582,6 +583,53 @@ def trilinear_softargmin_mode(c, Do, H, W, radius):
     _lib.call("ecm_trilinear_softargmin_mode_fwd", _p(c), C.c_longlong(B * Dl * h * w), _p(modal), NH, B, Dl, h, w, Do, H, W,
               radius, _stream())
     return _mode_planes(modal)
+
+
+# ------------------------------------------------------------------------------------ left-right consistency check
+# DESIGN.md section 17.  Forward only, one kernel: the error of the left disparity against the right view's disparity warped
+# into the left view, the failure class and the disparity filled from the background.
+LR_KINDS = ("consistent", "occluded", "mismatch", "out of view")      # the values 0..3 of the kind plane
+
+
+def lr_check_max_width():
+    """The widest map lr_check takes (a size query of the library: no GPU needed)."""
+    return int(_lib.query("ecm_lr_check_max_width"))
+
+
+def check_lr_tolerances(threshold, rel):
+    """(threshold, rel) as floats: both finite and >= 0 (pixels; a share of the disparity)."""
+    out = []
+    for name, v in (("threshold", threshold), ("rel", rel)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"lr_check: {name} {v!r}: a finite number >= 0")
+        out.append(float(v))
+    return tuple(out)
+
+
+@torch.no_grad()
+def lr_check(disp_l, disp_r, threshold=1.0, rel=0.0, mirrored=False, with_source=False):
+    """(error, kind, filled[, src]) of the left-right cross-check, each [B,H,W]: disp_l the left view's disparity, disp_r the
+    right view's in right-image coordinates ([B,H,W] or [B,1,H,W], pixels); mirrored: disp_r is stored flipped along W, as
+    forward(flip(right), flip(left)) returns it.  A pixel is consistent (kind 0) where |d - r| <= max(threshold, rel * d), r the
+    right disparity interpolated at x - d; else occluded (1) where r > d, else a mismatch (2); out of view (3) where x - d
+    leaves the image or d is not finite.  error is |d - r| (+inf for kind 3 and a non-finite r), kind a float plane, filled d
+    where consistent and elsewhere the smaller of the nearest consistent disparities on the row's left and right (0 if the row
+    has none); src (int32, with_source=True) the column it came from, -1 for none."""
+    threshold, rel = check_lr_tolerances(threshold, rel)               # before any device work
+    _chk(disp_l, disp_r)
+    if disp_l.dim() == 4 and disp_l.shape[1] == 1:
+        disp_l = disp_l[:, 0]
+    if disp_r.dim() == 4 and disp_r.shape[1] == 1:
+        disp_r = disp_r[:, 0]
+    _need(disp_l.dim() == 3 and disp_l.numel() > 0 and disp_r.shape == disp_l.shape,
+          lambda: f"lr_check: disp_l {tuple(disp_l.shape)}, disp_r {tuple(disp_r.shape)}: want two equal [B,H,W] or [B,1,H,W]")
+    B, H, W = disp_l.shape
+    dl, dr = _c(disp_l.detach()), _c(disp_r.detach())
+    check = torch.empty(3, B, H, W, device=dl.device, dtype=dl.dtype)
+    src = torch.empty(B, H, W, device=dl.device, dtype=torch.int32) if with_source else None
+    # W beyond lr_check_max_width() is refused by the library before any launch (ECM_EUNSUP -> RuntimeError)
+    _lib.call("ecm_lr_check_fwd", _p(dl), _p(dr), _p(check), _p(src), B, H, W, threshold, rel, int(bool(mirrored)), _stream())
+    return (check[0], check[1], check[2]) + ((src,) if with_source else ())
 
 
 # ------------------------------------------------------------------------------------ a5-a7 conv / deconv / GN

@@ -431,6 +431,24 @@ int ecm_eval_kitti(const float* pred, const float* gt, float* out8, float* per_s
 int ecm_disp_to_u16(const float* pred, unsigned short* out, int B, int Hp, int Wp, const int* h, const int* w,
                     int Ho, int Wo, float scale, void* stream);
 
+/* ABI 10: left-right consistency check of two disparity maps in one kernel (the cross-check that users of
+ * the reference run in numpy on the host).  dl [B,H,W]: left-view disparity in pixels; dr [B,H,W]: right-view disparity in
+ * right-image coordinates (right pixel x' matches left pixel x' + dr); with mirrored != 0 dr is stored flipped along W (element
+ * x' at W-1-x': what a forward pass on the two flipped images returns).  Per pixel, d = dl[b,y,x], all in fp32:
+ *   xr = x - d;  x0 = floor(xr);  x1 = min(x0 + 1, W-1);  t = xr - x0;  r = dr[x0] + t (dr[x1] - dr[x0]) on the same row;
+ *   tol = max(threshold, rel * d);  error = |d - r|, +inf where kind is 3 or r is not finite;
+ *   kind = 3 (out of view) if d is not finite or xr < 0 or xr > W-1;  else 0 (consistent) if error <= tol;  else 1 (occluded)
+ *          if r is finite and r > d;  else 2 (mismatch);
+ *   filled = d where kind is 0, else dl at the nearest consistent column of the row on the left or on the right, whichever holds
+ *          the smaller disparity (the left one on a tie; the only one if the other side has none), 0 if the row has none.
+ * check: [3,B,H,W] = (error, kind, filled), kind a float plane of exact integers.  src (int [B,H,W], may be NULL): the column
+ * `filled` was copied from, -1 for none.  One launch, a workgroup per row at a time; no atomics: bit-reproducible.
+ * threshold, rel >= 0 and finite, B, H, W >= 1, else ECM_EINVAL; W > ecm_lr_check_max_width() or B * H >= 2^31: ECM_EUNSUP,
+ * before any launch. */
+int ecm_lr_check_max_width(void);
+int ecm_lr_check_fwd(const float* dl, const float* dr, float* check, int* src, int B, int H, int W, float threshold, float rel,
+                     int mirrored, void* stream);
+
 /* Harness loss + metrics (train.py:162,172-174; train_kitti.py:205-216) over n = B*H*W pixels; mask = 0 < gt < maxdisp.
  * out8 (device): [loss, #mask, epe(p3), err3(p3) in %, mean smooth-L1 of p1, p2, p3, 0];
  * loss = w1*m1 + w2*m2 + w3*m3 (reference weights 0.5 / 0.7 / 1.0).  Empty mask -> NaN (as the reference's empty mean).

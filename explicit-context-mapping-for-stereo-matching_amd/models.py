@@ -606,6 +606,10 @@ ModalPrediction = collections.namedtuple("ModalPrediction", "disparity std peak 
 # 2 mismatch, 3 out of view; a float plane) and the left disparity with the failures filled from the background.
 CrossCheck = collections.namedtuple("CrossCheck", "disparity disparity_right error kind filled")
 
+# What _ECMNet.refine returns: CrossCheck's five fields, bit for bit, then the masked median of `filled`
+# and the joint bilateral filter of that median guided by the left image, each [B,1,H,W].
+Refined = collections.namedtuple("Refined", "disparity disparity_right error kind filled median refined")
+
 _NO_DISTRIBUTION = {
     "five": "the full-resolution disparity of this head is a sum of low-resolution disparities weighted by softmax * logit planes: "
             "signed weights that do not sum to one, so it is not the mean of any distribution over disparities",
@@ -765,6 +769,29 @@ class _ECMNet(nn.Module):
                 out, out_r = out.unsqueeze(1), out_r.unsqueeze(1)
             error, kind, filled = ops.lr_check(out, out_r, threshold, rel, mirrored=True)
             return CrossCheck(out, torch.flip(out_r, (-1,)), error.unsqueeze(1), kind.unsqueeze(1), filled.unsqueeze(1))
+
+    def refine(self, left, right, threshold=1.0, rel=0.0, head=2, median_radius=2, bilateral_radius=4, sigma_space=2.0,
+               sigma_color=0.25):
+        """cross_check, then the two image-space filters that make `filled` a dense map: ops.disparity_median (median_radius 1..3)
+        over the pixels with filled > 0 -- one ATen compare; 0 is what a row without a consistent pixel holds -- and
+        ops.disparity_bilateral (bilateral_radius, sigma_space in pixels, sigma_color in the units of `left`) of that median over
+        the pixels with median > 0, guided by `left` as passed.  Returns a Refined: cross_check's five fields bit for bit, then
+        .median and .refined, each [B,1,H,W].  median_radius=None skips the median (.median is .filled, and the bilateral reads
+        it); bilateral_radius=None skips the bilateral (.refined is .median).  The defaults (5x5, 9x9, sigma 2 px, 0.25) are
+        plausible values for images normalised as the model consumes them; their effect on EPE or D1 has not been measured."""
+        if median_radius is not None:                                                                  # before any device work
+            median_radius = ops.check_median_radius(median_radius, "refine")
+        if bilateral_radius is not None:
+            bilateral_radius, sigma_space, sigma_color = ops.check_bilateral_parameters(bilateral_radius, sigma_space, sigma_color, "refine")
+        cc = self.cross_check(left, right, threshold, rel, head)
+        with torch.no_grad():
+            median = cc.filled
+            if median_radius is not None:
+                median = ops.disparity_median(median, median > 0, median_radius).unsqueeze(1)
+            refined = median
+            if bilateral_radius is not None:
+                refined = ops.disparity_bilateral(median, left, median > 0, bilateral_radius, sigma_space, sigma_color).unsqueeze(1)
+            return Refined(*cc, median, refined)
 
 
 class cmfsm(_ECMNet):

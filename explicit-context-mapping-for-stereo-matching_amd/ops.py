@@ -632,6 +632,94 @@ def lr_check(disp_l, disp_r, threshold=1.0, rel=0.0, mirrored=False, with_source
     return (check[0], check[1], check[2]) + ((src,) if with_source else ())
 
 
+# ------------------------------------------------------------------------------------ disparity post-filters
+# DESIGN.md section 18.  Forward only, one kernel each: the masked lower median of a (2r+1)^2 window, and the joint bilateral
+# filter guided by an image.  A sample is usable iff it is inside the image, finite and valid; windows are clipped to the image.
+DISP_FILTER_KINDS = ("median", "bilateral")                            # the `kind` of ecm_disp_filter_max_radius: 0, 1
+
+
+def disp_filter_max_radius(kind):
+    """The largest radius of disparity_median ("median") or disparity_bilateral ("bilateral"): a size query, no GPU needed."""
+    if kind not in DISP_FILTER_KINDS:
+        raise ValueError(f"disp_filter_max_radius: kind {kind!r}: one of {DISP_FILTER_KINDS}")
+    return int(_lib.query("ecm_disp_filter_max_radius", DISP_FILTER_KINDS.index(kind)))
+
+
+def _check_filter_radius(who, kind, radius):
+    top = disp_filter_max_radius(kind)
+    if isinstance(radius, bool) or not isinstance(radius, numbers.Integral) or not 1 <= radius <= top:
+        raise ValueError(f"{who}: radius {radius!r}: an integer in 1..{top}")
+    return int(radius)
+
+
+def check_median_radius(radius, who="disparity_median"):
+    """radius as an int: 1, 2 or 3 (a 3x3, 5x5 or 7x7 window)."""
+    return _check_filter_radius(who, "median", radius)
+
+
+def check_bilateral_parameters(radius, sigma_space, sigma_color, who="disparity_bilateral"):
+    """(radius, sigma_space, sigma_color): an int in 1..disp_filter_max_radius("bilateral") and two finite floats > 0."""
+    radius = _check_filter_radius(who, "bilateral", radius)
+    out = []
+    for name, v in (("sigma_space", sigma_space), ("sigma_color", sigma_color)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v <= 0:
+            raise ValueError(f"{who}: {name} {v!r}: a finite number > 0")
+        out.append(float(v))
+    return (radius,) + tuple(out)
+
+
+def _filter_planes(who, disp, valid):
+    """disp as a contiguous [B,H,W] plane and valid as a contiguous uint8 plane of the same shape (or None)."""
+    _chk(disp)
+    if disp.dim() == 4 and disp.shape[1] == 1:
+        disp = disp[:, 0]
+    _need(disp.dim() == 3 and disp.numel() > 0, lambda: f"{who}: disp {tuple(disp.shape)}: want [B,H,W] or [B,1,H,W]")
+    if valid is not None:
+        _need(valid.is_cuda, "ecm ops run only on the MI355X HIP path: got a CPU tensor (no CPU fallback exists)")
+        _need(valid.dtype in (torch.bool, torch.uint8), lambda: f"{who}: valid is {valid.dtype}: want bool or uint8")
+        if valid.dim() == 4 and valid.shape[1] == 1:
+            valid = valid[:, 0]
+        _need(valid.shape == disp.shape, lambda: f"{who}: valid {tuple(valid.shape)} against disp {tuple(disp.shape)}")
+        valid = valid.detach().contiguous()
+        if valid.dtype == torch.bool:
+            valid = valid.view(torch.uint8)                            # a bool is one byte, 0 or 1: no copy
+    return _c(disp.detach()), valid
+
+
+@torch.no_grad()
+def disparity_median(disp, valid=None, radius=2, with_support=False):
+    """The masked lower median of disp ([B,H,W] or [B,1,H,W], pixels) over a (2 radius + 1)^2 window clipped to the image, as a
+    [B,H,W] plane: the value of rank floor((m-1)/2) among the m usable samples of the window -- inside the image, finite, and
+    valid != 0 (valid: bool or uint8 of disp's shape; None: all ones) -- so one of the inputs bit for bit, and 0 where m == 0.
+    with_support=True returns (median, support), support = m as a float plane.  radius 1, 2 or 3."""
+    radius = check_median_radius(radius)                               # before any device work
+    d, v = _filter_planes("disparity_median", disp, valid)
+    B, H, W = d.shape
+    out = torch.empty(2, B, H, W, device=d.device, dtype=d.dtype)
+    # B * H * W >= 2^31 is refused by the library before any launch (ECM_EUNSUP -> RuntimeError)
+    _lib.call("ecm_disp_median_fwd", _p(d), _p(v), _p(out), B, H, W, radius, _stream())
+    return (out[0], out[1]) if with_support else out[0]
+
+
+@torch.no_grad()
+def disparity_bilateral(disp, guide, valid=None, radius=4, sigma_space=2.0, sigma_color=0.25, with_weight=False):
+    """The joint bilateral filter of disp ([B,H,W] or [B,1,H,W]) guided by guide [B,C,H,W] (C in 1..4, fp32; e.g. the left image
+    as the model consumes it), as a [B,H,W] plane: sum w d / sum w over the usable samples q of the (2 radius + 1)^2 window
+    clipped to the image, w = exp(-|q - p|^2 / (2 sigma_space^2) - |guide[p] - guide[q]|^2 / (2 sigma_color^2)); a sample whose
+    exponent is NaN is left out; 0 where sum w == 0.  A pixel that is not usable itself is written from its neighbours (hole
+    filling).  with_weight=True returns (refined, weight), weight = sum w.  radius in 1..disp_filter_max_radius("bilateral")."""
+    radius, sigma_space, sigma_color = check_bilateral_parameters(radius, sigma_space, sigma_color)      # before any device work
+    _chk(guide)
+    d, v = _filter_planes("disparity_bilateral", disp, valid)
+    B, H, W = d.shape
+    _need(guide.dim() == 4 and guide.shape[0] == B and 1 <= guide.shape[1] <= 4 and tuple(guide.shape[2:]) == (H, W),
+          lambda: f"disparity_bilateral: guide {tuple(guide.shape)} against disp {tuple(d.shape)}: want [B,C,H,W], C in 1..4")
+    g = _c(guide.detach())
+    out = torch.empty(2, B, H, W, device=d.device, dtype=d.dtype)
+    _lib.call("ecm_disp_bilateral_fwd", _p(d), _p(v), _p(g), _p(out), B, g.shape[1], H, W, radius, sigma_space, sigma_color, _stream())
+    return (out[0], out[1]) if with_weight else out[0]
+
+
 # ------------------------------------------------------------------------------------ a5-a7 conv / deconv / GN
 def _pack_conv(w, flip_transpose=False):
     Co, Ci = w.shape[0], w.shape[1]

@@ -449,6 +449,32 @@ int ecm_lr_check_max_width(void);
 int ecm_lr_check_fwd(const float* dl, const float* dr, float* check, int* src, int B, int H, int W, float threshold, float rel,
                      int mirrored, void* stream);
 
+/* ABI 11: image-space post-filters of a disparity map (the median and the guided bilateral filter that end
+ * the classical stereo pipeline and that users of the reference run with OpenCV or numpy on the host).  All arithmetic in fp32.
+ *   Usable sample.  d [B,H,W] fp32, valid [B,H,W] unsigned char (NULL: all ones).  A sample q is usable iff it lies inside the
+ *     image, d[q] is finite and valid[q] != 0.  Windows are clipped to the image: a position outside it is excluded exactly like
+ *     an invalid one; no padding, no replication.
+ *   Masked median, radius r in 1..ecm_disp_filter_max_radius(ECM_DISP_FILTER_MEDIAN) = 3 (3x3, 5x5, 7x7).  m = the number of
+ *     usable samples in the (2r+1)^2 window about p (the centre counts if it is usable); median[p] = the LOWER median, the value
+ *     of rank floor((m-1)/2), 0-based and ascending, among them -- one of the inputs, bit for bit (+0 and -0 compare equal) -- and
+ *     0, KITTI's invalid value, where m == 0; support[p] = m, a float plane of exact integers.  out [2,B,H,W] = (median, support).
+ *   Joint bilateral, radius r in 1..ecm_disp_filter_max_radius(ECM_DISP_FILTER_BILATERAL) = 8 (17x17), guide g [B,C,H,W] fp32,
+ *     C in 1..4.  For a usable q = p + (dx, dy) of the clipped window
+ *       w(q) = exp( -(dx^2 + dy^2) / (2 sigma_space^2) - sum_c (g_c[p] - g_c[q])^2 / (2 sigma_color^2) );
+ *     a sample whose exponent is NaN (a non-finite guide value at p or at q) is excluded.  refined[p] = sum w d / sum w where
+ *     sum w > 0, else 0; weight[p] = sum w.  The centre is included when it is usable (w = 1); a pixel whose centre is not usable
+ *     is written all the same, from its neighbours: the hole filling.  out [2,B,H,W] = (refined, weight).
+ * One launch each, LDS-tiled, no scratch, no atomics: bit-reproducible.  Neither H nor W has an upper bound; B * H * W >= 2^31
+ * returns ECM_EUNSUP before any launch.  ECM_EINVAL, before any device work: a null d / guide / out, B, H or W < 1, a radius out
+ * of range, C outside 1..4, a sigma that is not finite and positive.  ecm_disp_filter_max_radius is a size query (no GPU);
+ * ECM_EINVAL for an unknown kind. */
+#define ECM_DISP_FILTER_MEDIAN    0
+#define ECM_DISP_FILTER_BILATERAL 1
+int ecm_disp_filter_max_radius(int kind);
+int ecm_disp_median_fwd(const float* d, const unsigned char* valid, float* out, int B, int H, int W, int radius, void* stream);
+int ecm_disp_bilateral_fwd(const float* d, const unsigned char* valid, const float* guide, float* out, int B, int C, int H, int W,
+                           int radius, float sigma_space, float sigma_color, void* stream);
+
 /* Harness loss + metrics (train.py:162,172-174; train_kitti.py:205-216) over n = B*H*W pixels; mask = 0 < gt < maxdisp.
  * out8 (device): [loss, #mask, epe(p3), err3(p3) in %, mean smooth-L1 of p1, p2, p3, 0];
  * loss = w1*m1 + w2*m2 + w3*m3 (reference weights 0.5 / 0.7 / 1.0).  Empty mask -> NaN (as the reference's empty mean).

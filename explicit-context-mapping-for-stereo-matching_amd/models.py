@@ -610,6 +610,11 @@ CrossCheck = collections.namedtuple("CrossCheck", "disparity disparity_right err
 # and the joint bilateral filter of that median guided by the left image, each [B,1,H,W].
 Refined = collections.namedtuple("Refined", "disparity disparity_right error kind filled median refined")
 
+# What _ECMNet.despeckle returns: Refined's seven fields in the same order -- the first
+# five cross_check's bit for bit, the two filters reading `despeckled` -- then the filled map without the small segments and the
+# segment size of every pixel (int32; 0 where the pixel is not consistent), each [B,1,H,W].
+Despeckled = collections.namedtuple("Despeckled", Refined._fields + ("despeckled", "segment"))
+
 _NO_DISTRIBUTION = {
     "five": "the full-resolution disparity of this head is a sum of low-resolution disparities weighted by softmax * logit planes: "
             "signed weights that do not sum to one, so it is not the mean of any distribution over disparities",
@@ -759,6 +764,11 @@ class _ECMNet(nn.Module):
         flipped forward's, flipped back once for the caller (the kernel reads the mirrored plane as it is).  Needs `forward`
         only, so every registered architecture has it.  threshold (pixels) and rel (a share of the disparity) as in
         ops.lr_check; head in 0..2."""
+        return self._cross_check(left, right, threshold, rel, head, False)[0]
+
+    def _cross_check(self, left, right, threshold, rel, head, with_source):
+        """(the CrossCheck, src): cross_check's computation; src [B,H,W] int32, the column each pixel of `filled` was copied
+        from (its own where it is consistent, -1 for none), where with_source, else None."""
         if isinstance(head, bool) or not isinstance(head, numbers.Integral) or not 0 <= head <= 2:     # before any device work
             raise ValueError(f"cross_check: head {head!r}: one of 0, 1, 2")
         threshold, rel = ops.check_lr_tolerances(threshold, rel)
@@ -767,8 +777,9 @@ class _ECMNet(nn.Module):
             out_r = self(torch.flip(right, (-1,)), torch.flip(left, (-1,)))[head]
             if out.dim() == 3:
                 out, out_r = out.unsqueeze(1), out_r.unsqueeze(1)
-            error, kind, filled = ops.lr_check(out, out_r, threshold, rel, mirrored=True)
-            return CrossCheck(out, torch.flip(out_r, (-1,)), error.unsqueeze(1), kind.unsqueeze(1), filled.unsqueeze(1))
+            error, kind, filled, *src = ops.lr_check(out, out_r, threshold, rel, mirrored=True, with_source=with_source)
+            cc = CrossCheck(out, torch.flip(out_r, (-1,)), error.unsqueeze(1), kind.unsqueeze(1), filled.unsqueeze(1))
+            return cc, (src[0] if with_source else None)
 
     def refine(self, left, right, threshold=1.0, rel=0.0, head=2, median_radius=2, bilateral_radius=4, sigma_space=2.0,
                sigma_color=0.25):
@@ -779,18 +790,45 @@ class _ECMNet(nn.Module):
         .median and .refined, each [B,1,H,W].  median_radius=None skips the median (.median is .filled, and the bilateral reads
         it); bilateral_radius=None skips the bilateral (.refined is .median).  The defaults (5x5, 9x9, sigma 2 px, 0.25) are
         plausible values for images normalised as the model consumes them; their effect on EPE or D1 has not been measured."""
+        return self._refine(left, right, threshold, rel, head, median_radius, bilateral_radius, sigma_space, sigma_color, None, 1.0)
+
+    def despeckle(self, left, right, threshold=1.0, rel=0.0, head=2, median_radius=2, bilateral_radius=4, sigma_space=2.0,
+                  sigma_color=0.25, speckle_size=200, speckle_diff=1.0):
+        """refine with the speckle filter in it, run where OpenCV's pipelines run it: on the checked map, before any filling.
+        After cross_check, ops.disparity_speckle of .disparity over the consistent pixels (kind == 0) with max_size =
+        speckle_size (an integer >= 0) and max_diff = speckle_diff; a pixel of `filled` then shares the fate of the pixel it was
+        copied from (its own, where it is consistent): .despeckled is `filled` where that pixel's segment has more than
+        speckle_size pixels and 0 elsewhere -- one gather along W and one where -- and refine's two filters read .despeckled in
+        place of `filled` (valid = despeckled > 0; the None radii as in refine).  Returns a Despeckled: Refined's seven fields in
+        the same order, the first five cross_check's bit for bit, then .despeckled and .segment (int32: the size of each pixel's
+        segment, 0 where it is not consistent), each [B,1,H,W].  speckle_size=None is refine itself: the same code path, results
+        and return type (speckle_diff is not looked at).  200 pixels and 1.0 are the values customary with OpenCV; their effect
+        on EPE or D1 has not been measured either."""
+        return self._refine(left, right, threshold, rel, head, median_radius, bilateral_radius, sigma_space, sigma_color,
+                            speckle_size, speckle_diff)
+
+    def _refine(self, left, right, threshold, rel, head, median_radius, bilateral_radius, sigma_space, sigma_color, speckle_size,
+                speckle_diff):
         if median_radius is not None:                                                                  # before any device work
             median_radius = ops.check_median_radius(median_radius, "refine")
         if bilateral_radius is not None:
             bilateral_radius, sigma_space, sigma_color = ops.check_bilateral_parameters(bilateral_radius, sigma_space, sigma_color, "refine")
-        cc = self.cross_check(left, right, threshold, rel, head)
+        if speckle_size is not None:
+            speckle_size, speckle_diff = ops.check_speckle_parameters(speckle_size, speckle_diff, "despeckle")
+        cc, src = self._cross_check(left, right, threshold, rel, head, speckle_size is not None)
         with torch.no_grad():
             median = cc.filled
+            if speckle_size is not None:
+                kept, _, segment = ops.disparity_speckle(cc.disparity, cc.kind == 0, speckle_size, speckle_diff, with_segments=True)
+                source = torch.gather(kept, 2, src.clamp(min=0).long())                  # kept at the column the fill came from
+                median = despeckled = torch.where((src >= 0) & (source > 0), cc.filled[:, 0], 0.0).unsqueeze(1)
             if median_radius is not None:
                 median = ops.disparity_median(median, median > 0, median_radius).unsqueeze(1)
             refined = median
             if bilateral_radius is not None:
                 refined = ops.disparity_bilateral(median, left, median > 0, bilateral_radius, sigma_space, sigma_color).unsqueeze(1)
+            if speckle_size is not None:
+                return Despeckled(*cc, median, refined, despeckled, segment.unsqueeze(1))
             return Refined(*cc, median, refined)
 
 

@@ -720,6 +720,37 @@ def disparity_bilateral(disp, guide, valid=None, radius=4, sigma_space=2.0, sigm
     return (out[0], out[1]) if with_weight else out[0]
 
 
+# ------------------------------------------------------------------------------------ speckle filter
+# DESIGN.md section 19.  Forward only: the connected segments of near-constant disparity (4-neighbours, both usable,
+# |d[p] - d[q]| <= max_diff), each pixel's segment label and size, and the map with the segments of at most max_size pixels removed.
+def check_speckle_parameters(max_size, max_diff, who="disparity_speckle"):
+    """(max_size, max_diff) as an int and a float: an integer >= 0 (pixels) and a finite number >= 0 (pixels of disparity)."""
+    if isinstance(max_size, bool) or not isinstance(max_size, numbers.Integral) or max_size < 0:
+        raise ValueError(f"{who}: max_size {max_size!r}: an integer >= 0")
+    if isinstance(max_diff, bool) or not isinstance(max_diff, numbers.Real) or not math.isfinite(max_diff) or max_diff < 0:
+        raise ValueError(f"{who}: max_diff {max_diff!r}: a finite number >= 0")
+    return int(max_size), float(max_diff)
+
+
+@torch.no_grad()
+def disparity_speckle(disp, valid=None, max_size=200, max_diff=1.0, with_segments=False):
+    """The speckle filter of disp ([B,H,W] or [B,1,H,W], pixels) as a [B,H,W] plane: disp, bit for bit, where the pixel is usable
+    -- finite, and valid != 0 (valid: bool or uint8 of disp's shape; None: all ones) -- and its segment has more than max_size
+    pixels; 0 elsewhere.  A segment is a connected component of the usable pixels under "4-neighbours in the same image whose
+    disparities differ by at most max_diff" (fp32, inclusive; OpenCV's filterSpeckles rule, a segment of exactly max_size pixels
+    is removed).  with_segments=True returns (out, label, size), both int32: the row-major index y*W + x, within its image, of
+    the segment's first pixel (-1 where not usable) and the segment's pixel count (0 where not usable).  The defaults (200 pixels,
+    1.0) are the values customary with OpenCV; their effect on EPE or D1 has not been measured."""
+    max_size, max_diff = check_speckle_parameters(max_size, max_diff)  # before any device work
+    d, v = _filter_planes("disparity_speckle", disp, valid)
+    B, H, W = d.shape
+    out = torch.empty(B, H, W, device=d.device, dtype=d.dtype)
+    segments = torch.empty(2, B, H, W, device=d.device, dtype=torch.int32)
+    # B * H * W >= 2^31 is refused by the library before any launch (ECM_EUNSUP -> RuntimeError)
+    _lib.call("ecm_disp_speckle_fwd", _p(d), _p(v), _p(out), _p(segments), B, H, W, max_size, max_diff, _stream())
+    return (out, segments[0], segments[1]) if with_segments else out
+
+
 # ------------------------------------------------------------------------------------ a5-a7 conv / deconv / GN
 def _pack_conv(w, flip_transpose=False):
     Co, Ci = w.shape[0], w.shape[1]

@@ -475,6 +475,27 @@ int ecm_disp_median_fwd(const float* d, const unsigned char* valid, float* out, 
 int ecm_disp_bilateral_fwd(const float* d, const unsigned char* valid, const float* guide, float* out, int B, int C, int H, int W,
                            int radius, float sigma_space, float sigma_color, void* stream);
 
+/* ABI 12: the speckle filter of a disparity map (OpenCV's filterSpeckles, which users of the reference run on
+ * the host): the connected segments of near-constant disparity, and the map with the small ones removed.
+ *   Usable.  As in ABI 11: d [B,H,W] fp32, valid [B,H,W] unsigned char (NULL: all ones); a pixel is usable iff d is finite and
+ *     valid != 0.
+ *   Connected.  Two usable pixels of the same image are connected iff they are 4-neighbours (left/right/up/down: no diagonals, no
+ *     wrap from the end of a row to the start of the next or from one image to the next) and |d[p] - d[q]| <= max_diff, evaluated
+ *     in fp32 and inclusive.
+ *   Segment.  A connected component of that graph.  The relation is not transitive: a ramp whose step is <= max_diff is one
+ *     segment although its ends differ by much more.
+ *   segments [2,B,H,W] int32 = (label, size): label[p] = the row-major index y*W + x, within its image, of the first pixel of p's
+ *     segment, -1 where p is not usable; size[p] = the segment's pixel count, 0 where p is not usable.
+ *   out [B,H,W] fp32: d[p], bit for bit, where p is usable and size[p] > max_size; 0 elsewhere.  A segment is removed iff its size
+ *     is <= max_size (filterSpeckles' rule); with max_size = 0 nothing usable is removed.  out must not overlap d.
+ * Four launches on `stream` (union-find over int32 parents: per tile in LDS, across tile borders by agent-scope atomic min, then a
+ * count and a broadcast); `segments` and `out` double as the working arrays, so there is no scratch buffer.  Integer atomics only,
+ * and label is a minimum and size a sum of integers: bit-reproducible.  No kernel waits for another workgroup.  Neither H nor W has
+ * an upper bound; B * H * W >= 2^31 returns ECM_EUNSUP before any launch.  ECM_EINVAL, before any device work: a null d, out or
+ * segments, B, H or W < 1, max_size < 0, max_diff negative or not finite. */
+int ecm_disp_speckle_fwd(const float* d, const unsigned char* valid, float* out, int* segments, int B, int H, int W, int max_size,
+                         float max_diff, void* stream);
+
 /* Harness loss + metrics (train.py:162,172-174; train_kitti.py:205-216) over n = B*H*W pixels; mask = 0 < gt < maxdisp.
  * out8 (device): [loss, #mask, epe(p3), err3(p3) in %, mean smooth-L1 of p1, p2, p3, 0];
  * loss = w1*m1 + w2*m2 + w3*m3 (reference weights 0.5 / 0.7 / 1.0).  Empty mask -> NaN (as the reference's empty mean).

@@ -615,6 +615,11 @@ Refined = collections.namedtuple("Refined", "disparity disparity_right error kin
 # segment size of every pixel (int32; 0 where the pixel is not consistent), each [B,1,H,W].
 Despeckled = collections.namedtuple("Despeckled", Refined._fields + ("despeckled", "segment"))
 
+# What _ECMNet.smooth returns: CrossCheck's five fields bit for bit, then the confidence plane the smoother
+# was given (1.0 where the pixel is consistent and, with the speckle filter on, in a segment larger than speckle_size; else 0) and
+# the WLS-smoothed disparity, each [B,1,H,W].
+Smoothed = collections.namedtuple("Smoothed", CrossCheck._fields + ("confidence", "smoothed"))
+
 _NO_DISTRIBUTION = {
     "five": "the full-resolution disparity of this head is a sum of low-resolution disparities weighted by softmax * logit planes: "
             "signed weights that do not sum to one, so it is not the mean of any distribution over disparities",
@@ -830,6 +835,29 @@ class _ECMNet(nn.Module):
             if speckle_size is not None:
                 return Despeckled(*cc, median, refined, despeckled, segment.unsqueeze(1))
             return Refined(*cc, median, refined)
+
+    def smooth(self, left, right, threshold=1.0, rel=0.0, head=2, speckle_size=200, speckle_diff=1.0, lam=8000.0, sigma_color=0.25,
+               iterations=3):
+        """cross_check, then the global smoother that ends OpenCV's chain (DisparityWLSFilter), in place of every local fill:
+        with speckle_size not None, ops.disparity_speckle of .disparity over the consistent pixels exactly as despeckle runs it;
+        confidence = 1.0 where kind == 0 and (speckles on) the pixel's segment has more than speckle_size pixels, else 0; then
+        ops.disparity_wls(.disparity, left, confidence, lam, sigma_color, iterations), guided by `left` as passed.  Neither
+        `filled`, the median nor the bilateral filter is run: a hole is a pixel of confidence 0 and is written from as far away as
+        the guide's edges allow.  Returns a Smoothed: cross_check's five fields bit for bit, then .confidence and .smoothed, each
+        [B,1,H,W].  The defaults are untested for quality: 8000 and 3 are the values customary with OpenCV, 0.25 is the bilateral
+        filter's default in the units of `left`, 200 and 1.0 are despeckle's; nobody has measured their effect on EPE or D1."""
+        lam, sigma_color, iterations = ops.check_wls_parameters(lam, sigma_color, iterations, "smooth")  # before any device work
+        if speckle_size is not None:
+            speckle_size, speckle_diff = ops.check_speckle_parameters(speckle_size, speckle_diff, "smooth")
+        cc, _ = self._cross_check(left, right, threshold, rel, head, False)
+        with torch.no_grad():
+            confident = cc.kind == 0
+            if speckle_size is not None:
+                _, _, segment = ops.disparity_speckle(cc.disparity, confident, speckle_size, speckle_diff, with_segments=True)
+                confident = confident & (segment.unsqueeze(1) > speckle_size)
+            confidence = confident.to(torch.float32)
+            smoothed = ops.disparity_wls(cc.disparity, left, confidence, lam, sigma_color, iterations).unsqueeze(1)
+            return Smoothed(*cc, confidence, smoothed)
 
 
 class cmfsm(_ECMNet):

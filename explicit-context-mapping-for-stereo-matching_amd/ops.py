@@ -751,6 +751,57 @@ def disparity_speckle(disp, valid=None, max_size=200, max_diff=1.0, with_segment
     return (out, segments[0], segments[1]) if with_segments else out
 
 
+# ------------------------------------------------------------------------------------ WLS smoother
+# DESIGN.md section 20.  Forward only: the confidence-weighted fast global smoother (OpenCV's DisparityWLSFilter), 2T launches.
+WLS_MAX_ITERATIONS = 8
+
+
+def check_wls_parameters(lam, sigma_color, iterations, who="disparity_wls"):
+    """(lam, sigma_color, iterations): two finite floats > 0 and an int in 1..8."""
+    out = []
+    for name, v in (("lam", lam), ("sigma_color", sigma_color)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v <= 0:
+            raise ValueError(f"{who}: {name} {v!r}: a finite number > 0")
+        out.append(float(v))
+    if isinstance(iterations, bool) or not isinstance(iterations, numbers.Integral) or not 1 <= iterations <= WLS_MAX_ITERATIONS:
+        raise ValueError(f"{who}: iterations {iterations!r}: an integer in 1..{WLS_MAX_ITERATIONS}")
+    return out[0], out[1], int(iterations)
+
+
+@torch.no_grad()
+def disparity_wls(disp, guide, confidence=None, lam=8000.0, sigma_color=0.25, iterations=3, with_weight=False):
+    """The WLS smoothing of disp ([B,H,W] or [B,1,H,W], pixels) guided by guide [B,C,H,W] (C in 1..4, fp32; e.g. the left image as
+    the model consumes it), as a [B,H,W] plane: N = confidence * disp and D = confidence each go through `iterations` rounds of
+    "every row, then every column" of the tridiagonal solve (I + lam_t A) u = f, A the Laplacian of the link weights
+    w = exp(-|guide[p] - guide[q]| / sigma_color) between 4-neighbours (a NaN weight cuts the link) and lam_t =
+    1.5 * 4^(T-t) / (4^T - 1) * lam; the result is N / D where D > 0 and 0 elsewhere.  confidence: a float plane of disp's shape
+    (bool or uint8 is converted; None: all ones); a pixel whose disp is not finite, or whose confidence is not finite or is
+    negative, counts as confidence 0 -- holes need no filling.  with_weight=True returns (smoothed, weight), weight = D.
+    The defaults (8000, 3: customary with OpenCV; 0.25: the bilateral filter's) are untested for quality."""
+    lam, sigma_color, iterations = check_wls_parameters(lam, sigma_color, iterations)            # before any device work
+    _chk(guide)
+    d, _ = _filter_planes("disparity_wls", disp, None)
+    B, H, W = d.shape
+    conf = confidence
+    if conf is not None:
+        _need(conf.is_cuda, "ecm ops run only on the MI355X HIP path: got a CPU tensor (no CPU fallback exists)")
+        _need(conf.dtype in (torch.float32, torch.bool, torch.uint8),
+              lambda: f"disparity_wls: confidence is {conf.dtype}: want float32, bool or uint8")
+        if conf.dim() == 4 and conf.shape[1] == 1:
+            conf = conf[:, 0]
+        _need(conf.shape == d.shape, lambda: f"disparity_wls: confidence {tuple(conf.shape)} against disp {tuple(d.shape)}")
+        conf = _c(conf.detach().to(torch.float32))
+    _need(guide.dim() == 4 and guide.shape[0] == B and 1 <= guide.shape[1] <= 4 and tuple(guide.shape[2:]) == (H, W),
+          lambda: f"disparity_wls: guide {tuple(guide.shape)} against disp {tuple(d.shape)}: want [B,C,H,W], C in 1..4")
+    g = _c(guide.detach())
+    out = torch.empty(2, B, H, W, device=d.device, dtype=d.dtype)
+    scratch = _scratch(_lib.query("ecm_disp_wls_scratch_bytes", B, H, W), d.device)
+    # B * H * W >= 2^31 is refused by the library before any launch (ECM_EUNSUP -> RuntimeError)
+    _lib.call("ecm_disp_wls_fwd", _p(d), _p(conf), _p(g), _p(out), _p(scratch), B, g.shape[1], H, W, lam, sigma_color, iterations,
+              _stream())
+    return (out[0], out[1]) if with_weight else out[0]
+
+
 # ------------------------------------------------------------------------------------ a5-a7 conv / deconv / GN
 def _pack_conv(w, flip_transpose=False):
     Co, Ci = w.shape[0], w.shape[1]

@@ -496,6 +496,31 @@ int ecm_disp_bilateral_fwd(const float* d, const unsigned char* valid, const flo
 int ecm_disp_speckle_fwd(const float* d, const unsigned char* valid, float* out, int* segments, int B, int H, int W, int max_size,
                          float max_diff, void* stream);
 
+/* ABI 13: the WLS disparity smoother: the confidence-weighted, edge-aware global smoother that ends OpenCV's
+ * post-processing chain (DisparityWLSFilter; the fast global smoother of Min et al. 2014).  All device arithmetic in fp32.
+ *   Inputs.  d [B,H,W] fp32 (pixels), guide g [B,C,H,W] fp32 with C in 1..4, conf [B,H,W] fp32 (NULL: all ones).
+ *   Usable pixel.  d[p] finite, conf[p] finite and conf[p] >= 0; where a pixel is not usable both its d and its conf count as 0.
+ *   Link weights.  Between horizontal neighbours p = (y,x), q = (y,x+1): w = exp(-sqrt(sum_c (g_c[p] - g_c[q])^2) / sigma_color),
+ *     the vertical ones alike; a weight that is NaN (a non-finite guide value) is 0: the link is cut.
+ *   One line solve, length n, right-hand side f, weights w_0..w_{n-2}, strength L: (I + L A) u = f with a_i = -L w_{i-1} (a_0 = 0),
+ *     c_i = -L w_i (c_{n-1} = 0), b_i = 1 - a_i - c_i, by the Thomas algorithm in natural order: den = b_i - a_i c'_{i-1},
+ *     c'_i = c_i / den, f'_i = (f_i - a_i f'_{i-1}) / den, then u_i = f'_i - c'_i u_{i+1}.  Strictly diagonally dominant: no pivoting.
+ *   Schedule.  N = conf * d, D = conf; for t = 1..T with L_t = 1.5 * 4^(T-t) / (4^T - 1) * lam (formed in double from the fp32 lam,
+ *     then rounded to fp32): every row of N and of D with the horizontal weights, then every column with the vertical ones.  N and
+ *     D go through the same instructions with the same coefficients.
+ *   out [2,B,H,W] = (smoothed, weight): smoothed = N / D (a true IEEE division) where D > 0, else 0; weight = D.  A constant
+ *     power-of-two plane comes back bit for bit wherever D > 0; a region that cut links separate from every confident pixel has
+ *     D == 0 exactly and is 0.
+ * 2T launches on `stream` (a row pass and a column pass per iteration; forward and backward sweep of a pass in one kernel, one
+ * lane per line).  `out` holds N and D between the passes; scratch (ecm_disp_wls_scratch_bytes(B, H, W) bytes, a size query that
+ * needs no GPU: the c' plane) is written before it is read.  out and scratch must not overlap d, conf or guide.  No atomics, no
+ * workgroup waits for another: bit-reproducible.  Neither H nor W has an upper bound; B * H * W >= 2^31 returns ECM_EUNSUP before
+ * any launch.  ECM_EINVAL, before any device work: a null d / guide / out / scratch, B, H or W < 1, C outside 1..4, lam or
+ * sigma_color not finite and positive, iterations outside 1..8 (the size query: B, H or W < 1). */
+long long ecm_disp_wls_scratch_bytes(int B, int H, int W);
+int ecm_disp_wls_fwd(const float* d, const float* conf, const float* guide, float* out, void* scratch, int B, int C, int H, int W,
+                     float lam, float sigma_color, int iterations, void* stream);
+
 /* Harness loss + metrics (train.py:162,172-174; train_kitti.py:205-216) over n = B*H*W pixels; mask = 0 < gt < maxdisp.
  * out8 (device): [loss, #mask, epe(p3), err3(p3) in %, mean smooth-L1 of p1, p2, p3, 0];
  * loss = w1*m1 + w2*m2 + w3*m3 (reference weights 0.5 / 0.7 / 1.0).  Empty mask -> NaN (as the reference's empty mean).

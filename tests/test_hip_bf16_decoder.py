@@ -5,7 +5,10 @@ both in fp32 on the same bf16-rounded operands -- bf16 outputs within 1 bf16 ulp
 max |y| where a value is tiny), fp32 outputs within fp32 accumulation-order tolerance.  Decoder and whole model: the bf16
 disparities against the fp64 fixtures within 2x the mean and 4x the max distance of an EMULATION: the decoder's own bf16
 forward with every bf16 kernel replaced by the library's fp32 kernel on the same bf16 values, rounded where the bf16 kernel
-rounds."""
+rounds.
+
+The per-path numerical check of these kernels (every instantiation against fp64, once-rounded outputs, repeats on poisoned
+memory) is tests/test_hip_bf16_fp64.py with tests/test_bf16_geometry.py; the bars below are kept as they were."""
 import contextlib
 import time
 

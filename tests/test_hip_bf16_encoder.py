@@ -5,7 +5,10 @@ bf16-rounded operands -- bf16 outputs within 1 bf16 ulp of that yardstick rounde
 tiny), fp32 outputs within fp32 accumulation-order tolerance.  Whole models: the HIP bf16 disparities against a reference R (the
 fp64 fixtures where they exist, else the fp32 HIP output) within 2x the mean and 4x the max distance of an EMULATION: the
 library's fp32 kernels fed and followed by bf16 rounding at exactly the bf16 encoder's rounding points (the emulated maps ARE
-bf16 tensors between layers; every convolution and GroupNorm computes in fp32 on their values)."""
+bf16 tensors between layers; every convolution and GroupNorm computes in fp32 on their values).
+
+The per-path numerical check of these kernels (every instantiation against fp64, once-rounded outputs, repeats on poisoned
+memory) is tests/test_hip_bf16_fp64.py with tests/test_bf16_geometry.py; the bars below are kept as they were."""
 import contextlib
 import time
 

@@ -4,7 +4,10 @@ Kernel parity: every new kernel against the fp32 computation of the same bf16-ro
 F.group_norm in fp32 on MIOpen), within 1 bf16 ulp of that yardstick rounded to bf16 (or 1e-5 of the output's max |value| where
 cancellation makes a value tiny).  Whole models: the HIP bf16 disparities against a reference R (the fp64 fixtures where they
 exist, else the unmodified fp32 HIP output) within 2x the mean and 4x the max distance of an EMULATION -- the library's own
-fp32 path with bf16 rounding injected at exactly the new kernels' rounding points."""
+fp32 path with bf16 rounding injected at exactly the new kernels' rounding points.
+
+The per-path numerical check of these kernels (every instantiation against fp64, once-rounded outputs, repeats on poisoned
+memory) is tests/test_hip_bf16_fp64.py with tests/test_bf16_geometry.py; the bars below are kept as they were."""
 import contextlib
 import os
 import time

@@ -103,6 +103,8 @@ PROTOTYPES = {
     "ecm_disp_speckle_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "ecm_disp_wls_scratch_bytes": (_LL, [_I, _I, _I]),
     "ecm_disp_wls_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _I, _P]),
+    "ecm_disp_splat_max_width": (_I, []),
+    "ecm_disp_splat_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "ecm_gn3d_cluster_mode": (_I, [_I]),
     "ecm_gn3d_poll_ms": (_I, [_I]),
     "ecm_async_status": (_I, [_I]),

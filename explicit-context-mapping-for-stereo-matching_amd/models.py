@@ -15,6 +15,7 @@ Deliberate deviations (documented in DESIGN.md):
 from __future__ import annotations
 
 import collections
+import contextlib
 import math
 import numbers
 import os as _os
@@ -606,6 +607,30 @@ ModalPrediction = collections.namedtuple("ModalPrediction", "disparity std peak 
 # 2 mismatch, 3 out of view; a float plane) and the left disparity with the failures filled from the background.
 CrossCheck = collections.namedtuple("CrossCheck", "disparity disparity_right error kind filled")
 
+# Where the disparity_right of refine, despeckle and smooth comes from: "cross", a second forward on the
+# flipped and swapped pair (cross_check: the default), or "splat", the left disparity forward-warped into the right view
+# (self_check: one forward).  Chosen by the occlusion_check block below; cross_check and self_check themselves do not look at it.
+CHECKS = ("cross", "splat")
+_CHECK = "cross"
+
+
+@contextlib.contextmanager
+def occlusion_check(check):
+    """"cross" (the default; a no-op) or "splat": inside the block refine, despeckle and smooth of every model start from
+    self_check -- one forward and ops.disparity_splat -- instead of cross_check's two forwards, with self_check's limits: no
+    mismatch class, only the occlusions the left map's own geometry implies, up to one extra column at an occlusion edge, and an
+    effect on EPE or D1 that nobody has measured.  Anything else raises ValueError on entry, before any device work.  Nests and
+    restores the previous setting on exit."""
+    global _CHECK
+    if check not in CHECKS:
+        raise ValueError(f"occlusion_check: check {check!r}: one of {CHECKS}")
+    prev, _CHECK = _CHECK, check
+    try:
+        yield
+    finally:
+        _CHECK = prev
+
+
 # What _ECMNet.refine returns (DESIGN.md section 18): CrossCheck's five fields, bit for bit, then the masked median of `filled`
 # and the joint bilateral filter of that median guided by the left image, each [B,1,H,W].
 Refined = collections.namedtuple("Refined", "disparity disparity_right error kind filled median refined")
@@ -769,21 +794,38 @@ class _ECMNet(nn.Module):
         flipped forward's, flipped back once for the caller (the kernel reads the mirrored plane as it is).  Needs `forward`
         only, so every registered architecture has it.  threshold (pixels) and rel (a share of the disparity) as in
         ops.lr_check; head in 0..2."""
-        return self._cross_check(left, right, threshold, rel, head, False)[0]
+        return self._cross_check(left, right, threshold, rel, head, False, "cross")[0]
 
-    def _cross_check(self, left, right, threshold, rel, head, with_source):
-        """(the CrossCheck, src): cross_check's computation; src [B,H,W] int32, the column each pixel of `filled` was copied
-        from (its own where it is consistent, -1 for none), where with_source, else None."""
+    def self_check(self, left, right, threshold=1.0, rel=0.0, head=2):
+        """The one-forward stand-in for cross_check: one plain inference forward, ops.disparity_splat of its disparity -- the left
+        map forward-warped into the right view, the nearest surface winning -- and ops.lr_check(disparity, splat, threshold, rel,
+        mirrored=False).  Returns a CrossCheck: .disparity is bit-identical to forward's under torch.no_grad(), .disparity_right
+        is the splatted plane (0 where nothing landed), .error, .kind and .filled are lr_check's.  The limits: every finite
+        in-view pixel samples only columns it wrote to itself, so the interpolated r >= d, error = r - d >= 0 and kind 2
+        (mismatch) never occurs; the check sees the occlusions that the left map's own geometry implies and cannot see a wrong
+        match that the second forward would contradict; it marks up to one extra column at an occlusion edge, because the
+        foreground claims both neighbours of its landing point; and nobody has measured its effect on EPE or D1."""
+        return self._cross_check(left, right, threshold, rel, head, False, "splat")[0]
+
+    def _cross_check(self, left, right, threshold, rel, head, with_source, check=None):
+        """(the CrossCheck, src): cross_check's computation (check "cross") or self_check's ("splat"), the one occlusion_check
+        names where check is None: what refine, despeckle and smooth pass; src [B,H,W] int32, the column each pixel of `filled`
+        was copied from (its own where it is consistent, -1 for none), where with_source, else None."""
+        check = _CHECK if check is None else check
         if isinstance(head, bool) or not isinstance(head, numbers.Integral) or not 0 <= head <= 2:     # before any device work
             raise ValueError(f"cross_check: head {head!r}: one of 0, 1, 2")
         threshold, rel = ops.check_lr_tolerances(threshold, rel)
         with torch.no_grad():
             out = self(left, right)[head]
-            out_r = self(torch.flip(right, (-1,)), torch.flip(left, (-1,)))[head]
             if out.dim() == 3:
-                out, out_r = out.unsqueeze(1), out_r.unsqueeze(1)
-            error, kind, filled, *src = ops.lr_check(out, out_r, threshold, rel, mirrored=True, with_source=with_source)
-            cc = CrossCheck(out, torch.flip(out_r, (-1,)), error.unsqueeze(1), kind.unsqueeze(1), filled.unsqueeze(1))
+                out = out.unsqueeze(1)
+            if check == "splat":
+                out_r = right_view = ops.disparity_splat(out).unsqueeze(1)
+            else:
+                out_r = self(torch.flip(right, (-1,)), torch.flip(left, (-1,)))[head].reshape(out.shape)
+                right_view = torch.flip(out_r, (-1,))
+            error, kind, filled, *src = ops.lr_check(out, out_r, threshold, rel, mirrored=check == "cross", with_source=with_source)
+            cc = CrossCheck(out, right_view, error.unsqueeze(1), kind.unsqueeze(1), filled.unsqueeze(1))
             return cc, (src[0] if with_source else None)
 
     def refine(self, left, right, threshold=1.0, rel=0.0, head=2, median_radius=2, bilateral_radius=4, sigma_space=2.0,
@@ -794,7 +836,8 @@ class _ECMNet(nn.Module):
         the pixels with median > 0, guided by `left` as passed.  Returns a Refined: cross_check's five fields bit for bit, then
         .median and .refined, each [B,1,H,W].  median_radius=None skips the median (.median is .filled, and the bilateral reads
         it); bilateral_radius=None skips the bilateral (.refined is .median).  The defaults (5x5, 9x9, sigma 2 px, 0.25) are
-        plausible values for images normalised as the model consumes them; their effect on EPE or D1 has not been measured."""
+        plausible values for images normalised as the model consumes them; their effect on EPE or D1 has not been measured.
+        Inside an occlusion_check("splat") block it starts from self_check instead: one forward, with the limits stated there."""
         return self._refine(left, right, threshold, rel, head, median_radius, bilateral_radius, sigma_space, sigma_color, None, 1.0)
 
     def despeckle(self, left, right, threshold=1.0, rel=0.0, head=2, median_radius=2, bilateral_radius=4, sigma_space=2.0,
@@ -808,7 +851,8 @@ class _ECMNet(nn.Module):
         the same order, the first five cross_check's bit for bit, then .despeckled and .segment (int32: the size of each pixel's
         segment, 0 where it is not consistent), each [B,1,H,W].  speckle_size=None is refine itself: the same code path, results
         and return type (speckle_diff is not looked at).  200 pixels and 1.0 are the values customary with OpenCV; their effect
-        on EPE or D1 has not been measured either."""
+        on EPE or D1 has not been measured either.  Inside an occlusion_check("splat") block it starts from self_check instead of
+        cross_check (one forward, with the limits stated there)."""
         return self._refine(left, right, threshold, rel, head, median_radius, bilateral_radius, sigma_space, sigma_color,
                             speckle_size, speckle_diff)
 
@@ -845,7 +889,9 @@ class _ECMNet(nn.Module):
         `filled`, the median nor the bilateral filter is run: a hole is a pixel of confidence 0 and is written from as far away as
         the guide's edges allow.  Returns a Smoothed: cross_check's five fields bit for bit, then .confidence and .smoothed, each
         [B,1,H,W].  The defaults are untested for quality: 8000 and 3 are the values customary with OpenCV, 0.25 is the bilateral
-        filter's default in the units of `left`, 200 and 1.0 are despeckle's; nobody has measured their effect on EPE or D1."""
+        filter's default in the units of `left`, 200 and 1.0 are despeckle's; nobody has measured their effect on EPE or D1.
+        Inside an occlusion_check("splat") block it starts from self_check instead of cross_check (one forward, with the limits
+        stated there)."""
         lam, sigma_color, iterations = ops.check_wls_parameters(lam, sigma_color, iterations, "smooth")  # before any device work
         if speckle_size is not None:
             speckle_size, speckle_diff = ops.check_speckle_parameters(speckle_size, speckle_diff, "smooth")

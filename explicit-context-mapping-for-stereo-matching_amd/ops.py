@@ -802,6 +802,36 @@ def disparity_wls(disp, guide, confidence=None, lam=8000.0, sigma_color=0.25, it
     return (out[0], out[1]) if with_weight else out[0]
 
 
+# ------------------------------------------------------------------------------------ disparity splat
+# DESIGN.md section 21.  Forward only, one kernel: the left disparity forward-warped into the right view, nearest surface winning.
+def disparity_splat_max_width():
+    """The widest map disparity_splat takes (a size query of the library: no GPU needed)."""
+    return int(_lib.query("ecm_disp_splat_max_width"))
+
+
+@torch.no_grad()
+def disparity_splat(disp, with_source=False):
+    """The left-view disparity disp ([B,H,W] or [B,1,H,W], pixels) forward-warped into the right view, as a [B,H,W] plane: pixel x
+    with a finite d and x - d inside [0, W-1] lands on floor(x - d) and, where x - d is not integral, on the column after it -- the
+    columns lr_check reads for that pixel -- and per right-view column the largest disparity wins (the nearest surface; among
+    equal disparities the larger source column; -0.0 loses to +0.0).  The winner's disparity is copied bit for bit; a column on
+    which nothing landed (a hole) is 0.  with_source=True returns (right, src), src int32: the winner's left column, -1 for a hole.
+    Fed to lr_check(disp, right, mirrored=False) it marks the occlusions that disp's own geometry implies, from one inference:
+    every in-view pixel reads only columns it wrote to, so r >= d, error = r - d and kind 2 never occurs.  Integer maxima only:
+    bit-reproducible."""
+    _chk(disp)
+    if disp.dim() == 4 and disp.shape[1] == 1:
+        disp = disp[:, 0]
+    _need(disp.dim() == 3 and disp.numel() > 0, lambda: f"disparity_splat: disp {tuple(disp.shape)}: want a non-empty [B,H,W] or [B,1,H,W]")
+    B, H, W = disp.shape
+    d = _c(disp.detach())
+    right = torch.empty(B, H, W, device=d.device, dtype=d.dtype)
+    src = torch.empty(B, H, W, device=d.device, dtype=torch.int32) if with_source else None
+    # W beyond disparity_splat_max_width() is refused by the library before any launch (ECM_EUNSUP -> RuntimeError)
+    _lib.call("ecm_disp_splat_fwd", _p(d), _p(right), _p(src), B, H, W, _stream())
+    return (right, src) if with_source else right
+
+
 # ------------------------------------------------------------------------------------ a5-a7 conv / deconv / GN
 def _pack_conv(w, flip_transpose=False):
     Co, Ci = w.shape[0], w.shape[1]

@@ -521,6 +521,27 @@ long long ecm_disp_wls_scratch_bytes(int B, int H, int W);
 int ecm_disp_wls_fwd(const float* d, const float* conf, const float* guide, float* out, void* scratch, int B, int C, int H, int W,
                      float lam, float sigma_color, int iterations, void* stream);
 
+/* ABI 14: the forward warp ("splat") of a left disparity map into the right view: the right view's
+ * disparity, and with it the occlusions, from ONE inference instead of two.  dl [B,H,W] fp32: left-view disparity in pixels.
+ *   Candidate.  Pixel x of a row, d = dl[b,y,x], is a candidate iff d is finite and xr = (float)x - d, one fp32 subtraction, lies
+ *     in [0, W-1]: the in-view rule of ABI 10.  With f = floorf(xr) it lands on column x0 = (int)f and, if xr > f, also on
+ *     x1 = min(x0 + 1, W-1): exactly the one or two columns ecm_lr_check_fwd reads for that pixel.
+ *   Key.  A 64-bit unsigned word: the high 32 bits the order-preserving image of d's bits (every bit flipped if the sign bit is
+ *     set, else the sign bit set; unsigned order is then float order with -0.0 < +0.0), the low 32 bits the source column x.
+ *     Every finite float's image is >= 0x00800000, so the word 0 means that nothing landed.
+ *   Winner.  Per right-view column the candidate with the largest key: the largest disparity (the nearest surface), and among
+ *     equal disparities the larger source column.
+ *   right [B,H,W] fp32: the winner's disparity, bit for bit; 0.0 where nothing landed (a hole).  src (int [B,H,W], may be NULL):
+ *     the winner's left column, -1 for a hole.  right must not be dl (ECM_EINVAL).
+ * Fed to ecm_lr_check_fwd as dr (mirrored = 0), every candidate samples only columns it wrote to itself, so r >= d there: the
+ * error is r - d and kind 2 does not occur; what the check then marks are the occlusions that the left map's own geometry implies.
+ * One launch, a workgroup per row at a time, one 8-byte LDS word per column.  The only atomics are integer maxima in LDS: the
+ * result does not depend on the order of arrival and is bit-reproducible.  B, H, W >= 1 and non-null dl, right, else ECM_EINVAL;
+ * W > ecm_disp_splat_max_width() or B * H >= 2^31: ECM_EUNSUP, before any launch.  ecm_disp_splat_max_width is a size query (no
+ * GPU). */
+int ecm_disp_splat_max_width(void);
+int ecm_disp_splat_fwd(const float* dl, float* right, int* src, int B, int H, int W, void* stream);
+
 /* Harness loss + metrics (train.py:162,172-174; train_kitti.py:205-216) over n = B*H*W pixels; mask = 0 < gt < maxdisp.
  * out8 (device): [loss, #mask, epe(p3), err3(p3) in %, mean smooth-L1 of p1, p2, p3, 0];
  * loss = w1*m1 + w2*m2 + w3*m3 (reference weights 0.5 / 0.7 / 1.0).  Empty mask -> NaN (as the reference's empty mean).

@@ -94,6 +94,10 @@ PROTOTYPES = {
     "ecm_eval_epe": (_I, [_P, _P, _P, _P, _LL] + [_I] * 7 + [_F, _P]),
     "ecm_eval_kitti_scratch_bytes": (_LL, [_I, _I, _I]),
     "ecm_eval_kitti": (_I, [_P, _P, _P, _P, _P, _LL, _I, _I, _I, _F, _P]),
+    "ecm_eval_sparsify_max_measures": (_I, []),
+    "ecm_eval_sparsify_max_steps": (_I, []),
+    "ecm_eval_sparsify_scratch_bytes": (_LL, [_I] * 5),
+    "ecm_eval_sparsify": (_I, [_P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _I, _I, _F, _P]),
     "ecm_disp_to_u16": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _I, _F, _P]),
     "ecm_lr_check_max_width": (_I, []),
     "ecm_lr_check_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P]),

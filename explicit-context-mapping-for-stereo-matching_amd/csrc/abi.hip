@@ -1,5 +1,5 @@
 #include "common.h"
-extern "C" int ecm_abi_version(void) { return 14; }
+extern "C" int ecm_abi_version(void) { return 15; }
 extern "C" const char* ecm_error_string(int code) {
     switch (code) {
         case 0: return "success";

@@ -319,6 +319,55 @@ def evaluate_kitti(model: torch.nn.Module, batches, maxdisp: int = 192):
     return res
 
 
+def sparsification_dataset(table: torch.Tensor, count: torch.Tensor):
+    """Dataset-level curves from per-sample tables [N,K+1,steps,2] and counts [N,3] (ops.eval_sparsification's): the mean of the
+    per-sample curves over the samples with n > 0, and the areas formed from that mean, all in double.  -> dict of float64
+    tensors: epe, d1 [K,steps]; oracle_epe, oracle_d1 [steps]; ause_epe, ause_d1, aurg_epe, aurg_d1 [K]; samples = how many
+    images carried valid pixels (0: everything is NaN)."""
+    from . import ops
+    keep = count[:, 0] > 0
+    mean = table.double()[keep].mean(0)                                  # an empty selection gives NaN
+    K = table.shape[1] - 1
+    res = {"epe": mean[:K, :, 0], "d1": mean[:K, :, 1], "oracle_epe": mean[K, :, 0], "oracle_d1": mean[K, :, 1],
+           "samples": int(keep.sum())}
+    for key in ("epe", "d1"):
+        res["ause_" + key], res["aurg_" + key] = ops.sparsification_areas(res[key], res["oracle_" + key])
+    return res
+
+
+def evaluate_sparsification(model: torch.nn.Module, batches, head: int = 2, measures=("std", "entropy", "peak"), mode_radius=None,
+                            steps: int = 20, maxdisp: int = 192):
+    """model.sparsification over a validation set, modelled on evaluate_kitti: `batches` yields (left, right, disparity, ...); the
+    model runs under model.eval(), every batch's table and counts stay on the device, and the host synchronises once, when they
+    are read at the end.
+
+    -> dict:
+      table      float32 [n_samples, K+1, steps, 2]: (epe, d1) of each measure, in the order of `measures`, and of the oracle last,
+      count      int64 [n_samples, 3] = (n, E_tot, bad_tot) of each image,
+      dataset    sparsification_dataset of them.
+    With an initialised process group `batches` is this rank's shard; the tables and counts of all ranks are all-gathered (rank
+    order) into `table_all` and `count_all`, and `dataset` is formed from those: identical on every rank."""
+    model.eval()
+    tables, counts = [], []
+    for left, right, disparity, *_ in batches:
+        left, right, disparity = (t if t.is_cuda else t.cuda(non_blocking=True) for t in (left, right, disparity))
+        _, sp = model.sparsification(left, right, disparity, head, measures, mode_radius, steps, maxdisp)
+        tables.append(torch.cat([torch.stack([sp.epe, sp.d1], -1), torch.stack([sp.oracle_epe, sp.oracle_d1], -1).unsqueeze(1)], 1))
+        counts.append(sp.count)
+    if not tables:
+        raise RuntimeError("evaluate_sparsification: no batches")
+    table, count = torch.cat(tables).cpu(), torch.cat(counts).cpu()      # the one host synchronisation
+    res = {"table": table, "count": count}
+    if dist.is_available() and dist.is_initialized():
+        n = table.shape[0]
+        res["table_all"] = _all_gather_rows(table.reshape(n, -1)).reshape(-1, *table.shape[1:])
+        res["count_all"] = _all_gather_rows(count)
+        res["dataset"] = sparsification_dataset(res["table_all"], res["count_all"])
+    else:
+        res["dataset"] = sparsification_dataset(table, count)
+    return res
+
+
 class GraphedForward:
     """Inference through one captured HIP graph: the eval forward of a model is a fixed sequence of ~400 kernel launches
     (encoder + hot path, all on this library's kernels), which at batch 1 is partly launch-bound; capturing it once and

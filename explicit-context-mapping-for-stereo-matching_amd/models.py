@@ -602,6 +602,10 @@ Prediction = collections.namedtuple("Prediction", "disparity std peak entropy")
 # distribution (`mass`) and the highest level itself (`index`, pixels).  The first four fields are Prediction's, bit for bit.
 ModalPrediction = collections.namedtuple("ModalPrediction", "disparity std peak entropy mode mass index")
 
+# The fields of a prediction that _ECMNet.sparsification ranks the errors by: for the first two a higher
+# value means less trusted, the last two are negated; "mass" exists only with a mode_radius.
+SPARSIFICATION_MEASURES = ("std", "entropy", "peak", "mass")
+
 # What _ECMNet.cross_check returns, each field [B,1,H,W]: one head's disparity of the left view and of
 # the right view (in right-image coordinates), the left-right error (pixels), the failure class (0 consistent, 1 occluded,
 # 2 mismatch, 3 out of view; a float plane) and the left disparity with the failures filled from the background.
@@ -786,6 +790,29 @@ class _ECMNet(nn.Module):
                 kind, fields = ModalPrediction, tuple(fields) + tuple(_MODE_OP[self.HEAD](*args, mode_radius))
         last = fields[0].shape[0] - 1
         return kind(*(tuple(f[min(k, last)].unsqueeze(1) for k in heads) for f in fields))
+
+    def sparsification(self, left, right, gt, head=2, measures=("std", "entropy", "peak"), mode_radius=None, steps=20, maxdisp=192):
+        """Do the confidence outputs rank this net's errors?  One predict forward (with mode_radius, so that "mass" can be among
+        the measures when it is given) and ops.eval_sparsification of head `head`'s disparity against gt [B,H,W] with the named
+        fields as the measures -- "peak" and "mass" negated, since for those a higher value means MORE trusted.  Returns
+        (prediction, Sparsification): the prediction is predict(left, right, (head,), mode_radius), bit for bit; the curves and
+        areas are in the order of `measures`.  The curves say how well each measure orders the errors of THIS input; they say
+        nothing about how large the errors are, and with untrained weights nothing about which measure is best."""
+        if self.HEAD in _NO_DISTRIBUTION:                                # predict's refusal, before any device work
+            raise NotImplementedError(f"{type(self).__name__}.predict: {_NO_DISTRIBUTION[self.HEAD]}")
+        if isinstance(head, bool) or not isinstance(head, numbers.Integral) or not 0 <= head <= 2:
+            raise ValueError(f"sparsification: head {head!r}: one of 0, 1, 2")
+        measures = (measures,) if isinstance(measures, str) else tuple(measures)
+        known = SPARSIFICATION_MEASURES if mode_radius is not None else SPARSIFICATION_MEASURES[:3]
+        for name in measures:
+            if name not in known:
+                raise ValueError(f"sparsification: measure {name!r}: one of {known}" +
+                                 ("" if mode_radius is not None else ' ("mass" needs a mode_radius)'))
+        steps, maxdisp = ops.check_sparsification_parameters(len(measures), steps, maxdisp, "sparsification")
+        prediction = self.predict(left, right, (int(head),), mode_radius)
+        planes = [getattr(prediction, name)[0] for name in measures]
+        planes = [-m if name in ("peak", "mass") else m for name, m in zip(measures, planes)]
+        return prediction, ops.eval_sparsification(prediction.disparity[0], gt, planes, maxdisp, steps)
 
     def cross_check(self, left, right, threshold=1.0, rel=0.0, head=2):
         """The left-right consistency check of one head: two plain inference forwards -- (left, right), and the two images

@@ -6,6 +6,7 @@ through `_lib.call`.  There is no eager/CPU fallback: a non-CUDA tensor or a mis
 """
 from __future__ import annotations
 
+import collections
 import contextlib as _contextlib
 import ctypes as C
 import math
@@ -1877,6 +1878,77 @@ def eval_kitti(pred, gt, maxdisp=192, out=None, per_sample=False):
     _call_scratch(pred.device, "ecm_eval_kitti_scratch_bytes", (B, H, W), "ecm_eval_kitti", _p(pred), _p(gt), _p(out), _p(table),
                   _SCRATCH, B, H, W, C.c_float(maxdisp), _stream())
     return (out, table) if per_sample else out
+
+
+# DESIGN.md section 22.  What eval_sparsification returns: the curves of the K measures (epe in pixels, d1 in percent, each
+# [B,K,steps]) and of the oracle ([B,steps]) -- views of one table -- the areas between them ([B,K]: ause against the oracle, aurg
+# against random removal, whose curve is flat at the first point) and count [B,3] int64 = (n, E_tot, bad_tot).
+Sparsification = collections.namedtuple("Sparsification", "epe d1 oracle_epe oracle_d1 ause_epe ause_d1 aurg_epe aurg_d1 count")
+
+
+def eval_sparsification_limits():
+    """(the most measures, the most steps) eval_sparsification takes (size queries of the library: no GPU needed)."""
+    return int(_lib.query("ecm_eval_sparsify_max_measures")), int(_lib.query("ecm_eval_sparsify_max_steps"))
+
+
+def check_sparsification_parameters(n_measures, steps, maxdisp=192, who="eval_sparsification"):
+    """(steps, maxdisp): an int in 1..64 and a finite number > 0, with 1..8 measures."""
+    max_k, max_steps = eval_sparsification_limits()
+    if not 1 <= n_measures <= max_k:
+        raise ValueError(f"{who}: {n_measures} measures: 1..{max_k}")
+    if isinstance(steps, bool) or not isinstance(steps, numbers.Integral) or not 1 <= steps <= max_steps:
+        raise ValueError(f"{who}: steps {steps!r}: an integer in 1..{max_steps}")
+    if isinstance(maxdisp, bool) or not isinstance(maxdisp, numbers.Real) or not math.isfinite(maxdisp) or maxdisp <= 0:
+        raise ValueError(f"{who}: maxdisp {maxdisp!r}: a finite number > 0")
+    return int(steps), float(maxdisp)
+
+
+def sparsification_areas(curve, oracle):
+    """(ause, aurg) of curves [..., K, steps] against oracle [..., steps], in fp64: ause = mean_j(curve_j - oracle_j), the area
+    between a measure and the best possible ranking; aurg = mean_j(curve_0 - curve_j), the area random removal leaves above it."""
+    curve, oracle = curve.double(), oracle.double()
+    return (curve - oracle.unsqueeze(-2)).mean(-1), (curve[..., :1] - curve).mean(-1)
+
+
+@torch.no_grad()
+def eval_sparsification(pred, gt, measures, maxdisp=192, steps=20):
+    """Sparsification curves on the device: pred [B,1,H,W] or [B,H,W], gt [B,H,W], measures a sequence of 1..8 planes of pred's
+    shape in which a HIGHER value means LESS trusted (negate a confidence).  Per sample, over the pixels with 0 < gt < maxdisp: for
+    j = 0..steps-1 the r_j = floor(j n / steps) least trusted pixels are removed -- equal values leave pro rata, NaN first, -0.0 as
+    +0.0 -- and the mean |pred - gt| (epe) and the 3-px / 5 % error rate in percent (d1, eval_kitti's) of the rest are recorded;
+    the oracle removes the largest errors first (its d1: the bad pixels first).  -> Sparsification.  Errors enter the sums as
+    integers, rintf(min(e, 4095) * 65536): every mean is within 2^-17 px of the exact one, errors above 4095 px (and NaN) count as
+    4095, and the result is bit-reproducible and the same whatever else is in the batch.  Exact on the full 32-bit value of a
+    measure: a radix selection of the `steps` cut ranks, not a sort.  A sample without valid pixels gives NaN rows.  The areas
+    are formed in fp64 from the table by torch ops and cast to fp32.  Nothing here synchronises with the host.
+    Limits: H * W < 2^31, B <= 65535, 1..8 measures, steps in 1..64."""
+    measures = list(measures)
+    steps, maxdisp = check_sparsification_parameters(len(measures), steps, maxdisp)         # before any device work
+    _chk(pred, gt, *measures)
+    if pred.dim() == 4 and pred.shape[1] == 1:
+        pred = pred[:, 0]
+    _need(pred.dim() == 3 and pred.shape == gt.shape and pred.numel() > 0,
+          lambda: f"eval_sparsification: pred {tuple(pred.shape)} / gt {tuple(gt.shape)}: want the same non-empty [B,H,W]")
+    B, H, W = pred.shape
+    planes = []
+    for k, m in enumerate(measures):
+        if m.dim() == 4 and m.shape[1] == 1:
+            m = m[:, 0]
+        _need(m.shape == pred.shape, lambda: f"eval_sparsification: measure {k} {tuple(m.shape)} against pred {tuple(pred.shape)}")
+        planes.append(m.detach().contiguous())
+    if H * W >= 1 << 31 or B > 65535:
+        raise ValueError(f"eval_sparsification: {B} x {H} x {W}: H * W < 2^31 and B <= 65535")
+    pred, gt = pred.detach().contiguous(), gt.detach().contiguous()      # any 4-byte alignment: the kernel picks its load width
+    K = len(planes)
+    table = torch.empty(B, K + 1, steps, 2, device=pred.device, dtype=torch.float32)
+    count = torch.empty(B, 3, device=pred.device, dtype=torch.int64)
+    ptrs = (C.c_void_p * K)(*(m.data_ptr() for m in planes))
+    _call_scratch(pred.device, "ecm_eval_sparsify_scratch_bytes", (B, H, W, K, steps), "ecm_eval_sparsify", _p(pred), _p(gt), ptrs,
+                  _p(table), _p(count), _SCRATCH, B, H, W, K, steps, C.c_float(maxdisp), _stream())
+    epe, d1, oracle_epe, oracle_d1 = table[:, :K, :, 0], table[:, :K, :, 1], table[:, K, :, 0], table[:, K, :, 1]
+    ause_epe, aurg_epe = sparsification_areas(epe, oracle_epe)
+    ause_d1, aurg_d1 = sparsification_areas(d1, oracle_d1)
+    return Sparsification(epe, d1, oracle_epe, oracle_d1, ause_epe.float(), ause_d1.float(), aurg_epe.float(), aurg_d1.float(), count)
 
 
 def disparity_to_uint16(pred, h, w, scale=256.0):

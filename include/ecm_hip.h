@@ -424,6 +424,32 @@ long long ecm_eval_kitti_scratch_bytes(int B, int H, int W);
 int ecm_eval_kitti(const float* pred, const float* gt, float* out8, float* per_sample, void* scratch, long long scratch_bytes,
                    int B, int H, int W, float maxdisp, void* stream);
 
+/* ABI 15: sparsification curves of K confidence planes and of the oracle, per sample.  Nothing in the
+ * reference corresponds to it.  pred, gt [B,H,W] fp32; measures: a HOST array of K device pointers, each a [B,H,W] fp32 plane in
+ * which a HIGHER value means LESS trusted.  Per sample:
+ *   valid    0 < gt < maxdisp; n valid pixels.
+ *   error    e = |pred - gt| in fp32, entering every sum as the integer E = rintf(min(e, 4095) * 65536) (a NaN e takes the clamp;
+ *            E < 2^28, the scaling is exact, a mean moves by at most 2^-17 px); bad = not (e < 3 or e < 0.05f * gt).
+ *   key      of a measure value: its order-preserving 32-bit image (all bits flipped if the sign bit is set, else the sign bit
+ *            set), -0.0 taken as +0.0, any NaN 0xFFFFFFFF (removed first).  Plane K, the oracle, has the key E.
+ *   cuts     r_j = floor(j * n / steps), j = 0..steps-1.  With the valid pixels grouped by equal key and ranked from the highest
+ *            key down, A = the groups strictly above the group (c, E_t, bad_t) that holds rank r_j, t = r_j - n_A; in fp64, in
+ *            this order:  remE = (E_tot - E_A) - t * E_t / c;  rembad = (bad_tot - bad_A) - t * bad_t / c  (ties leave pro rata);
+ *            epe_j = (float)(remE / (n - r_j) / 65536);  d1_j = (float)(100 * rembad / (n - r_j)).
+ * table (device) fp32 [B, K+1, steps, 2] = (epe_j, d1_j); plane K is the oracle, whose d1 column holds the closed form
+ * (float)(100 * (bad_tot - min(r_j, bad_tot)) / (n - r_j)).  count (device) int64 [B,3] = (n, E_tot, bad_tot).  n = 0: NaN rows.
+ * Exact on the full 32-bit key (a radix selection, four digits of 8 bits; nothing is sorted).  Integer accumulation only (integer
+ * atomics commute): bit-reproducible, and row b does not depend on the other samples.  16-byte loads when W % 4 == 0 and pred,
+ * gt and every plane are 16-byte aligned; any 4-byte alignment works.  scratch: 8-byte aligned, ecm_eval_sparsify_scratch_bytes
+ * (0 for sizes outside the limits); too small: ECM_ESCRATCH and nothing is launched.  B, H, W, K, steps >= 1, else ECM_EINVAL;
+ * H * W >= 2^31, B > 65535, K > ecm_eval_sparsify_max_measures() (8) or steps > ecm_eval_sparsify_max_steps() (64): ECM_EUNSUP.
+ * The three queries need no GPU. */
+int ecm_eval_sparsify_max_measures(void);
+int ecm_eval_sparsify_max_steps(void);
+long long ecm_eval_sparsify_scratch_bytes(int B, int H, int W, int K, int steps);
+int ecm_eval_sparsify(const float* pred, const float* gt, const float* const* measures, float* table, long long* count,
+                      void* scratch, long long scratch_bytes, int B, int H, int W, int K, int steps, float maxdisp, void* stream);
+
 /* KITTI submission image (test_kitti.py:163-168): out[b,y,x] = (uint16)(pred[b, Hp-h[b]+y, Wp-w[b]+x] * scale) for
  * y < h[b], x < w[b] (the loader padded at the top and left), 0 elsewhere; scale = 256.  The cast is numpy's on the
  * reference's host: truncation toward zero, low 16 bits of the 32-bit integer, 0 for NaN / out-of-int32-range values.

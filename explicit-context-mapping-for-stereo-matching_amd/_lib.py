@@ -1,7 +1,9 @@
 """ctypes binding of libecm_hip.so (the C ABI declared in include/ecm_hip.h).
 
 The product path has NO fallback: if the library is missing or a call fails, a RuntimeError is
-raised.  Prototypes below mirror include/ecm_hip.h one to one (checked by tests/test_abi.py).
+raised.  Prototypes below mirror include/ecm_hip.h one to one: tests/test_abi_types.py parses the header and compares every
+return type and every parameter type, in order; tests/test_abi.py compares the names with the built library's exports; and
+tests/test_hip_abi_calls.py checks the values that ops.py hands to them on the device.
 """
 from __future__ import annotations
 

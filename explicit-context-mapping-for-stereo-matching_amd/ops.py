@@ -70,6 +70,15 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _host(ctype, values):
+    """A HOST array parameter of the ABI (`const int*`, `const float*`, `const float* const*`) as the c_void_p its prototype
+    declares; None for values None.  The pointer keeps the array it points into alive."""
+    if values is None:
+        return None
+    values = list(values)
+    return C.cast((ctype * len(values))(*values), C.c_void_p)
+
+
 def _chk(*ts):
     for t in ts:
         if t is None:
@@ -354,11 +363,11 @@ class ContextWeights(torch.autograd.Function):
         glr, ghr = _empty_like(lr), _empty_like(hr)
         gW = torch.empty(sum(_ECM_MLP_SIZES), device=lr.device, dtype=lr.dtype)
         if variant == 0:
-            name, tail, zero = "ecm_weights9_bwd", (s,), None
+            query, name, tail, zero = "ecm_weights9_bwd_scratch_bytes", "ecm_weights9_bwd", (s,), None
         else:
-            name, tail = "ecm_context_weights_bwd", (s, variant)
+            query, name, tail = "ecm_context_weights_bwd_scratch_bytes", "ecm_context_weights_bwd", (s, variant)
             zero = f"context_weights backward: unsupported scale {s} (the registered architectures' scales are 4, 8, 16)"
-        _call_scratch(lr.device, name + "_scratch_bytes", (B, h, w) + tail, name, _p(lr), _p(hr), _p(W0), _p(W1), _p(W2), _p(W3),
+        _call_scratch(lr.device, query, (B, h, w) + tail, name, _p(lr), _p(hr), _p(W0), _p(W1), _p(W2), _p(W3),
                       _p(out), _p(g), _p(glr), _p(ghr), _p(gW), _SCRATCH, B, h, w, *tail, _stream(), zero=zero)
         return (glr, ghr, gW[:2112].view_as(W0), gW[2112:2624].view_as(W1), gW[2624:2752].view_as(W2),
                 gW[2752:].view_as(W3), None)
@@ -1674,7 +1683,7 @@ def _gn_fwd(x, gamma, beta, skip, relu):
     stats = torch.empty(x.shape[0], GN_GROUPS, 2, device=x.device, dtype=x.dtype)
     y = _empty_like(x)
     _gn_launch("ecm_gn3d_fwd", "ecm_gn3d_fwd_p", x, (_p(x), _p(gamma), _p(beta), _p(skip), _p(y), _p(stats)),
-               (int(relu), C.c_float(GN_EPS)))
+               (int(relu), float(GN_EPS)))
     return y, stats
 
 
@@ -1808,9 +1817,9 @@ def _frame_prep(frames, crop_y0, crop_x0, th, tw, split, tail, mean, std, want_i
             raise RuntimeError(f"frame_prep expects [B,H,W,7] frames (left RGB, right RGB, disparity), got {tuple(frames.shape)}")
         dev = frames.device
     split = th if split is None else int(split)
-    ys = (C.c_int * B)(*[int(v) for v in crop_y0]) if crop_y0 is not None else None
-    xs = (C.c_int * B)(*[int(v) for v in crop_x0]) if crop_x0 is not None else None
-    m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    ys = _host(C.c_int, [int(v) for v in crop_y0] if crop_y0 is not None else None)
+    xs = _host(C.c_int, [int(v) for v in crop_x0] if crop_x0 is not None else None)
+    m3, s3 = _host(C.c_float, mean), _host(C.c_float, std)
     left = torch.empty(B, 3, th, tw, device=dev, dtype=torch.float32)
     right = torch.empty_like(left)
     disp = torch.empty(B, th, tw, device=dev, dtype=torch.float32)
@@ -1854,7 +1863,7 @@ def eval_epe(pred, gt, crop_h=540, crop_w=960, maxdisp=192, out=None):
     out = _out_row(out, 6, pred.device)
     n = B * int(crop_h) * int(crop_w)
     _call_scratch(pred.device, "ecm_eval_epe_scratch_bytes", (C.c_longlong(n),), "ecm_eval_epe", _p(pred), _p(gt), _p(out),
-                  _SCRATCH, B, Hp, Wp, Hg, Wg, int(crop_h), int(crop_w), C.c_float(maxdisp), _stream())
+                  _SCRATCH, B, Hp, Wp, Hg, Wg, int(crop_h), int(crop_w), float(maxdisp), _stream())
     return out
 
 
@@ -1876,7 +1885,7 @@ def eval_kitti(pred, gt, maxdisp=192, out=None, per_sample=False):
     out = _out_row(out, 8, pred.device)
     table = torch.empty(B, 8, device=pred.device, dtype=torch.float32) if per_sample else None
     _call_scratch(pred.device, "ecm_eval_kitti_scratch_bytes", (B, H, W), "ecm_eval_kitti", _p(pred), _p(gt), _p(out), _p(table),
-                  _SCRATCH, B, H, W, C.c_float(maxdisp), _stream())
+                  _SCRATCH, B, H, W, float(maxdisp), _stream())
     return (out, table) if per_sample else out
 
 
@@ -1942,9 +1951,9 @@ def eval_sparsification(pred, gt, measures, maxdisp=192, steps=20):
     K = len(planes)
     table = torch.empty(B, K + 1, steps, 2, device=pred.device, dtype=torch.float32)
     count = torch.empty(B, 3, device=pred.device, dtype=torch.int64)
-    ptrs = (C.c_void_p * K)(*(m.data_ptr() for m in planes))
+    ptrs = _host(C.c_void_p, (m.data_ptr() for m in planes))
     _call_scratch(pred.device, "ecm_eval_sparsify_scratch_bytes", (B, H, W, K, steps), "ecm_eval_sparsify", _p(pred), _p(gt), ptrs,
-                  _p(table), _p(count), _SCRATCH, B, H, W, K, steps, C.c_float(maxdisp), _stream())
+                  _p(table), _p(count), _SCRATCH, B, H, W, K, steps, float(maxdisp), _stream())
     epe, d1, oracle_epe, oracle_d1 = table[:, :K, :, 0], table[:, :K, :, 1], table[:, K, :, 0], table[:, K, :, 1]
     ause_epe, aurg_epe = sparsification_areas(epe, oracle_epe)
     ause_d1, aurg_d1 = sparsification_areas(d1, oracle_d1)
@@ -1964,8 +1973,8 @@ def disparity_to_uint16(pred, h, w, scale=256.0):
     ws = [int(w)] * B if isinstance(w, int) else [int(v) for v in w]
     Ho, Wo = max(hs), max(ws)
     out = torch.empty(B, Ho, Wo, device=pred.device, dtype=torch.uint16)
-    _lib.call("ecm_disp_to_u16", _p(pred), _p(out), B, Hp, Wp, (C.c_int * B)(*hs), (C.c_int * B)(*ws), Ho, Wo,
-              C.c_float(scale), _stream())
+    _lib.call("ecm_disp_to_u16", _p(pred), _p(out), B, Hp, Wp, _host(C.c_int, hs), _host(C.c_int, ws), Ho, Wo,
+              float(scale), _stream())
     return out
 
 
@@ -1983,8 +1992,8 @@ class StereoLoss3(torch.autograd.Function):
         n = gt.numel()
         out = torch.empty(8, device=gt.device, dtype=gt.dtype)
         _call_scratch(gt.device, "ecm_stereo_loss_scratch_bytes", (C.c_longlong(n),), "ecm_stereo_loss_fwd",
-                      _p(p1), _p(p2), _p(p3), _p(gt), _p(out), _SCRATCH, C.c_longlong(n), C.c_float(maxdisp), C.c_float(w1),
-                      C.c_float(w2), C.c_float(w3), _stream())
+                      _p(p1), _p(p2), _p(p3), _p(gt), _p(out), _SCRATCH, C.c_longlong(n), float(maxdisp), float(w1),
+                      float(w2), float(w3), _stream())
         ctx.save_for_backward(p1, p2, p3, gt, out)
         ctx.cfg = (float(maxdisp), float(w1), float(w2), float(w3))
         ctx.mark_non_differentiable(out)
@@ -1997,7 +2006,7 @@ class StereoLoss3(torch.autograd.Function):
         gloss = _c(gloss.reshape(1).to(gt.dtype))
         g1, g2, g3 = _empty_like(p1), _empty_like(p2), _empty_like(p3)
         _lib.call("ecm_stereo_loss_bwd", _p(p1), _p(p2), _p(p3), _p(gt), _p(out), _p(gloss), _p(g1), _p(g2), _p(g3),
-                  C.c_longlong(gt.numel()), C.c_float(maxdisp), C.c_float(w1), C.c_float(w2), C.c_float(w3), _stream())
+                  C.c_longlong(gt.numel()), float(maxdisp), float(w1), float(w2), float(w3), _stream())
         return g1, g2, g3, None, None, None, None, None
 
 
@@ -2250,7 +2259,7 @@ def _gn_stats(x):
     stats = torch.empty(B, GN_GROUPS, 2, device=x.device, dtype=torch.float32)
     name = "ecm_gn3d_stats_bf16" if x.dtype == torch.bfloat16 else "ecm_gn3d_stats"
     _call_scratch(x.device, "ecm_gn3d_scratch_bytes", (B, Cc, C.c_longlong(S)), name, _p(x), _p(stats), _SCRATCH,
-                  B, Cc, C.c_longlong(S), C.c_float(GN_EPS), _stream(), call=_gn_call)
+                  B, Cc, C.c_longlong(S), float(GN_EPS), _stream(), call=_gn_call)
     return stats
 
 

@@ -1,5 +1,6 @@
 """CPU-side checks of the C ABI: libecm_hip.so loads (no GPU needed to dlopen it), exports every symbol that
-include/ecm_hip.h declares, and the ctypes prototypes cover exactly that set.  No compute calls."""
+include/ecm_hip.h declares, and the ctypes prototypes cover exactly that set (their types: tests/test_abi_types.py).  No compute
+calls."""
 import ctypes
 import os
 import re
@@ -60,9 +61,13 @@ def test_size_queries_need_no_gpu(lib_mod):
 
 
 def test_null_pointers_are_rejected_without_touching_the_gpu(lib_mod):
-    lib = lib_mod.load()
-    assert lib.ecm_costvol_concat_fwd(None, None, None, 1, 1, 1, 1, 1, None) == -1
-    assert lib.ecm_conv3d_k3_fwd(None, None, None, 1, 32, 32, 4, 4, 4, 1, None) == -1
+    from test_abi_types import header_prototypes
+    lib, parsed = lib_mod.load(), header_prototypes()
+    for name, sizes in (("ecm_costvol_concat_fwd", (1, 1, 1, 1, 1)), ("ecm_conv3d_k3_fwd", (1, 32, 32, 4, 4, 4, 1))):
+        res, params = parsed[name]                            # the argument list is laid out by the header, not counted by hand
+        assert res is ctypes.c_int and [t for t in params if t is not ctypes.c_void_p] == [ctypes.c_int] * len(sizes), (name, params)
+        ints = iter(sizes)
+        assert getattr(lib, name)(*[None if t is ctypes.c_void_p else next(ints) for t in params]) == -1, name
 
 
 def test_product_path_refuses_cpu_tensors():

@@ -1,4 +1,4 @@
-"""ctypes binding of libecm_hip.so (the C ABI declared in include/ecm_hip.h).
+"""ctypes binding of libecm_hip.so (the C ABI declared in include/ecm_hip.h and, for the geometry entries, include/ecm_geometry.h).
 
 The product path has NO fallback: if the library is missing or a call fails, a RuntimeError is
 raised.  Prototypes below mirror include/ecm_hip.h one to one: tests/test_abi_types.py parses the header and compares every
@@ -145,6 +145,16 @@ PROTOTYPES = {
     "ecm_deconv3d_k3s2_split_fwd": (_I, [_P, _P, _P] + [_I] * 9 + [_P]),     # cmfsm.py:262-268
 }
 
+# The geometry entries (include/ecm_geometry.h, prefix ecmg_): a table of their own, held to their own header by
+# tests/test_disp_reproject_cpu.py.  PROTOTYPES stays the image of include/ecm_hip.h (the network and its post-filters); call(),
+# query() and missing_symbols() serve both.
+GEOMETRY_PROTOTYPES = {
+    "ecmg_reproject_fwd": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _F, _F, _P]),
+    "ecmg_point_cloud_tile": (_I, []),
+    "ecmg_point_cloud_scratch_bytes": (_LL, [_I, _I, _I]),
+    "ecmg_point_cloud_fwd": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _F, _F, _P]),
+}
+
 _lib = None
 
 
@@ -157,7 +167,7 @@ def load():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or `make -C explicit-context-mapping-for-stereo-matching_amd/csrc`). There is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in PROTOTYPES.items():
+        for name, (res, args) in list(PROTOTYPES.items()) + list(GEOMETRY_PROTOTYPES.items()):
             fn = getattr(lib, name, None)
             if fn is None:
                 continue            # reported by missing_symbols()/tests; calling it raises below
@@ -168,7 +178,7 @@ def load():
 
 def missing_symbols():
     lib = load()
-    return [n for n in PROTOTYPES if not hasattr(lib, n)]
+    return [n for n in list(PROTOTYPES) + list(GEOMETRY_PROTOTYPES) if not hasattr(lib, n)]
 
 
 # Optional per-launch timing (bench.py's roofline leg): name -> list of (start_event, end_event, int_args).

@@ -649,6 +649,14 @@ Despeckled = collections.namedtuple("Despeckled", Refined._fields + ("despeckled
 # the WLS-smoothed disparity, each [B,1,H,W].
 Smoothed = collections.namedtuple("Smoothed", CrossCheck._fields + ("confidence", "smoothed"))
 
+# What _ECMNet.point_cloud returns: the packed cloud [N, 3 + C] and its offsets [B + 1] (int64), the dense
+# point map [B,3,H,W] and its mask [B,H,W] (bool), and `stage`: the result of the entry point named by `source`, bit for bit.
+PointCloud = collections.namedtuple("PointCloud", "points offsets xyz mask stage")
+
+# source -> the field of that entry point's result that is reprojected (None: head 2 of forward's tuple, every pixel valid)
+POINT_CLOUD_SOURCES = {"forward": None, "self_check": "filled", "cross_check": "filled", "refine": "refined", "despeckle": "refined",
+                       "smooth": "smoothed"}
+
 _NO_DISTRIBUTION = {
     "five": "the full-resolution disparity of this head is a sum of low-resolution disparities weighted by softmax * logit planes: "
             "signed weights that do not sum to one, so it is not the mean of any distribution over disparities",
@@ -931,6 +939,30 @@ class _ECMNet(nn.Module):
             confidence = confident.to(torch.float32)
             smoothed = ops.disparity_wls(cc.disparity, left, confidence, lam, sigma_color, iterations).unsqueeze(1)
             return Smoothed(*cc, confidence, smoothed)
+
+    def point_cloud(self, left, right, Q, colors=None, source="smooth", min_disp=0.0, max_disp=None, **stage_args):
+        """From the image pair to geometry: the entry point named by `source` -- "forward", "self_check", "cross_check", "refine",
+        "despeckle" or "smooth", called with stage_args -- then ops.point_cloud of its final plane (head 2 of forward; .filled,
+        .refined or .smoothed of the others) with the matrix Q (ops.q_matrix), over the pixels where that plane is > 0 (every
+        pixel for "forward"; a hole of the chains is 0) and min_disp < d <= max_disp.  colors ([B,C,H,W] fp32, C <= 4; None: no
+        attributes; `left` gives XYZRGB rows in the normalisation the model consumes) is gathered beside the coordinates.
+        Returns a PointCloud: .points [N, 3 + C], .offsets [B + 1], .xyz [B,3,H,W], .mask [B,H,W] and .stage, the entry point's
+        own result bit for bit.  It calls the same methods, so an occlusion_check("splat") block applies; it needs `forward`
+        only, so every registered architecture has it.  An unknown source, a bad Q or bound raises ValueError before any device
+        work.  The defaults say nothing about EPE or D1, and Q's sign conventions are the caller's."""
+        if not isinstance(source, str) or source not in POINT_CLOUD_SOURCES:                          # before any device work
+            raise ValueError(f"point_cloud: source {source!r}: one of {tuple(POINT_CLOUD_SOURCES)}")
+        n_colors = colors.shape[1] if isinstance(colors, torch.Tensor) and colors.dim() == 4 else 0
+        ops.check_reproject_parameters(Q, min_disp, max_disp, n_colors, "point_cloud")
+        with torch.no_grad():
+            if source == "forward":
+                stage = self(left, right, **stage_args)
+                plane, valid = stage[2], None
+            else:
+                stage = getattr(self, source)(left, right, **stage_args)
+                plane = getattr(stage, POINT_CLOUD_SOURCES[source])
+                valid = plane > 0
+            return PointCloud(*ops.point_cloud(plane, Q, colors, valid, min_disp, max_disp, with_dense=True), stage)
 
 
 class cmfsm(_ECMNet):

@@ -842,6 +842,124 @@ def disparity_splat(disp, with_source=False):
     return (right, src) if with_source else right
 
 
+# ------------------------------------------------------------------------------------ disparity reprojection
+# DESIGN.md section 23; include/ecm_geometry.h.  Forward only: [X Y Z W]^T = Q [x y d 1]^T in fp64 on the device, the point
+# (X/W, Y/W, Z/W) rounded once to fp32 -- OpenCV's reprojectImageTo3D -- as a dense map and as a packed cloud.
+REPROJECT_MAX_ATTRIBUTES = 4
+_FLT_MAX = 3.4028234663852886e38
+
+
+def q_matrix(focal, baseline, cx, cy, cx_right=None, x0=0, y0=0):
+    """The 4x4 disparity-to-depth matrix of a rectified pair, in stereoRectify's form with a POSITIVE baseline, as a float64 CPU
+    tensor: rows [1,0,0,-(cx-x0)], [0,1,0,-(cy-y0)], [0,0,0,f], [0,0,1/b,-(cx-cx_right)/b], so that Z = f b / (d - (cx - cx_right)),
+    X = (x + x0 - cx) Z / f and Y = (y + y0 - cy) Z / f.  focal and the principal point (cx, cy; cx_right: the right camera's, None
+    for the same) are in pixels of the full frame, baseline in the unit the points come out in; (x0, y0) is the origin of the crop
+    that the disparity map covers (what frame_prep was given as crop_x0, crop_y0)."""
+    vals = {"focal": focal, "baseline": baseline, "cx": cx, "cy": cy, "cx_right": cx if cx_right is None else cx_right, "x0": x0, "y0": y0}
+    for name, v in vals.items():
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v):
+            raise ValueError(f"q_matrix: {name} {v!r}: a finite number")
+    if focal <= 0 or baseline <= 0:
+        raise ValueError(f"q_matrix: focal {focal!r} and baseline {baseline!r}: both > 0")
+    f, b = float(focal), float(baseline)
+    return torch.tensor([[1.0, 0.0, 0.0, float(x0) - float(cx)],
+                         [0.0, 1.0, 0.0, float(y0) - float(cy)],
+                         [0.0, 0.0, 0.0, f],
+                         [0.0, 0.0, 1.0 / b, (float(vals["cx_right"]) - float(cx)) / b]], dtype=torch.float64)
+
+
+def check_reproject_parameters(Q, min_disp=0.0, max_disp=None, n_attributes=0, who="disparity_reproject"):
+    """(min_disp, max_disp) as the two floats the library takes, after refusing -- before any device work -- a Q that is not a
+    floating-point [4,4] or [B,4,4] tensor or, where it lies on the CPU, has a non-finite entry (a Q already on the device is not
+    read back: its entries are the caller's), a min_disp that is not a finite fp32 value, a max_disp below it, and more than four
+    attribute planes.  max_disp None or beyond the largest float is that float: a usable disparity is finite."""
+    if not isinstance(Q, torch.Tensor) or not Q.is_floating_point() or Q.dim() not in (2, 3) or tuple(Q.shape[-2:]) != (4, 4) \
+            or Q.shape[0] < 1:
+        what = f"{tuple(Q.shape)} {Q.dtype}" if isinstance(Q, torch.Tensor) else type(Q).__name__
+        raise ValueError(f"{who}: Q {what}: a floating-point [4,4] or [B,4,4] tensor")
+    if not Q.is_cuda and not bool(torch.isfinite(Q).all()):
+        raise ValueError(f"{who}: Q has a non-finite entry")
+    if isinstance(min_disp, bool) or not isinstance(min_disp, numbers.Real) or not math.isfinite(min_disp) or abs(min_disp) > _FLT_MAX:
+        raise ValueError(f"{who}: min_disp {min_disp!r}: a finite number")
+    if max_disp is None:
+        max_disp = _FLT_MAX
+    if isinstance(max_disp, bool) or not isinstance(max_disp, numbers.Real) or not max_disp >= min_disp:
+        raise ValueError(f"{who}: max_disp {max_disp!r}: None or a number >= min_disp ({min_disp!r})")
+    if not 0 <= n_attributes <= REPROJECT_MAX_ATTRIBUTES:
+        raise ValueError(f"{who}: {n_attributes} attribute planes: at most {REPROJECT_MAX_ATTRIBUTES}")
+    return float(min_disp), min(float(max_disp), _FLT_MAX)
+
+
+def _reproject_operands(who, disp, Q, attributes, valid, min_disp, max_disp):
+    """Every refusal of the two ops, then the operands: (d, v, q, per_image, a, lo, hi); q the float64 device copy of Q."""
+    if attributes is not None:
+        _need(isinstance(attributes, torch.Tensor) and attributes.dim() == 4,
+              lambda: f"{who}: attributes {tuple(getattr(attributes, 'shape', ()))}: want [B,C,H,W]")
+    lo, hi = check_reproject_parameters(Q, min_disp, max_disp, 0 if attributes is None else attributes.shape[1], who)
+    d, v = _filter_planes(who, disp, valid)
+    B, H, W = d.shape
+    if Q.dim() == 3 and Q.shape[0] != B:
+        raise ValueError(f"{who}: Q {tuple(Q.shape)} against disp {tuple(d.shape)}: one matrix, or one per image")
+    a = None
+    if attributes is not None and attributes.shape[1] > 0:
+        _chk(attributes)
+        _need(attributes.shape[0] == B and tuple(attributes.shape[2:]) == (H, W),
+              lambda: f"{who}: attributes {tuple(attributes.shape)} against disp {tuple(d.shape)}: want [B,C,H,W]")
+        a = _c(attributes.detach())
+    q = Q.detach().to(device=d.device, dtype=torch.float64).contiguous()
+    return d, v, q, int(Q.dim() == 3), a, lo, hi
+
+
+@torch.no_grad()
+def disparity_reproject(disp, Q, valid=None, min_disp=0.0, max_disp=None, with_mask=False):
+    """The 3-D point of every pixel of disp ([B,H,W] or [B,1,H,W], pixels) as xyz [B,3,H,W]: [X Y Z W]^T = Q [x y d 1]^T in fp64
+    and (X/W, Y/W, Z/W), each rounded once to fp32 (OpenCV's reprojectImageTo3D; Q: [4,4] or [B,4,4], on the CPU or the device,
+    any float dtype, converted once to float64 on the device; ops.q_matrix builds one).  A pixel is usable where d is finite,
+    valid != 0 (bool or uint8 of disp's shape; None: all ones), min_disp < d <= max_disp (fp32; None: no upper bound) and W is
+    finite and non-zero; every other pixel is +0.0 in all three planes.  with_mask=True returns (xyz, mask), mask bool [B,H,W].
+    One launch, no atomics: bit-reproducible.  The defaults say nothing about EPE or D1, and Q's sign conventions are the
+    caller's."""
+    d, v, q, per_image, _, lo, hi = _reproject_operands("disparity_reproject", disp, Q, None, valid, min_disp, max_disp)
+    B, H, W = d.shape
+    xyz = torch.empty(B, 3, H, W, device=d.device, dtype=d.dtype)
+    mask = torch.empty(B, H, W, device=d.device, dtype=torch.uint8) if with_mask else None
+    # B * H * W >= 2^31 is refused by the library before any launch (ECM_EUNSUP -> RuntimeError)
+    _lib.call("ecmg_reproject_fwd", _p(d), _p(v), _p(q), per_image, _p(xyz), _p(mask), B, H, W, lo, hi, _stream())
+    return (xyz, mask.view(torch.bool)) if with_mask else xyz
+
+
+def point_cloud_tile():
+    """The pixels of one compaction tile of point_cloud (a size query of the library: no GPU needed)."""
+    return int(_lib.query("ecmg_point_cloud_tile"))
+
+
+@torch.no_grad()
+def point_cloud(disp, Q, attributes=None, valid=None, min_disp=0.0, max_disp=None, with_dense=False):
+    """The usable pixels of disparity_reproject as a packed cloud: (points, offsets), points [N, 3 + C] fp32 -- a row is
+    (X/W, Y/W, Z/W) and the pixel's values in the C planes of attributes ([B,C,H,W] fp32, C in 0..4; e.g. the left image for
+    XYZRGB), bit for bit -- and offsets [B + 1] int64: image b's points are rows offsets[b]..offsets[b+1], in row-major pixel
+    order.  The order is the pixel order whatever the scheduling (three launches, no atomics, no workgroup waits for another):
+    bit-reproducible, and an image's rows do not depend on the rest of the batch.  The op allocates the worst case (B*H*W rows),
+    reads offsets[B] on the host -- its one synchronisation -- and returns the [:N] view; N = 0 gives an empty [0, 3 + C]
+    tensor.  with_dense=True returns (points, offsets, xyz, mask): disparity_reproject's outputs, bit for bit, written in the
+    same pass.  disp, Q, valid, min_disp and max_disp as in disparity_reproject."""
+    d, v, q, per_image, a, lo, hi = _reproject_operands("point_cloud", disp, Q, attributes, valid, min_disp, max_disp)
+    B, H, W = d.shape
+    C_ = 0 if a is None else a.shape[1]
+    nb = _lib.query("ecmg_point_cloud_scratch_bytes", B, H, W)
+    _need(nb > 0, lambda: f"point_cloud: disp {tuple(d.shape)}: more pixels than the kernels are built for (B*H*W < 2^31)")
+    points = torch.empty(B * H * W, 3 + C_, device=d.device, dtype=d.dtype)
+    offsets = torch.empty(B + 1, device=d.device, dtype=torch.int64)
+    xyz = torch.empty(B, 3, H, W, device=d.device, dtype=d.dtype) if with_dense else None
+    mask = torch.empty(B, H, W, device=d.device, dtype=torch.uint8) if with_dense else None
+    scratch = _scratch(nb, d.device)
+    _lib.call("ecmg_point_cloud_fwd", _p(d), _p(v), _p(q), per_image, _p(a), C_, _p(points), _p(offsets), _p(xyz), _p(mask),
+              _p(scratch), C.c_longlong(nb), B, H, W, lo, hi, _stream())
+    n = int(offsets[B].item())                                         # the one host synchronisation
+    points = points[:n]
+    return (points, offsets, xyz, mask.view(torch.bool)) if with_dense else (points, offsets)
+
+
 # ------------------------------------------------------------------------------------ a5-a7 conv / deconv / GN
 def _pack_conv(w, flip_transpose=False):
     Co, Ci = w.shape[0], w.shape[1]

@@ -1,4 +1,5 @@
-"""ctypes binding of libecm_hip.so (the C ABI declared in include/ecm_hip.h and, for the geometry entries, include/ecm_geometry.h).
+"""ctypes binding of libecm_hip.so (the C ABI declared in include/ecm_hip.h and, for the geometry and rectification entries,
+include/ecm_geometry.h and include/ecm_rectify.h).
 
 The product path has NO fallback: if the library is missing or a call fails, a RuntimeError is
 raised.  Prototypes below mirror include/ecm_hip.h one to one: tests/test_abi_types.py parses the header and compares every
@@ -155,6 +156,19 @@ GEOMETRY_PROTOTYPES = {
     "ecmg_point_cloud_fwd": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _F, _F, _P]),
 }
 
+# The rectification entries (include/ecm_rectify.h, prefix ecmr_): a third table, held to its header by tests/test_rectify_cpu.py.
+RECTIFY_PROTOTYPES = {
+    "ecmr_rectify_map_params": (_I, []),
+    "ecmr_tile_width": (_I, []),
+    "ecmr_rectify_map_fwd": (_I, [_P, _P, _I, _I, _P]),
+    "ecmr_remap_pair_fwd": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _F, _P]),
+}
+
+
+def _tables():
+    return list(PROTOTYPES.items()) + list(GEOMETRY_PROTOTYPES.items()) + list(RECTIFY_PROTOTYPES.items())
+
+
 _lib = None
 
 
@@ -167,7 +181,7 @@ def load():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or `make -C explicit-context-mapping-for-stereo-matching_amd/csrc`). There is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(PROTOTYPES.items()) + list(GEOMETRY_PROTOTYPES.items()):
+        for name, (res, args) in _tables():
             fn = getattr(lib, name, None)
             if fn is None:
                 continue            # reported by missing_symbols()/tests; calling it raises below
@@ -178,7 +192,7 @@ def load():
 
 def missing_symbols():
     lib = load()
-    return [n for n in list(PROTOTYPES) + list(GEOMETRY_PROTOTYPES) if not hasattr(lib, n)]
+    return [n for n, _ in _tables() if not hasattr(lib, n)]
 
 
 # Optional per-launch timing (bench.py's roofline leg): name -> list of (start_event, end_event, int_args).

@@ -1200,3 +1200,50 @@ def get_model(name):
         print("Model {} not available".format(name))
         return None
     return cls()
+
+
+class StereoRig:
+    """A calibrated horizontal rig: from raw, distorted camera frames to the inputs of the network and, with
+    a model, to a metric point cloud, without leaving the device.  A plain object, not a module: .rectification is
+    ops.stereo_rectify's result for (K1, D1, K2, D2, R, T, size, new_size, focal, center), .Q its disparity-to-depth matrix
+    (what ops.disparity_reproject and _ECMNet.point_cloud take).  No model method is added or changed."""
+
+    def __init__(self, K1, D1, K2, D2, R, T, size, new_size=None, focal=None, center=None):
+        self.rectification = ops.stereo_rectify(K1, D1, K2, D2, R, T, size, new_size, focal, center)
+        self.Q = self.rectification.Q
+        self._cameras = ((K1.detach().clone(), D1.detach().clone()), (K2.detach().clone(), D2.detach().clone()))
+        self._maps = {}
+
+    def maps(self, device):
+        """(map_left, map_right), each [2,Ho,Wo] fp32 on `device`: ops.rectify_map of each camera, computed once per device."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device not in self._maps:
+            r = self.rectification
+            self._maps[device] = tuple(ops.rectify_map(K, D, Rn, Pn, r.new_size, device)
+                                       for (K, D), Rn, Pn in zip(self._cameras, (r.R1, r.R2), (r.P1, r.P2)))
+        return self._maps[device]
+
+    def __call__(self, left_raw, right_raw, want_image=False, with_mask=False):
+        """ops.remap_pair of the raw pair (uint8 [B,H,W,3] or float32 [B,3,H,W] of the calibrated size) through this rig's maps:
+        (left, right[, image][, mask_left, mask_right])."""
+        if not isinstance(left_raw, torch.Tensor) or not left_raw.is_cuda:
+            raise RuntimeError("ecm ops run only on the MI355X HIP path: got a CPU tensor (no CPU fallback exists)")
+        hw = tuple(left_raw.shape[1:3]) if left_raw.dtype == torch.uint8 else tuple(left_raw.shape[2:4])
+        if left_raw.dim() != 4 or hw != self.rectification.size:
+            raise ValueError(f"StereoRig: frames {tuple(left_raw.shape)}: the rig was calibrated at (H, W) = {self.rectification.size}")
+        map_left, map_right = self.maps(left_raw.device)
+        return ops.remap_pair(left_raw, right_raw, map_left, map_right, want_image=want_image, with_mask=with_mask)
+
+    def point_cloud(self, model, left_raw, right_raw, source="smooth", colors="image", **stage_args):
+        """Rectify the raw pair, then model.point_cloud(left, right, self.Q, colors=..., source=source, **stage_args): that
+        PointCloud, unchanged.  colors: "image" (the rectified left image in /255 units: XYZRGB rows), None, or a tensor
+        [B,C,Ho,Wo] of the caller's."""
+        if isinstance(colors, str) and colors != "image":
+            raise ValueError(f"StereoRig.point_cloud: colors {colors!r}: \"image\", None or a tensor")
+        if isinstance(colors, str):
+            left, right, colors = self(left_raw, right_raw, want_image=True)
+        else:
+            left, right = self(left_raw, right_raw)
+        return model.point_cloud(left, right, self.Q, colors=colors, source=source, **stage_args)

@@ -1954,6 +1954,231 @@ def _frame_prep(frames, crop_y0, crop_x0, th, tw, split, tail, mean, std, want_i
     return (left, right, disp, image) if want_image else (left, right, disp)
 
 
+# ------------------------------------------------------------------------------------ stereo rectification
+# DESIGN.md section 24; include/ecm_rectify.h.  The front of the chain: from a calibrated rig (K1, D1, K2, D2, R, T) and a raw,
+# distorted pair to the normalised inputs of the network and the Q that disparity_reproject / point_cloud take.  stereo_rectify is
+# host arithmetic in fp64 (Bouguet's construction); rectify_map is initUndistortRectifyMap in fp64 on the device, once per rig;
+# remap_pair is the per-frame kernel: both views, bilinear, with frame_prep's normalisation, in one launch.  Forward only.
+# The camera model is the pinhole with rational radial and tangential distortion; no fisheye, thin-prism or tilt terms.
+Rectification = collections.namedtuple("Rectification", "R1 R2 P1 P2 Q size new_size")
+_DIST_LENGTHS = (4, 5, 8)                     # k1 k2 p1 p2 [k3 [k4 k5 k6]]: OpenCV's order
+
+
+def _calib(who, name, t, shape):
+    """A calibration operand: a float64 CPU tensor of `shape` (None in it: any length) with finite entries, or ValueError."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.is_cuda or t.dim() != len(shape) \
+            or any(s is not None and s != n for s, n in zip(shape, t.shape)):
+        what = f"{tuple(t.shape)} {t.dtype}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{who}: {name} {what}: a float64 CPU tensor {list(shape)}")
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError(f"{who}: {name} has a non-finite entry")
+    return t.detach()
+
+
+def _camera(who, name, K, D):
+    """(fx, fy, cx, cy) and the eight coefficients k1 k2 p1 p2 k3 k4 k5 k6 (those not given: 0.0) as floats."""
+    K, D = _calib(who, name, K, (3, 3)), _calib(who, "D" + name[1:], D, (None,))
+    if D.shape[0] not in _DIST_LENGTHS:
+        raise ValueError(f"{who}: D{name[1:]} holds {D.shape[0]} coefficients: one of {_DIST_LENGTHS} (k1 k2 p1 p2 [k3 [k4 k5 k6]])")
+    k = K.tolist()
+    if k[0][1] != 0 or k[1][0] != 0 or k[2] != [0.0, 0.0, 1.0] or not (k[0][0] > 0 and k[1][1] > 0):
+        raise ValueError(f"{who}: {name} is not a pinhole matrix [fx 0 cx; 0 fy cy; 0 0 1] with fx, fy > 0")
+    return (k[0][0], k[1][1], k[0][2], k[1][2]), D.tolist() + [0.0] * (8 - D.shape[0])
+
+
+def _hw(who, name, size):
+    if not isinstance(size, (tuple, list)) or len(size) != 2 or \
+            any(isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 1 for v in size):
+        raise ValueError(f"{who}: {name} {size!r}: (H, W), two positive ints")
+    return int(size[0]), int(size[1])
+
+
+def _rotation_matrix(om):
+    """Rodrigues: the rotation by |om| about om / |om| (float64 [3]); the zero vector gives the identity exactly."""
+    theta = float(torch.linalg.vector_norm(om))
+    eye = torch.eye(3, dtype=torch.float64)
+    if theta == 0.0:
+        return eye
+    a = om / theta
+    skew = torch.tensor([[0.0, -float(a[2]), float(a[1])], [float(a[2]), 0.0, -float(a[0])], [-float(a[1]), float(a[0]), 0.0]],
+                        dtype=torch.float64)
+    c, s = math.cos(theta), math.sin(theta)
+    return c * eye + (1.0 - c) * torch.outer(a, a) + s * skew
+
+
+def _rotation_vector(R):
+    """Rodrigues' inverse: axis * angle of an orthonormal R (float64 [3,3]), the angle in [0, pi]."""
+    v = torch.stack([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])            # 2 sin(angle) * axis
+    s = float(torch.linalg.vector_norm(v)) / 2.0
+    c = (float(R[0, 0] + R[1, 1] + R[2, 2]) - 1.0) / 2.0
+    theta = math.atan2(s, c)
+    if s > 1e-8:
+        return v * (theta / (2.0 * s))
+    if c > 0:
+        return v / 2.0                                                                    # angle = sin(angle) to fp64 there
+    sym = (R + R.T) / 2.0 + torch.eye(3, dtype=torch.float64)                             # near pi: 2 axis axis^T
+    col = sym[:, int(torch.argmax(torch.diagonal(sym)))]
+    axis = col / torch.linalg.vector_norm(col)
+    if float(torch.dot(axis, v)) < 0:
+        axis = -axis
+    return axis * theta
+
+
+def _align_to_x(t):
+    """The smallest rotation taking t (float64 [3], non-zero) onto the x axis on the side t_x lies on (t_x = 0: the positive
+    one): I + [v]x + [v]x^2 / (1 + c) with v = a x u, c = a . u for a = t / |t| and u = (+-1, 0, 0).  Exact identity where t is
+    already on the axis."""
+    a = t / torch.linalg.vector_norm(t)
+    u = torch.tensor([-1.0 if float(t[0]) < 0 else 1.0, 0.0, 0.0], dtype=torch.float64)
+    v = torch.linalg.cross(a, u)
+    c = float(torch.dot(a, u))                                                            # >= 0
+    skew = torch.tensor([[0.0, -float(v[2]), float(v[1])], [float(v[2]), 0.0, -float(v[0])], [-float(v[1]), float(v[0]), 0.0]],
+                        dtype=torch.float64)
+    return torch.eye(3, dtype=torch.float64) + skew + (skew @ skew) / (1.0 + c)
+
+
+def stereo_rectify(K1, D1, K2, D2, R, T, size, new_size=None, focal=None, center=None):
+    """Bouguet's rectification of a horizontal rig, on the host in fp64: Rectification(R1, R2, P1, P2, Q, size, new_size).
+    Conventions are OpenCV's: a point of the left camera frame is X2 = R X1 + T in the right one; K [3,3], D = k1 k2 p1 p2
+    [k3 [k4 k5 k6]], R [3,3], T [3] are float64 CPU tensors; size and new_size (None: size) are (H, W).
+    With r = R^(-1/2) (Rodrigues of minus half the rotation vector) and t = r T, wR is the smallest rotation taking t onto the x
+    axis on the side of t_x; R1 = wR r^T and R2 = wR r rotate the left and the right camera frame into the common rectified
+    frame, and R2 T = (t_x', 0, 0).  The intrinsics are this project's rule, not OpenCV's alpha / ROI logic: f = focal, or
+    min(K1[1,1], K2[1,1]) * new_H / H; (cx, cy) = center, or the mean of the two principal points scaled by new_W / W and
+    new_H / H; both views share them (zero disparity at infinity).  P1 = [f 0 cx 0; 0 f cy 0; 0 0 1 0], P2 the same with
+    P2[0,3] = f t_x', Q = q_matrix(f, |t_x'|, cx, cy).  ValueError: wrong shapes or dtypes, non-finite entries, len(D) not 4, 5
+    or 8, R not orthonormal to 1e-6, T = 0, a vertical rig (|t_y| > |t_x|), and t_x' > 0 (the "right" camera lies on the left:
+    swap the views)."""
+    who = "stereo_rectify"
+    (_, fy1, cx1, cy1), _ = _camera(who, "K1", K1, D1)
+    (_, fy2, cx2, cy2), _ = _camera(who, "K2", K2, D2)
+    R, T = _calib(who, "R", R, (3, 3)), _calib(who, "T", T, (3,))
+    H, W = _hw(who, "size", size)
+    Hn, Wn = (H, W) if new_size is None else _hw(who, "new_size", new_size)
+    if focal is not None and (isinstance(focal, bool) or not isinstance(focal, numbers.Real) or not math.isfinite(focal) or focal <= 0):
+        raise ValueError(f"{who}: focal {focal!r}: None or a finite number > 0")
+    if center is not None and (not isinstance(center, (tuple, list)) or len(center) != 2 or any(
+            isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) for v in center)):
+        raise ValueError(f"{who}: center {center!r}: None or (cx, cy), two finite numbers")
+    eye = torch.eye(3, dtype=torch.float64)
+    if float((R @ R.T - eye).abs().max()) > 1e-6 or float(torch.linalg.det(R)) < 0:
+        raise ValueError(f"{who}: R is not a rotation (R R^T = I to 1e-6, det +1)")
+    if float(torch.linalg.vector_norm(T)) == 0.0:
+        raise ValueError(f"{who}: T is zero: no baseline")
+    r = _rotation_matrix(-0.5 * _rotation_vector(R))
+    t = r @ T
+    if abs(float(t[1])) > abs(float(t[0])):
+        raise ValueError(f"{who}: a vertical rig (|t_y| {abs(float(t[1]))!r} > |t_x| {abs(float(t[0]))!r}): only horizontal rigs")
+    if float(t[0]) > 0:
+        raise ValueError(f"{who}: t_x' > 0: the \"right\" camera lies on the left of the \"left\" one; swap the views")
+    wR = _align_to_x(t)
+    R1, R2 = wR @ r.T, wR @ r
+    tx = float((R2 @ T)[0])
+    sy, sx = Hn / H, Wn / W                                                               # 1.0 exactly where new_size is size
+    f = float(focal) if focal is not None else min(fy1, fy2) * sy
+    cx, cy = (float(center[0]), float(center[1])) if center is not None else ((cx1 + cx2) / 2.0 * sx, (cy1 + cy2) / 2.0 * sy)
+    P1 = torch.tensor([[f, 0.0, cx, 0.0], [0.0, f, cy, 0.0], [0.0, 0.0, 1.0, 0.0]], dtype=torch.float64)
+    P2 = P1.clone()
+    P2[0, 3] = f * tx
+    return Rectification(R1, R2, P1, P2, q_matrix(f, abs(tx), cx, cy), (H, W), (Hn, Wn))
+
+
+def rectify_tile_width():
+    """The output columns one workgroup of rectify_map and remap_pair covers (a size query of the library: no GPU needed)."""
+    return int(_lib.query("ecmr_tile_width"))
+
+
+def rectify_map_params(K, D, R, P):
+    """The doubles rectify_map hands to the device, as a float64 CPU tensor: iR = (P[:, :3] R)^-1 row-major (taken here, on the
+    host), fx fy cx cy of K, then k1 k2 p1 p2 k3 k4 k5 k6 (coefficients D does not give: 0).  ValueError for operands that are not
+    float64 CPU tensors K [3,3], D [4|5|8], R [3,3], P [3,4] with finite entries, and for a singular P[:, :3] R."""
+    who = "rectify_map"
+    cam, dist = _camera(who, "K", K, D)
+    R, P = _calib(who, "R", R, (3, 3)), _calib(who, "P", P, (3, 4))
+    M = P[:, :3] @ R
+    if not abs(float(torch.linalg.det(M))) > 1e-12 * float(M.abs().max()) ** 3:
+        raise ValueError(f"{who}: P[:, :3] R is singular")
+    iR = torch.linalg.inv(M)
+    if not bool(torch.isfinite(iR).all()):
+        raise ValueError(f"{who}: P[:, :3] R is singular")
+    params = torch.cat([iR.reshape(9), torch.tensor(list(cam) + dist, dtype=torch.float64)])
+    _need(params.numel() == _lib.query("ecmr_rectify_map_params"), "rectify_map: the library expects another parameter count")
+    return params
+
+
+@torch.no_grad()
+def rectify_map(K, D, R, P, new_size, device):
+    """initUndistortRectifyMap on the device, in fp64, one launch: map [2,Ho,Wo] fp32 for new_size = (Ho, Wo), plane 0 the source
+    x and plane 1 the source y of every rectified pixel, each rounded once to fp32.  K, D: the camera; R: its rectifying
+    rotation (R1 or R2 of stereo_rectify); P: its new projection (P1 or P2; the fourth column is not used).  The operation
+    order is written out in include/ecm_rectify.h."""
+    params = rectify_map_params(K, D, R, P)
+    Ho, Wo = _hw("rectify_map", "new_size", new_size)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("ecm ops run only on the MI355X HIP path: got a CPU device (no CPU fallback exists)")
+    with torch.cuda.device(device):
+        pd = params.to(device)
+        out = torch.empty(2, Ho, Wo, device=device, dtype=torch.float32)
+        # Ho * Wo >= 2^31 is refused by the library before any launch (ECM_EUNSUP -> RuntimeError)
+        _lib.call("ecmr_rectify_map_fwd", _p(pd), _p(out), Ho, Wo, _stream())
+    return out
+
+
+def _norm3(who, name, values, nonzero):
+    if not isinstance(values, (tuple, list)) or len(values) != 3 or any(
+            isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or (nonzero and v == 0) for v in values):
+        raise ValueError(f"{who}: {name} {values!r}: three finite numbers" + (", none zero" if nonzero else ""))
+    return [float(v) for v in values]
+
+
+@torch.no_grad()
+def remap_pair(left_raw, right_raw, map_left, map_right, mean=FLYING3D_MEAN, std=FLYING3D_STD, border=0.0, want_image=False,
+               with_mask=False):
+    """The raw pair through its rectification maps to the network's inputs, both views in one launch: (left, right), each
+    [B,3,Ho,Wo] fp32 = (s / 255 - mean) / std with s the bilinear sample of the raw frame at the map's coordinates -- frame_prep's
+    arithmetic, so a map of integer coordinates reproduces its planes bit for bit.  left_raw, right_raw: uint8 [B,H,W,3] or
+    float32 [B,3,H,W] holding 0..255; map_left, map_right: fp32 [2,Ho,Wo] (one rig) or [B,2,Ho,Wo] (rectify_map builds them).  A
+    tap outside the source is `border` (0..255 units); a non-finite map entry gives border in every channel.  want_image=True
+    adds the rectified left image in /255 units (the colours of a point cloud); with_mask=True adds (mask_left, mask_right), bool
+    [B,Ho,Wo]: True where the coordinates are finite and all four taps lie inside the source.  Returns
+    (left, right[, image][, mask_left, mask_right]).  No atomics: bit-reproducible.  What bilinear resampling does to EPE or D1 is
+    not measured."""
+    who = "remap_pair"
+    for t in (left_raw, right_raw, map_left, map_right):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError("ecm ops run only on the MI355X HIP path: got a CPU tensor (no CPU fallback exists)")
+    u8 = left_raw.dtype == torch.uint8
+    _need(left_raw.dim() == 4 and ((u8 and left_raw.shape[3] == 3) or (left_raw.dtype == torch.float32 and left_raw.shape[1] == 3))
+          and left_raw.numel() > 0,
+          lambda: f"{who}: left_raw {left_raw.dtype} {tuple(left_raw.shape)}: want uint8 [B,H,W,3] or float32 [B,3,H,W]")
+    _need(right_raw.dtype == left_raw.dtype and right_raw.shape == left_raw.shape,
+          lambda: f"{who}: right_raw {right_raw.dtype} {tuple(right_raw.shape)} against left_raw {left_raw.dtype} {tuple(left_raw.shape)}")
+    B, H, W = (left_raw.shape[0], left_raw.shape[1], left_raw.shape[2]) if u8 else (left_raw.shape[0], left_raw.shape[2], left_raw.shape[3])
+    _need(map_left.dtype == torch.float32 and map_left.dim() in (3, 4) and map_left.shape[-3] == 2 and map_left.numel() > 0
+          and (map_left.dim() == 3 or map_left.shape[0] == B),
+          lambda: f"{who}: map_left {map_left.dtype} {tuple(map_left.shape)}: want float32 [2,Ho,Wo] or [{B},2,Ho,Wo]")
+    _need(map_right.dtype == torch.float32 and map_right.shape == map_left.shape,
+          lambda: f"{who}: map_right {map_right.dtype} {tuple(map_right.shape)} against map_left {tuple(map_left.shape)}")
+    m3, s3 = _norm3(who, "mean", mean, False), _norm3(who, "std", std, True)
+    if isinstance(border, bool) or not isinstance(border, numbers.Real) or not math.isfinite(border) or abs(border) > _FLT_MAX:
+        raise ValueError(f"{who}: border {border!r}: a finite number")
+    Ho, Wo = map_left.shape[-2:]
+    lr, rr, ml, mr = left_raw.detach().contiguous(), right_raw.detach().contiguous(), _c(map_left.detach()), _c(map_right.detach())
+    dev = lr.device
+    left = torch.empty(B, 3, Ho, Wo, device=dev, dtype=torch.float32)
+    right = torch.empty_like(left)
+    image = torch.empty_like(left) if want_image else None
+    mask_l = torch.empty(B, Ho, Wo, device=dev, dtype=torch.uint8) if with_mask else None
+    mask_r = torch.empty_like(mask_l) if with_mask else None
+    # B * max(H * W, Ho * Wo) >= 2^31 is refused by the library before any launch (ECM_EUNSUP -> RuntimeError)
+    _lib.call("ecmr_remap_pair_fwd", _p(lr), _p(rr), int(u8), _p(ml), _p(mr), int(map_left.dim() == 4), _p(left), _p(right),
+              _p(image), _p(mask_l), _p(mask_r), B, H, W, Ho, Wo, _host(C.c_float, m3), _host(C.c_float, s3), float(border),
+              _stream())
+    out = (left, right) + ((image,) if want_image else ())
+    return out + ((mask_l.view(torch.bool), mask_r.view(torch.bool)) if with_mask else ())
+
+
 def _out_row(out, n, device):
     """The `out=` operand of the evaluation ops: None -> a fresh float32[n] on `device`; else a contiguous fp32 view of n floats
     there (e.g. a row of a preallocated [n_batches, n] log) that the kernel writes in place."""

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 #include "../../include/ecm_hip.h"
 
@@ -9,6 +10,18 @@
 #define ECM_LAUNCH_RESULT() ((int)hipGetLastError())
 
 static inline hipStream_t ecm_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+// A runtime value as a compile-time one: f(std::integral_constant<int, V>{}) for the V of Vs... that equals v, and f's own
+// status; ECM_EUNSUP, with f not called, for any other v.
+template <int... Vs, class F>
+static inline int ecm_dispatch(int v, F&& f) {
+    int rc = ECM_EUNSUP;
+    (void)((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return rc;
+}
+// the disparity heads are built for one to three heads
+template <class F>
+static inline int ecm_dispatch_heads(int nheads, F&& f) { return ecm_dispatch<1, 2, 3>(nheads, f); }
 
 // Raise a kernel's dynamic-LDS limit, once per (kernel, device): function attributes are per device and one process
 // may drive several GPUs from several threads (the reference wraps the model in nn.DataParallel, train.py:78-79).

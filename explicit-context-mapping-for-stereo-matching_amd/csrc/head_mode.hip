@@ -3,14 +3,12 @@
 // window |d - D*| <= r and p's mean inside that window.  The volume and trilinear heads' modal estimate is MODE 2 of their own
 // kernels (variants.hip); this file is the LDS-staged mixture kernel that section 15 named as the follow-up of
 // aggregate9_stats_fwd: a workgroup normalises the cell columns under its tile ONCE and its pixels mix from LDS, with no
-// exponential of their own.
+// exponential of their own.  Which neighbours a pixel mixes and with what weights is ecm_mixture9 (ecm_nbr.h), shared with
+// head_stats.hip; that kernel reads its columns from global memory, this one from LDS.
 #include "common.h"
+#include "ecm_nbr.h"
 
 namespace {
-
-// neighbour order of heads.hip (cmfsm.py:551,585-593): c,l,r,t,b,lt,rt,lb,rb
-__constant__ int kDy[9] = {0, 0, 0, -1, 1, -1, -1, 1, 1};
-__constant__ int kDx[9] = {0, -1, 1, 0, 0, -1, 1, -1, 1};
 
 constexpr int TX = 64, TY = 4;            // the tile of full-resolution pixels: a wave is 64 consecutive X, a workgroup four rows
 constexpr int DC_MAX = 48;                // at most this many levels are staged at a time (D' = 48 at 576 x 960: one chunk)
@@ -109,19 +107,10 @@ __global__ __launch_bounds__(256) void aggregate9_mode_fwd(const float* __restri
     const int pix = Yc * W + Xc;
     const int lc = (Yc / s - cy0) * ncx + (Xc / s - cx0);             // the centre's column: inside the halo ring
     float a[9];
-    int off[9];
-    float wsum = 0.f;
+    int off[9], cell[9];
+    ecm_mixture9(w9 + (size_t)b * 9 * HW + pix, HW, Yc / s, Xc / s, h, w, a, cell);
 #pragma unroll
-    for (int n = 0; n < 9; ++n) {
-        off[n] = lc + kDy[n] * ncx + kDx[n];
-        const int yy = Yc / s + kDy[n], xx = Xc / s + kDx[n];
-        const bool ok = yy >= 0 && yy < h && xx >= 0 && xx < w;
-        a[n] = ok ? w9[((size_t)b * 9 + n) * HW + pix] : 0.f;
-        wsum += a[n];
-    }
-    const float inv = 1.f / wsum;
-#pragma unroll
-    for (int n = 0; n < 9; ++n) a[n] *= inv;
+    for (int n = 0; n < 9; ++n) off[n] = lc + Nbr<0>::dy(n) * ncx + Nbr<0>::dx(n);
     auto mix = [&](int k, int dd) {
         const float* p = P + ((size_t)k * dc + dd) * ncol;
         float v = 0.f;
@@ -189,7 +178,7 @@ __global__ __launch_bounds__(256) void aggregate9_mode_fwd(const float* __restri
 extern "C" int ecm_aggregate9_mode_fwd(const float* c0, long long head_stride, const float* lse, const float* w9, float* modal,
                                        int nheads, int B, int D, int h, int w, int s, int radius, void* stream) {
     ECM_CHECK_ARG(c0 && lse && w9 && modal && B > 0 && D > 0 && h > 0 && w > 0 && s > 0 && radius >= 0 && radius % s == 0);
-    if (nheads < 1 || nheads > 3 || B > 65535) return ECM_EUNSUP;
+    if (nheads < 1 || nheads > 3 || B > 65535) return ECM_EUNSUP;     // nheads sizes the LDS below
     const int ncol = span_cells(TX, s) * span_cells(TY, s);
     // the levels that fit beside S, L and Kc; at s = 4: 54 columns, 48 levels x 3 heads = 31,104 B + 1,944 B
     const int dc = min(min(D, DC_MAX), (LDS_BUDGET / (int)sizeof(float) - 3 * nheads * ncol) / (nheads * ncol));
@@ -197,12 +186,9 @@ extern "C" int ecm_aggregate9_mode_fwd(const float* c0, long long head_stride, c
     const size_t lds = ((size_t)nheads * dc + 3 * (size_t)nheads) * ncol * sizeof(float);
     const int r = min(radius / s, D);
     dim3 grid((w * s + TX - 1) / TX, (h * s + TY - 1) / TY, B), block(256);
-    switch (nheads) {
-#define ECM_MODE_CASE(N)                                                                                                       \
-        case N: hipLaunchKernelGGL(aggregate9_mode_fwd<N>, grid, block, lds, ecm_stream(stream), c0, head_stride, lse, w9,    \
-                                   modal, B, D, h, w, s, r, dc, ncol); break;
-        ECM_MODE_CASE(1) ECM_MODE_CASE(2) ECM_MODE_CASE(3)
-#undef ECM_MODE_CASE
-    }
-    return ECM_LAUNCH_RESULT();
+    return ecm_dispatch_heads(nheads, [&](auto nh) {
+        hipLaunchKernelGGL(aggregate9_mode_fwd<decltype(nh)::value>, grid, block, lds, ecm_stream(stream), c0, head_stride, lse, w9,
+                           modal, B, D, h, w, s, r, dc, ncol);
+        return ECM_LAUNCH_RESULT();
+    });
 }

@@ -1,13 +1,11 @@
 // Per-pixel uncertainty of the eight-neighbour head: std, peak and entropy of each full-resolution
 // pixel's mixture of its neighbours' low-resolution distributions.  The head itself is heads.hip (softargmin_fwd with LSE,
-// aggregate9_fwd); this kernel reads the same classifier outputs, the same w9 and the normalisers softargmin_fwd stored.
+// aggregate9_fwd); this kernel reads the same classifier outputs, the same w9 and the normalisers softargmin_fwd stored.  Which
+// neighbours a pixel mixes and with what weights is ecm_mixture9 (ecm_nbr.h), shared with head_mode.hip.
 #include "common.h"
+#include "ecm_nbr.h"
 
 namespace {
-
-// neighbour order of heads.hip (cmfsm.py:551,585-593): c,l,r,t,b,lt,rt,lb,rb
-__constant__ int kDy[9] = {0, 0, 0, -1, 1, -1, -1, 1, 1};
-__constant__ int kDx[9] = {0, -1, 1, 0, 0, -1, 1, -1, 1};
 
 // Statistics of the HR pixel's distribution: the mixture p(d) = sum_n a_n p_n(d) of the low-resolution
 // softmaxes of the neighbours aggregate9_fwd does not skip, a_n = w9[n] / sum of the valid w9.  p_n(d) = exp(logit_n(d) - lse_n).
@@ -29,17 +27,11 @@ __global__ __launch_bounds__(256) void aggregate9_stats_fwd(const float* __restr
     const int hw = h * w;
     float a[9], ln[9][NH];
     int cell[9];
-    float wsum = 0.f;
+    ecm_mixture9(w9 + (size_t)b * 9 * HW + r, HW, cy, cx, h, w, a, cell);
 #pragma unroll
-    for (int n = 0; n < 9; ++n) {
-        const int yy = cy + kDy[n], xx = cx + kDx[n];
-        const bool ok = yy >= 0 && yy < h && xx >= 0 && xx < w;
-        cell[n] = ok ? yy * w + xx : -1;
-        a[n] = ok ? w9[((size_t)b * 9 + n) * HW + r] : 0.f;
-        wsum += a[n];
+    for (int n = 0; n < 9; ++n)
 #pragma unroll
-        for (int k = 0; k < NH; ++k) ln[n][k] = ok ? lse[((size_t)k * B + b) * hw + cell[n]] : 0.f;
-    }
+        for (int k = 0; k < NH; ++k) ln[n][k] = cell[n] >= 0 ? lse[((size_t)k * B + b) * hw + cell[n]] : 0.f;
     const float* base = c0 + (size_t)b * D * hw;
     // lse is one rounded float: at |lse| ~ 100 it is off by 4e-6, and so would every p_n be.  It serves as the shift that keeps
     // the exponentials in range; a first sweep sums them and folds the exact normaliser into the weight, an = a_n / sum.
@@ -60,11 +52,10 @@ __global__ __launch_bounds__(256) void aggregate9_stats_fwd(const float* __restr
             }
         }
     }
-    const float inv = 1.f / wsum;
 #pragma unroll
     for (int n = 0; n < 9; ++n)
 #pragma unroll
-        for (int k = 0; k < NH; ++k) an[n][k] = a[n] * inv / an[n][k];
+        for (int k = 0; k < NH; ++k) an[n][k] = a[n] / an[n][k];
     float S[NH], mu[NH], M2[NH], pk[NH], en[NH];
 #pragma unroll
     for (int k = 0; k < NH; ++k) { S[k] = 0.f; mu[k] = 0.f; M2[k] = 0.f; pk[k] = 0.f; en[k] = 0.f; }
@@ -113,13 +104,9 @@ extern "C" int ecm_aggregate9_stats_fwd(const float* c0, long long head_stride, 
     ECM_CHECK_ARG(c0 && lse && w9 && stats && B > 0 && D > 0 && h > 0 && w > 0 && s > 0);
     const long long n = (long long)B * h * s * w * s;
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    switch (nheads) {
-#define ECM_STATS_CASE(N)                                                                                                      \
-        case N: hipLaunchKernelGGL(aggregate9_stats_fwd<N>, grid, block, 0, ecm_stream(stream), c0, head_stride, lse, w9,     \
-                                   stats, B, D, h, w, s); break;
-        ECM_STATS_CASE(1) ECM_STATS_CASE(2) ECM_STATS_CASE(3)
-#undef ECM_STATS_CASE
-        default: return ECM_EUNSUP;
-    }
-    return ECM_LAUNCH_RESULT();
+    return ecm_dispatch_heads(nheads, [&](auto nh) {
+        hipLaunchKernelGGL(aggregate9_stats_fwd<decltype(nh)::value>, grid, block, 0, ecm_stream(stream), c0, head_stride, lse, w9,
+                           stats, B, D, h, w, s);
+        return ECM_LAUNCH_RESULT();
+    });
 }

@@ -1,15 +1,50 @@
 // a8 + a9: disparity heads.  soft-argmin over D' for the three heads (cmfsm.py:703-706, 725-728,
 // 748-753; disparityregression 111-123) and NN-upsample + 9-neighbour weighted sum
 // (cmfsm.py:709-723, 730-744, 755-769).  All HBM/L2-bound, one thread per pixel column / HR pixel.
+// The logits of a column are formed by column_sweep alone; the nine neighbours (c,l,r,t,b,lt,rt,lb,rb: cmfsm.py:551,585-593)
+// are Nbr<0> of ecm_nbr.h, the table of the weight generators and of head_stats.hip / head_mode.hip.
 #include "common.h"
+#include "ecm_nbr.h"
 
 namespace {
 
-// neighbour order of the reference's return tuple (cmfsm.py:551,585-593): c,l,r,t,b,lt,rt,lb,rb
-__constant__ int kDy[9] = {0, 0, 0, -1, 1, -1, -1, 1, 1};
-__constant__ int kDx[9] = {0, -1, 1, 0, 0, -1, 1, -1, 1};
-
 // ---- soft-argmin, heads fused: logits_k = c_0 + ... + c_k ----------------------------------
+// One sweep of an LR column in the order of d: f(d, v), v[k] the logit of head k.  THE ONLY PLACE THIS HEAD'S LOGITS ARE FORMED
+// in this file; every pass of softargmin_fwd and softargmin_bwd is one such sweep (a later pass re-reads from L2).
+template <int NH, class F>
+__device__ __forceinline__ void column_sweep(const float* __restrict__ base, long long hs, int D, int hw, F&& f) {
+    for (int d = 0; d < D; ++d) {
+        float acc = 0.f, v[NH];
+#pragma unroll
+        for (int k = 0; k < NH; ++k) {
+            acc += base[(size_t)k * hs + (size_t)d * hw];
+            v[k] = acc;
+        }
+        f(d, v);
+    }
+}
+
+// The column softmax both kernels start with: pass 1 the maxima (torch's softmax: exp(x - max) / sum), pass 2
+// s = sum exp(logit - m) and t = sum exp(logit - m) d.
+template <int NH>
+__device__ __forceinline__ void column_softmax(const float* __restrict__ base, long long hs, int D, int hw, float (&m)[NH],
+                                               float (&s)[NH], float (&t)[NH]) {
+#pragma unroll
+    for (int k = 0; k < NH; ++k) { m[k] = -INFINITY; s[k] = 0.f; t[k] = 0.f; }
+    column_sweep<NH>(base, hs, D, hw, [&](int, const float (&v)[NH]) {
+#pragma unroll
+        for (int k = 0; k < NH; ++k) m[k] = fmaxf(m[k], v[k]);
+    });
+    column_sweep<NH>(base, hs, D, hw, [&](int d, const float (&v)[NH]) {
+#pragma unroll
+        for (int k = 0; k < NH; ++k) {
+            const float e = expf(v[k] - m[k]);
+            s[k] += e;
+            t[k] += e * (float)d;
+        }
+    });
+}
+
 // LSE: also lse[k,b,p] = m + ln s, the normaliser of head k's column, for aggregate9_stats_fwd
 template <int NH, bool LSE = false>
 __global__ __launch_bounds__(256) void softargmin_fwd(const float* __restrict__ c0, long long hs,
@@ -18,31 +53,8 @@ __global__ __launch_bounds__(256) void softargmin_fwd(const float* __restrict__ 
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;     // b*hw + p
     if (i >= (long long)B * hw) return;
     const int b = (int)(i / hw), p = (int)(i - (long long)b * hw);
-    const float* base = c0 + (size_t)b * D * hw + p;
     float m[NH], s[NH], t[NH];
-#pragma unroll
-    for (int k = 0; k < NH; ++k) { m[k] = -INFINITY; }
-    // pass 1: maxima (torch's softmax: exp(x - max) / sum); pass 2 re-reads from L2
-    for (int d = 0; d < D; ++d) {
-        float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < NH; ++k) {
-            acc += base[(size_t)k * hs + (size_t)d * hw];
-            m[k] = fmaxf(m[k], acc);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < NH; ++k) { s[k] = 0.f; t[k] = 0.f; }
-    for (int d = 0; d < D; ++d) {
-        float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < NH; ++k) {
-            acc += base[(size_t)k * hs + (size_t)d * hw];
-            const float e = expf(acc - m[k]);
-            s[k] += e;
-            t[k] += e * (float)d;
-        }
-    }
+    column_softmax<NH>(c0 + (size_t)b * D * hw + p, hs, D, hw, m, s, t);
 #pragma unroll
     for (int k = 0; k < NH; ++k) {
         disp[(size_t)k * B * hw + i] = t[k] / s[k];
@@ -59,47 +71,22 @@ __global__ __launch_bounds__(256) void softargmin_bwd(const float* __restrict__ 
     if (i >= (long long)B * hw) return;
     const int b = (int)(i / hw), p = (int)(i - (long long)b * hw);
     const size_t off = (size_t)b * D * hw + p;
-    const float* base = c0 + off;
     float m[NH], s[NH], t[NH], g[NH];
-#pragma unroll
-    for (int k = 0; k < NH; ++k) { m[k] = -INFINITY; }
-    for (int d = 0; d < D; ++d) {
-        float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < NH; ++k) {
-            acc += base[(size_t)k * hs + (size_t)d * hw];
-            m[k] = fmaxf(m[k], acc);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < NH; ++k) { s[k] = 0.f; t[k] = 0.f; g[k] = gdisp[(size_t)k * B * hw + i]; }
-    for (int d = 0; d < D; ++d) {
-        float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < NH; ++k) {
-            acc += base[(size_t)k * hs + (size_t)d * hw];
-            const float e = expf(acc - m[k]);
-            s[k] += e;
-            t[k] += e * (float)d;
-        }
-    }
+    column_softmax<NH>(c0 + off, hs, D, hw, m, s, t);
     float inv[NH], dk[NH];
 #pragma unroll
-    for (int k = 0; k < NH; ++k) { inv[k] = 1.f / s[k]; dk[k] = t[k] * inv[k]; }
-    for (int d = 0; d < D; ++d) {
-        float acc = 0.f, gl[NH];
+    for (int k = 0; k < NH; ++k) { inv[k] = 1.f / s[k]; dk[k] = t[k] * inv[k]; g[k] = gdisp[(size_t)k * B * hw + i]; }
+    column_sweep<NH>(c0 + off, hs, D, hw, [&](int d, const float (&v)[NH]) {
+        float gl[NH];
 #pragma unroll
-        for (int k = 0; k < NH; ++k) {
-            acc += base[(size_t)k * hs + (size_t)d * hw];
-            gl[k] = expf(acc - m[k]) * inv[k] * ((float)d - dk[k]) * g[k];
-        }
+        for (int k = 0; k < NH; ++k) gl[k] = expf(v[k] - m[k]) * inv[k] * ((float)d - dk[k]) * g[k];
         float run = 0.f;
 #pragma unroll
         for (int k = NH - 1; k >= 0; --k) {
             run += gl[k];
             gc0[off + (size_t)k * hs + (size_t)d * hw] = run;
         }
-    }
+    });
 }
 
 __global__ __launch_bounds__(256) void dispreg_fwd(const float* __restrict__ x, float* __restrict__ out, int B, int D,
@@ -133,7 +120,7 @@ __global__ __launch_bounds__(256) void aggregate9_fwd(const float* __restrict__ 
     const float fs = (float)s;
 #pragma unroll
     for (int n = 0; n < 9; ++n) {
-        const int yy = cy + kDy[n], xx = cx + kDx[n];
+        const int yy = cy + Nbr<0>::dy(n), xx = cx + Nbr<0>::dx(n);
         if (yy < 0 || yy >= h || xx < 0 || xx >= w) continue;
         const float wn = w9[((size_t)b * 9 + n) * HW + r];
 #pragma unroll
@@ -161,7 +148,7 @@ __global__ __launch_bounds__(256) void aggregate9_bwd_w(const float* __restrict_
     for (int k = 0; k < NH; ++k) g[k] = gout[((size_t)k * B + b) * HW + r] * (float)s;
 #pragma unroll
     for (int n = 0; n < 9; ++n) {
-        const int yy = cy + kDy[n], xx = cx + kDx[n];
+        const int yy = cy + Nbr<0>::dy(n), xx = cx + Nbr<0>::dx(n);
         float v = 0.f;
         if (yy >= 0 && yy < h && xx >= 0 && xx < w) {
 #pragma unroll
@@ -190,7 +177,7 @@ __global__ __launch_bounds__(256) void aggregate9_bwd_d(const float* __restrict_
     const int ss = s * s;
     for (int j = lane; j < 9 * ss; j += 64) {
         const int n = j / ss, q = j - n * ss;
-        const int sy = cy - kDy[n], sx = cx - kDx[n];          // the HR cell whose plane-n weight points at (cy,cx)
+        const int sy = cy - Nbr<0>::dy(n), sx = cx - Nbr<0>::dx(n);  // the HR cell whose plane-n weight points at (cy,cx)
         if (sy < 0 || sy >= h || sx < 0 || sx >= w) continue;
         const int Y = sy * s + q / s, X = sx * s + q % s;
         const size_t r = (size_t)Y * W + X;
@@ -207,28 +194,17 @@ __global__ __launch_bounds__(256) void aggregate9_bwd_d(const float* __restrict_
 
 }  // namespace
 
-#define DISPATCH_NH(KERNEL, ...)                                                       \
-    switch (nheads) {                                                                  \
-        case 1: hipLaunchKernelGGL(KERNEL<1>, __VA_ARGS__); break;                     \
-        case 2: hipLaunchKernelGGL(KERNEL<2>, __VA_ARGS__); break;                     \
-        case 3: hipLaunchKernelGGL(KERNEL<3>, __VA_ARGS__); break;                     \
-        default: return ECM_EUNSUP;                                                    \
-    }
-
-template <int NH>
-static constexpr auto softargmin_lse_fwd = softargmin_fwd<NH, true>;
-
 // the plain head (lse == nullptr) and the one that also stores the normaliser: one grid
 static int launch_softargmin_fwd(const float* c0, long long head_stride, float* disp, float* lse, int nheads, int B, int D,
                                  int hw, void* stream) {
     const long long n = (long long)B * hw;
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    if (lse) {
-        DISPATCH_NH(softargmin_lse_fwd, grid, block, 0, ecm_stream(stream), c0, head_stride, disp, lse, B, D, hw)
-    } else {
-        DISPATCH_NH(softargmin_fwd, grid, block, 0, ecm_stream(stream), c0, head_stride, disp, lse, B, D, hw)
-    }
-    return ECM_LAUNCH_RESULT();
+    return ecm_dispatch_heads(nheads, [&](auto nh) {
+        constexpr int NH = decltype(nh)::value;
+        const auto kernel = lse ? softargmin_fwd<NH, true> : softargmin_fwd<NH, false>;
+        hipLaunchKernelGGL(kernel, grid, block, 0, ecm_stream(stream), c0, head_stride, disp, lse, B, D, hw);
+        return ECM_LAUNCH_RESULT();
+    });
 }
 
 extern "C" int ecm_softargmin_heads_fwd(const float* c0, long long head_stride, float* disp, int nheads, int B, int D,
@@ -248,8 +224,11 @@ extern "C" int ecm_softargmin_heads_bwd(const float* c0, long long head_stride, 
     ECM_CHECK_ARG(c0 && gdisp && gc0 && B > 0 && D > 0 && hw > 0);
     const long long n = (long long)B * hw;
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    DISPATCH_NH(softargmin_bwd, grid, block, 0, ecm_stream(stream), c0, head_stride, gdisp, gc0, B, D, hw)
-    return ECM_LAUNCH_RESULT();
+    return ecm_dispatch_heads(nheads, [&](auto nh) {
+        hipLaunchKernelGGL(softargmin_bwd<decltype(nh)::value>, grid, block, 0, ecm_stream(stream), c0, head_stride, gdisp, gc0,
+                           B, D, hw);
+        return ECM_LAUNCH_RESULT();
+    });
 }
 
 extern "C" int ecm_disparity_regression_fwd(const float* x, float* out, int B, int D, int hw, void* stream) {
@@ -265,8 +244,10 @@ extern "C" int ecm_aggregate9_fwd(const float* d, const float* w9, float* out, i
     ECM_CHECK_ARG(d && w9 && out && B > 0 && h > 0 && w > 0 && s > 0);
     const long long n = (long long)B * h * s * w * s;
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    DISPATCH_NH(aggregate9_fwd, grid, block, 0, ecm_stream(stream), d, w9, out, B, h, w, s)
-    return ECM_LAUNCH_RESULT();
+    return ecm_dispatch_heads(nheads, [&](auto nh) {
+        hipLaunchKernelGGL(aggregate9_fwd<decltype(nh)::value>, grid, block, 0, ecm_stream(stream), d, w9, out, B, h, w, s);
+        return ECM_LAUNCH_RESULT();
+    });
 }
 
 extern "C" int ecm_aggregate9_bwd(const float* d, const float* w9, const float* gout, float* gd, float* gw9,
@@ -274,9 +255,11 @@ extern "C" int ecm_aggregate9_bwd(const float* d, const float* w9, const float* 
     ECM_CHECK_ARG(d && w9 && gout && gd && gw9 && B > 0 && h > 0 && w > 0 && s > 0);
     const long long n = (long long)B * h * s * w * s;
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    DISPATCH_NH(aggregate9_bwd_w, grid, block, 0, ecm_stream(stream), d, gout, gw9, B, h, w, s)
     const long long cells = (long long)B * h * w;
     dim3 grid2((unsigned)((cells + 3) / 4));
-    DISPATCH_NH(aggregate9_bwd_d, grid2, block, 0, ecm_stream(stream), w9, gout, gd, B, h, w, s)
-    return ECM_LAUNCH_RESULT();
+    return ecm_dispatch_heads(nheads, [&](auto nh) {
+        hipLaunchKernelGGL(aggregate9_bwd_w<decltype(nh)::value>, grid, block, 0, ecm_stream(stream), d, gout, gw9, B, h, w, s);
+        hipLaunchKernelGGL(aggregate9_bwd_d<decltype(nh)::value>, grid2, block, 0, ecm_stream(stream), w9, gout, gd, B, h, w, s);
+        return ECM_LAUNCH_RESULT();
+    });
 }

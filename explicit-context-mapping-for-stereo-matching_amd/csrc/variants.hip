@@ -7,18 +7,34 @@
 //        softmax(192) -> regression.
 // One thread per output pixel, lanes along X (coalesced rows); the LR column is walked with a rolling window and the
 // softmax over D is the online (running-max) form.  HBM/L2-bound: inputs are ~20 MB of weight planes + LR logits.
+//
+// The volume-mapping head's logits are formed in ONE place, VolumeWalk below: the forward kernel (plain, stats and modal) and
+// both sweeps of the backward kernel hand it a callback per level, so the gradient is taken of the very logits the forward used.
+// The five neighbours of its fuse are Nbr<1> of ecm_nbr.h.  The trilinear head keeps its three hand-written walks: the compiler
+// contracts its interpolation expressions differently from one code shape to the next.
 #include "common.h"
+#include "ecm_nbr.h"
 
 namespace {
 
-struct Online {            // online softmax-weighted mean of D
+// online softmax-weighted mean of D.  FUSED: whether e * d is fused into the sum t.  The one-head kernels have always fused it and
+// the two- and three-head ones never have (there the compiler packs the s and t sums into one instruction); which of the two a
+// kernel gets is written down here, so that the shape of the code around push() cannot move a disparity by an ulp.
+template <bool FUSED>
+struct Online {
     float m, s, t;
     __device__ __forceinline__ void init() { m = -INFINITY; s = 0.f; t = 0.f; }
     __device__ __forceinline__ void push(float v, float d) {
         if (v > m) { const float sc = expf(m - v); s *= sc; t *= sc; m = v; }
         const float e = expf(v - m);
         s += e;
-        t += e * d;
+        if constexpr (FUSED) {
+            t = fmaf(e, d, t);
+        } else {
+#pragma clang fp contract(off)
+            const float ed = e * d;
+            t += ed;
+        }
     }
     __device__ __forceinline__ float result() const { return t / s; }
 };
@@ -28,14 +44,16 @@ struct Online {            // online softmax-weighted mean of D
 // ln s - u / s.  e = exp(v - m) <= 1 with the maximum contributing exactly 1, so s >= 1, u <= 0 and the peak is 1 / s.
 struct Centred {
     float m, mu, var, u;
-    __device__ __forceinline__ void init(const Online& o) { m = o.m; mu = o.result(); var = 0.f; u = 0.f; }
+    template <bool F>
+    __device__ __forceinline__ void init(const Online<F>& o) { m = o.m; mu = o.result(); var = 0.f; u = 0.f; }
     __device__ __forceinline__ void push(float v, float d) {
         const float x = v - m, e = expf(x), c = d - mu;
         var = fmaf(e * c, c, var);
         u = fmaf(e, x, u);
     }
     // stats [NH,3,B,H,W]: o points at (k, 0, b, pixel), plane = B*H*W
-    __device__ __forceinline__ void store(const Online& on, float* __restrict__ o, size_t plane) const {
+    template <bool F>
+    __device__ __forceinline__ void store(const Online<F>& on, float* __restrict__ o, size_t plane) const {
         o[0] = sqrtf(var / on.s);
         o[plane] = 1.f / on.s;
         o[2 * plane] = logf(on.s) - u / on.s;
@@ -84,16 +102,25 @@ __device__ __forceinline__ void load_cum(const float* __restrict__ c, long long 
     for (int k = 0; k < NH; ++k) { acc += c[(size_t)k * hs + idx]; v[k] = acc; }
 }
 
-// 5-neighbour fuse of the LR column at depth j: F_k = sum_n m[n] * C_k[j, cell + n], n = c, r, l, t, b (0 outside)
+// d disp / d logit[D] = p[D] (D - disp), times the incoming gradient: what both backward kernels form from a finished Online
+struct SoftGrad {
+    float mx, inv, pred, g;
+    template <bool F>
+    __device__ __forceinline__ void init(const Online<F>& o, float gout) { mx = o.m; inv = 1.f / o.s; pred = o.t * inv; g = gout; }
+    __device__ __forceinline__ float operator()(float v, int D) const { return expf(v - mx) * inv * ((float)D - pred) * g; }
+};
+
+// ---- the volume-mapping head's logits -----------------------------------------------------------------------------------
+// 5-neighbour fuse of the LR column at depth j: F_k = sum_n m[n] * C_k[j, cell + n], n = c, r, l, t, b: the five planes of
+// Nbr<1> (ecm_nbr.h), the table the weight generator built m5 by (0 outside)
 template <int NH>
 __device__ __forceinline__ void fuse5(const float* __restrict__ c, long long hs, size_t bbase, int j, int h, int w, int cy,
                                       int cx, const float (&m5)[5], float (&F)[NH]) {
-    const int dy[5] = {0, 0, 0, -1, 1}, dx[5] = {0, 1, -1, 0, 0};
 #pragma unroll
     for (int k = 0; k < NH; ++k) F[k] = 0.f;
 #pragma unroll
     for (int n = 0; n < 5; ++n) {
-        const int yy = cy + dy[n], xx = cx + dx[n];
+        const int yy = cy + Nbr<1>::dy(n), xx = cx + Nbr<1>::dx(n);
         if (yy < 0 || yy >= h || xx < 0 || xx >= w) continue;
         float v[NH];
         load_cum<NH>(c, hs, bbase + ((size_t)j * h + yy) * w + xx, v);
@@ -102,38 +129,33 @@ __device__ __forceinline__ void fuse5(const float* __restrict__ c, long long hs,
     }
 }
 
-// MODE 1 (STATS): a second pass over the same logits for stats [NH,3,B,H,W] (std, peak, entropy).  MODE 2 (MODAL): two passes
-// into Modal, for modal [NH,3,B,H,W] (mode, mass, index) in the place of stats, window radius `radius`; it writes no disparity.
-// The loop body below is the only place the logits are formed, so the instantiations cannot drift apart; in MODE 0 the pass
-// loop runs once and the kernel is the one it was.
-template <int NH, int MODE = 0>
-__global__ __launch_bounds__(256) void volume_mapping_fwd(const float* __restrict__ c, long long hs,
-                                                          const float* __restrict__ m5p, const float* __restrict__ mt3p,
-                                                          float* __restrict__ out, float* __restrict__ stats, int B, int Dl,
-                                                          int h, int w, int s, int radius) {
-    constexpr bool STATS = MODE == 1, MODAL = MODE == 2;
-    const int H = h * s, W = w * s;
-    const long long HW = (long long)H * W;
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B * HW) return;
-    const int b = (int)(i / HW);
-    const int r = (int)(i - b * HW);
-    const int Y = r / W, X = r - Y * W;
-    const int cy = Y / s, cx = X / s;
-    float m5[5];
-#pragma unroll
-    for (int n = 0; n < 5; ++n) m5[n] = m5p[((size_t)b * 5 + n) * HW + r];
-    const float* mt = mt3p + (size_t)b * 3 * HW + (size_t)Y * W;      // rows of the three target planes (c, r, l)
-    const size_t bbase = (size_t)b * Dl * h * w;
-    float Fp[NH], Fc[NH], Fn[NH];
-    Online acc[NH];
-    Centred cen[NH];
-    Modal mod[NH];
-#pragma unroll
-    for (int k = 0; k < NH; ++k) acc[k].init();
-#pragma unroll
-    for (int k = 0; k < NH; ++k) mod[k].init();
-    for (int pass = 0; pass < (MODE ? 2 : 1); ++pass) {
+// one level D = j * s + q of a pixel's column: the logits v[k] and what they were formed from
+template <int NH>
+struct VolumeLevel {
+    int D, j;
+    bool has_next;                         // j + 1 < Dl: Fn and tl take part
+    float t0, tr, tl;                      // target weights (c, r, l) at X - D; ones left of the image
+    const float *Fp, *Fc, *Fn;             // the fused column at depths j - 1, j, j + 1
+    float v[NH];
+};
+
+// The walk of one full-resolution pixel (row Y of sample b, column X over LR cell (cy, cx)) through its Dl * s levels: the
+// rolling 5-neighbour fuse Fp/Fc/Fn, the target-weight lookup on the X - D diagonal and the expression of v.  THE ONLY PLACE THE
+// LOGITS OF THIS HEAD ARE FORMED: volume_mapping_fwd (every mode, both passes) and both sweeps of volume_mapping_bwd run it, so
+// the backward's recomputed logits are the forward's to the bit.  level(L) is called once per level, plane_end(j) after the s
+// levels of depth j and before the fuse window rolls.
+template <int NH>
+struct VolumeWalk {
+    const float* __restrict__ c;
+    long long hs;
+    size_t bbase;                          // b * Dl * h * w
+    const float* __restrict__ mt;          // row Y of the three target planes (c, r, l), HW apart
+    long long HW;
+    int Dl, h, w, s, cy, cx, X;
+    const float (&m5)[5];
+    template <class Level, class PlaneEnd>
+    __device__ __forceinline__ void operator()(Level&& level, PlaneEnd&& plane_end) const {
+        float Fp[NH], Fc[NH], Fn[NH];
 #pragma unroll
         for (int k = 0; k < NH; ++k) Fp[k] = 0.f;
         fuse5<NH>(c, hs, bbase, 0, h, w, cy, cx, m5, Fc);
@@ -141,24 +163,61 @@ __global__ __launch_bounds__(256) void volume_mapping_fwd(const float* __restric
             const bool has_next = j + 1 < Dl;
             if (has_next) fuse5<NH>(c, hs, bbase, j + 1, h, w, cy, cx, m5, Fn);
             for (int q = 0; q < s; ++q) {
-                const int D = j * s + q;
-                float t0 = 1.f, tr = 1.f, tl = 1.f;                    // ones_like initialisation (cmfsm_sub_16.py:782-784)
-                if (X >= D) { t0 = mt[X - D]; tr = mt[HW + X - D]; tl = mt[2 * HW + X - D]; }
+                VolumeLevel<NH> L{j * s + q, j, has_next, 1.f, 1.f, 1.f, Fp, Fc, Fn};     // ones_like (cmfsm_sub_16.py:782-784)
+                if (X >= L.D) { L.t0 = mt[X - L.D]; L.tr = mt[HW + X - L.D]; L.tl = mt[2 * HW + X - L.D]; }
 #pragma unroll
                 for (int k = 0; k < NH; ++k) {
-                    float v = Fc[k] * t0;
-                    if (has_next) v = fmaf(Fn[k], tl, v);              // [:, :-s] += fused[:, s:] * T_l[:, :-s]   (:797)
-                    if (j > 0) v = fmaf(Fp[k], tr, v);                 // [:, s:]  += fused[:, :-s] * T_r[:, s:]   (:798)
-                    if constexpr (MODAL) {
-                        if (pass) mod[k].push(v, D, radius);
-                        else mod[k].seek(v, D);
-                    } else if (STATS && pass) cen[k].push(v, (float)D);
-                    else acc[k].push(v, (float)D);
+                    float v = Fc[k] * L.t0;
+                    if (has_next) v = fmaf(Fn[k], L.tl, v);            // [:, :-s] += fused[:, s:] * T_l[:, :-s]   (:797)
+                    if (j > 0) v = fmaf(Fp[k], L.tr, v);               // [:, s:]  += fused[:, :-s] * T_r[:, s:]   (:798)
+                    L.v[k] = v;
                 }
+                level(L);
             }
+            plane_end(j);
 #pragma unroll
             for (int k = 0; k < NH; ++k) { Fp[k] = Fc[k]; Fc[k] = Fn[k]; }
         }
+    }
+};
+
+// MODE 1 (STATS): a second pass over the same logits for stats [NH,3,B,H,W] (std, peak, entropy).  MODE 2 (MODAL): two passes
+// into Modal, for modal [NH,3,B,H,W] (mode, mass, index) in the place of stats, window radius `radius`; it writes no disparity.
+// In MODE 0 the pass loop runs once and the kernel is the one it was.
+template <int NH, int MODE = 0>
+__global__ __launch_bounds__(256) void volume_mapping_fwd(const float* __restrict__ c, long long hs,
+                                                          const float* __restrict__ m5p, const float* __restrict__ mt3p,
+                                                          float* __restrict__ out, float* __restrict__ stats, int B, int Dl,
+                                                          int h, int w, int s, int radius) {
+    const int H = h * s, W = w * s;
+    const long long HW = (long long)H * W;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * HW) return;
+    const int b = (int)(i / HW);
+    const int r = (int)(i - b * HW);
+    const int Y = r / W, X = r - Y * W;
+    float m5[5];
+#pragma unroll
+    for (int n = 0; n < 5; ++n) m5[n] = m5p[((size_t)b * 5 + n) * HW + r];
+    const VolumeWalk<NH> walk{c, hs, (size_t)b * Dl * h * w, mt3p + (size_t)b * 3 * HW + (size_t)Y * W, HW, Dl, h, w, s,
+                              Y / s, X / s, X, m5};
+    constexpr bool STATS = MODE == 1, MODAL = MODE == 2;
+    Online<NH == 1> acc[NH];
+    Centred cen[NH];
+    Modal mod[NH];
+#pragma unroll
+    for (int k = 0; k < NH; ++k) { acc[k].init(); mod[k].init(); }
+    for (int pass = 0; pass < (MODE ? 2 : 1); ++pass) {
+        walk([&](const VolumeLevel<NH>& L) {
+#pragma unroll
+            for (int k = 0; k < NH; ++k) {
+                if constexpr (MODAL) {
+                    if (pass) mod[k].push(L.v[k], L.D, radius);
+                    else mod[k].seek(L.v[k], L.D);
+                } else if (STATS && pass) cen[k].push(L.v[k], (float)L.D);
+                else acc[k].push(L.v[k], (float)L.D);
+            }
+        }, [](int) {});
         if (pass == 0) {                                              // read by the second pass only
 #pragma unroll
             for (int k = 0; k < NH; ++k) cen[k].init(acc[k]);
@@ -177,6 +236,7 @@ __global__ __launch_bounds__(256) void volume_mapping_fwd(const float* __restric
     }
 }
 
+// ---- the trilinear head's logits ----------------------------------------------------------------------------------------
 // PyTorch upsample_trilinear3d source index, align_corners=False
 __device__ __forceinline__ void src_index(int dst, float scale, int in_size, int& i0, int& i1, float& l1) {
     float src = scale * ((float)dst + 0.5f) - 0.5f;
@@ -215,7 +275,7 @@ __global__ __launch_bounds__(256) void trilinear_softargmin_fwd(const float* __r
         for (int k = 0; k < NH; ++k) G[k] = w00 * a[k] + w01 * bq[k] + w10 * cq[k] + w11 * d[k];
     };
     float GA[NH], GB[NH];
-    Online acc[NH];
+    Online<NH == 1> acc[NH];
     Centred cen[NH];
     Modal mod[NH];
 #pragma unroll
@@ -308,9 +368,7 @@ __global__ __launch_bounds__(256) void volume_mapping_bwd(const float* __restric
     for (int e = lane; e < 3 * W; e += 64) T[e] = 0.f;
     wave_fence();
     const int cy = Y / s;
-    const float* mt = mt3p + (size_t)b * 3 * HW + (size_t)Y * W;
     const size_t bbase = (size_t)b * Dl * h * w;
-    const int dy[5] = {0, 0, 0, -1, 1}, dx[5] = {0, 1, -1, 0, 0};
     for (int X0 = 0; X0 < W; X0 += 64) {
         const int X = X0 + lane;
         const bool valid = X < W;
@@ -320,41 +378,22 @@ __global__ __launch_bounds__(256) void volume_mapping_bwd(const float* __restric
         float m5[5], gm[5];
 #pragma unroll
         for (int n = 0; n < 5; ++n) { m5[n] = m5p[((size_t)b * 5 + n) * HW + r]; gm[n] = 0.f; }
-        float Fp[NH], Fc[NH], Fn[NH];
+        const VolumeWalk<NH> walk{c, hs, bbase, mt3p + (size_t)b * 3 * HW + (size_t)Y * W, HW, Dl, h, w, s, cy, cx, Xc, m5};
         // ---- forward sweep: statistics ----------------------------------------------------------------------
-        Online acc[NH];
+        Online<NH == 1> acc[NH];
 #pragma unroll
-        for (int k = 0; k < NH; ++k) { Fp[k] = 0.f; acc[k].init(); }
-        fuse5<NH>(c, hs, bbase, 0, h, w, cy, cx, m5, Fc);
-        for (int j = 0; j < Dl; ++j) {
-            const bool has_next = j + 1 < Dl;
-            if (has_next) fuse5<NH>(c, hs, bbase, j + 1, h, w, cy, cx, m5, Fn);
-            for (int q = 0; q < s; ++q) {
-                const int D = j * s + q;
-                float t0 = 1.f, tr = 1.f, tl = 1.f;
-                if (Xc >= D) { t0 = mt[Xc - D]; tr = mt[HW + Xc - D]; tl = mt[2 * HW + Xc - D]; }
+        for (int k = 0; k < NH; ++k) acc[k].init();
+        walk([&](const VolumeLevel<NH>& L) {
 #pragma unroll
-                for (int k = 0; k < NH; ++k) {
-                    float v = Fc[k] * t0;
-                    if (has_next) v = fmaf(Fn[k], tl, v);
-                    if (j > 0) v = fmaf(Fp[k], tr, v);
-                    acc[k].push(v, (float)D);
-                }
-            }
+            for (int k = 0; k < NH; ++k) acc[k].push(L.v[k], (float)L.D);
+        }, [](int) {});
+        SoftGrad sg[NH];
 #pragma unroll
-            for (int k = 0; k < NH; ++k) { Fp[k] = Fc[k]; Fc[k] = Fn[k]; }
-        }
-        float mx[NH], inv[NH], pred[NH], g[NH];
-#pragma unroll
-        for (int k = 0; k < NH; ++k) {
-            mx[k] = acc[k].m; inv[k] = 1.f / acc[k].s; pred[k] = acc[k].t * inv[k];
-            g[k] = valid ? gout[((size_t)k * B + b) * HW + r] : 0.f;
-        }
+        for (int k = 0; k < NH; ++k) sg[k].init(acc[k], valid ? gout[((size_t)k * B + b) * HW + r] : 0.f);
         // ---- backward sweep ---------------------------------------------------------------------------------
         float gFp[NH], gFc[NH], gFn[NH];
 #pragma unroll
-        for (int k = 0; k < NH; ++k) { Fp[k] = 0.f; gFp[k] = gFc[k] = gFn[k] = 0.f; }
-        fuse5<NH>(c, hs, bbase, 0, h, w, cy, cx, m5, Fc);
+        for (int k = 0; k < NH; ++k) gFp[k] = gFc[k] = gFn[k] = 0.f;
         // emit the finished gF of depth jj: g_m5 and this row's share of the LR-logit gradient
         auto emit = [&](int jj, const float (&gF)[NH]) {
             float suf[NH];                               // gradient w.r.t. the RAW head outputs: suffix sums over heads
@@ -363,7 +402,7 @@ __global__ __launch_bounds__(256) void volume_mapping_bwd(const float* __restric
             for (int k = NH - 1; k >= 0; --k) { run += gF[k]; suf[k] = run; }
 #pragma unroll
             for (int n = 0; n < 5; ++n) {
-                const int yy = cy + dy[n], xx = cx + dx[n];
+                const int yy = cy + Nbr<1>::dy(n), xx = cx + Nbr<1>::dx(n);
                 if (yy < 0 || yy >= h) continue;                              // wave-uniform
                 const bool inb = xx >= 0 && xx < w;
                 if (inb) {
@@ -381,38 +420,28 @@ __global__ __launch_bounds__(256) void volume_mapping_bwd(const float* __restric
                 }
             }
         };
-        for (int j = 0; j < Dl; ++j) {
-            const bool has_next = j + 1 < Dl;
-            if (has_next) fuse5<NH>(c, hs, bbase, j + 1, h, w, cy, cx, m5, Fn);
-            for (int q = 0; q < s; ++q) {
-                const int D = j * s + q;
-                const bool in = Xc >= D;
-                float t0 = 1.f, tr = 1.f, tl = 1.f;
-                if (in) { t0 = mt[Xc - D]; tr = mt[HW + Xc - D]; tl = mt[2 * HW + Xc - D]; }
-                float a0 = 0.f, ar = 0.f, al = 0.f;
+        walk([&](const VolumeLevel<NH>& L) {
+            float a0 = 0.f, ar = 0.f, al = 0.f;
 #pragma unroll
-                for (int k = 0; k < NH; ++k) {
-                    float v = Fc[k] * t0;
-                    if (has_next) v = fmaf(Fn[k], tl, v);
-                    if (j > 0) v = fmaf(Fp[k], tr, v);
-                    const float gv = expf(v - mx[k]) * inv[k] * ((float)D - pred[k]) * g[k];
-                    gFc[k] = fmaf(gv, t0, gFc[k]);
-                    a0 = fmaf(gv, Fc[k], a0);
-                    if (has_next) { gFn[k] = fmaf(gv, tl, gFn[k]); al = fmaf(gv, Fn[k], al); }
-                    if (j > 0) { gFp[k] = fmaf(gv, tr, gFp[k]); ar = fmaf(gv, Fp[k], ar); }
-                }
-                if (in && valid) {                       // 64 lanes, 64 different addresses X - D
-                    const int li = Xc - D;
-                    T[li] += a0;
-                    T[W + li] += ar;
-                    T[2 * W + li] += al;
-                }
-                wave_fence();                            // the next D's read-modify-write hits a neighbour lane's address
+            for (int k = 0; k < NH; ++k) {
+                const float gv = sg[k](L.v[k], L.D);
+                gFc[k] = fmaf(gv, L.t0, gFc[k]);
+                a0 = fmaf(gv, L.Fc[k], a0);
+                if (L.has_next) { gFn[k] = fmaf(gv, L.tl, gFn[k]); al = fmaf(gv, L.Fn[k], al); }
+                if (L.j > 0) { gFp[k] = fmaf(gv, L.tr, gFp[k]); ar = fmaf(gv, L.Fp[k], ar); }
             }
+            if (Xc >= L.D && valid) {                    // 64 lanes, 64 different addresses X - D
+                const int li = Xc - L.D;
+                T[li] += a0;
+                T[W + li] += ar;
+                T[2 * W + li] += al;
+            }
+            wave_fence();                                // the next D's read-modify-write hits a neighbour lane's address
+        }, [&](int j) {
             if (j > 0) emit(j - 1, gFp);
 #pragma unroll
-            for (int k = 0; k < NH; ++k) { Fp[k] = Fc[k]; Fc[k] = Fn[k]; gFp[k] = gFc[k]; gFc[k] = gFn[k]; gFn[k] = 0.f; }
-        }
+            for (int k = 0; k < NH; ++k) { gFp[k] = gFc[k]; gFc[k] = gFn[k]; gFn[k] = 0.f; }
+        });
         emit(Dl - 1, gFp);
         if (valid) {
 #pragma unroll
@@ -440,11 +469,10 @@ __global__ __launch_bounds__(256) void volume_mapping_bwd_gather(const float* __
     const int j = (int)(r % Dl);
     const int b = (int)(r / Dl);
     const int H = h * s;
-    const int dy[5] = {0, 0, 0, -1, 1}, dx[5] = {0, 1, -1, 0, 0};
     float acc = 0.f;
 #pragma unroll
     for (int n = 0; n < 5; ++n) {
-        const int sy = y - dy[n], sx = x - dx[n];                     // the source cell whose neighbour n is (y, x)
+        const int sy = y - Nbr<1>::dy(n), sx = x - Nbr<1>::dx(n);                    // the source cell whose neighbour n is (y, x)
         if (sy < 0 || sy >= h || sx < 0 || sx >= w) continue;
         const float* p = part + (((((size_t)k * B + b) * Dl + j) * H + (size_t)sy * s) * 5 + n) * w + sx;
         float a = 0.f;
@@ -490,7 +518,7 @@ __global__ __launch_bounds__(256) void trilinear_softargmin_bwd(const float* __r
     const float dscale = (float)Dl / (float)Do;
     float mx[NH], inv[NH], pred[NH], g[NH];
     {
-        Online acc[NH];
+        Online<NH == 1> acc[NH];
 #pragma unroll
         for (int k = 0; k < NH; ++k) acc[k].init();
         float GA[NH], GB[NH];
@@ -610,57 +638,32 @@ __global__ __launch_bounds__(256) void trilinear_bwd_reduce_y(const float* __res
 
 }  // namespace
 
-#define DISPATCH_NH(KERNEL, ...)                                                       \
-    switch (nheads) {                                                                  \
-        case 1: hipLaunchKernelGGL(KERNEL<1>, __VA_ARGS__); break;                     \
-        case 2: hipLaunchKernelGGL(KERNEL<2>, __VA_ARGS__); break;                     \
-        case 3: hipLaunchKernelGGL(KERNEL<3>, __VA_ARGS__); break;                     \
-        default: return ECM_EUNSUP;                                                    \
-    }
-
-template <int NH>
-static constexpr auto volume_mapping_stats_fwd = volume_mapping_fwd<NH, 1>;
-template <int NH>
-static constexpr auto volume_mapping_mode_fwd = volume_mapping_fwd<NH, 2>;
-template <int NH>
-static constexpr auto trilinear_softargmin_stats_fwd = trilinear_softargmin_fwd<NH, 1>;
-template <int NH>
-static constexpr auto trilinear_softargmin_mode_fwd = trilinear_softargmin_fwd<NH, 2>;
-
 // the plain heads (stats == nullptr), the ones that also write the statistics, and the modal estimate (radius >= 0: `stats` is
-// the modal buffer and disp is not written): one grid each
+// the modal buffer and disp is not written): one grid each, MODE chosen here
 static int launch_volume_mapping_fwd(const float* c0, long long head_stride, const float* m5, const float* mt3, float* disp,
                                      float* stats, int nheads, int B, int Dl, int h, int w, int s, int radius, void* stream) {
     const long long n = (long long)B * h * s * w * s;
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    if (radius >= 0) {
-        DISPATCH_NH(volume_mapping_mode_fwd, grid, block, 0, ecm_stream(stream), c0, head_stride, m5, mt3, disp, stats, B, Dl, h,
-                    w, s, radius)
-    } else if (stats) {
-        DISPATCH_NH(volume_mapping_stats_fwd, grid, block, 0, ecm_stream(stream), c0, head_stride, m5, mt3, disp, stats, B, Dl, h,
-                    w, s, radius)
-    } else {
-        DISPATCH_NH(volume_mapping_fwd, grid, block, 0, ecm_stream(stream), c0, head_stride, m5, mt3, disp, stats, B, Dl, h, w, s,
-                    radius)
-    }
-    return ECM_LAUNCH_RESULT();
+    return ecm_dispatch_heads(nheads, [&](auto nh) {
+        return ecm_dispatch<0, 1, 2>(radius >= 0 ? 2 : stats ? 1 : 0, [&](auto mode) {
+            hipLaunchKernelGGL((volume_mapping_fwd<decltype(nh)::value, decltype(mode)::value>), grid, block, 0,
+                               ecm_stream(stream), c0, head_stride, m5, mt3, disp, stats, B, Dl, h, w, s, radius);
+            return ECM_LAUNCH_RESULT();
+        });
+    });
 }
 
 static int launch_trilinear_fwd(const float* c0, long long head_stride, float* disp, float* stats, int nheads, int B, int Dl,
                                 int h, int w, int Do, int H, int W, int radius, void* stream) {
     const long long n = (long long)B * H * W;
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    if (radius >= 0) {
-        DISPATCH_NH(trilinear_softargmin_mode_fwd, grid, block, 0, ecm_stream(stream), c0, head_stride, disp, stats, B, Dl, h, w,
-                    Do, H, W, radius)
-    } else if (stats) {
-        DISPATCH_NH(trilinear_softargmin_stats_fwd, grid, block, 0, ecm_stream(stream), c0, head_stride, disp, stats, B, Dl, h, w,
-                    Do, H, W, radius)
-    } else {
-        DISPATCH_NH(trilinear_softargmin_fwd, grid, block, 0, ecm_stream(stream), c0, head_stride, disp, stats, B, Dl, h, w, Do, H,
-                    W, radius)
-    }
-    return ECM_LAUNCH_RESULT();
+    return ecm_dispatch_heads(nheads, [&](auto nh) {
+        return ecm_dispatch<0, 1, 2>(radius >= 0 ? 2 : stats ? 1 : 0, [&](auto mode) {
+            hipLaunchKernelGGL((trilinear_softargmin_fwd<decltype(nh)::value, decltype(mode)::value>), grid, block, 0,
+                               ecm_stream(stream), c0, head_stride, disp, stats, B, Dl, h, w, Do, H, W, radius);
+            return ECM_LAUNCH_RESULT();
+        });
+    });
 }
 
 extern "C" int ecm_volume_mapping_fwd(const float* c0, long long head_stride, const float* m5, const float* mt3,
@@ -721,22 +724,16 @@ extern "C" int ecm_volume_mapping_bwd(const float* c0, long long head_stride, co
     if (lds > 160 * 1024) return ECM_EUNSUP;
     float* part = static_cast<float*>(scratch);
     dim3 grid((unsigned)(((long long)B * H + 3) / 4)), block(256);
-    switch (nheads) {
-#define ECM_VM_CASE(N)                                                                                                         \
-        case N: {                                                                                                              \
-            const hipError_t e = ecm_allow_lds(reinterpret_cast<const void*>(volume_mapping_bwd<N>), (int)lds);               \
-            if (e != hipSuccess) return (int)e;                                                                                \
-            hipLaunchKernelGGL(volume_mapping_bwd<N>, grid, block, lds, st, c0, head_stride, m5, mt3, gdisp, part, gm5, gmt3,  \
-                               B, Dl, h, w, s);                                                                                \
-        } break;
-        ECM_VM_CASE(1) ECM_VM_CASE(2) ECM_VM_CASE(3)
-#undef ECM_VM_CASE
-        default: return ECM_EUNSUP;
-    }
-    const long long n = (long long)nheads * B * Dl * h * w;
-    hipLaunchKernelGGL(volume_mapping_bwd_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, gc0, head_stride,
-                       nheads, B, Dl, h, w, s);
-    return ECM_LAUNCH_RESULT();
+    return ecm_dispatch_heads(nheads, [&](auto nh) {
+        constexpr auto kernel = volume_mapping_bwd<decltype(nh)::value>;
+        const hipError_t e = ecm_allow_lds(reinterpret_cast<const void*>(kernel), (int)lds);
+        if (e != hipSuccess) return (int)e;
+        hipLaunchKernelGGL(kernel, grid, block, lds, st, c0, head_stride, m5, mt3, gdisp, part, gm5, gmt3, B, Dl, h, w, s);
+        const long long n = (long long)nheads * B * Dl * h * w;
+        hipLaunchKernelGGL(volume_mapping_bwd_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, gc0,
+                           head_stride, nheads, B, Dl, h, w, s);
+        return ECM_LAUNCH_RESULT();
+    });
 }
 
 extern "C" long long ecm_trilinear_softargmin_bwd_scratch_bytes(int nheads, int B, int Dl, int h, int w, int H, int W) {
@@ -755,10 +752,13 @@ extern "C" int ecm_trilinear_softargmin_bwd(const float* c0, long long head_stri
     float* Tm = S + rows * W;
     const long long n = (long long)B * H * W;
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    DISPATCH_NH(trilinear_softargmin_bwd, grid, block, 0, st, c0, head_stride, gdisp, S, B, Dl, h, w, Do, H, W)
-    hipLaunchKernelGGL(trilinear_bwd_reduce_x, dim3((unsigned)((rows * w + 255) / 256)), dim3(256), 0, st, S, Tm, rows, w, W);
-    const long long nv = (long long)nheads * B * Dl * h * w;
-    hipLaunchKernelGGL(trilinear_bwd_reduce_y, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, Tm, gc0, head_stride, nheads,
-                       B, Dl, h, w, H);
-    return ECM_LAUNCH_RESULT();
+    return ecm_dispatch_heads(nheads, [&](auto nh) {
+        hipLaunchKernelGGL(trilinear_softargmin_bwd<decltype(nh)::value>, grid, block, 0, st, c0, head_stride, gdisp, S, B, Dl, h,
+                           w, Do, H, W);
+        hipLaunchKernelGGL(trilinear_bwd_reduce_x, dim3((unsigned)((rows * w + 255) / 256)), dim3(256), 0, st, S, Tm, rows, w, W);
+        const long long nv = (long long)nheads * B * Dl * h * w;
+        hipLaunchKernelGGL(trilinear_bwd_reduce_y, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, Tm, gc0, head_stride,
+                           nheads, B, Dl, h, w, H);
+        return ECM_LAUNCH_RESULT();
+    });
 }

@@ -382,21 +382,72 @@ def ecm_weights9(lr, hr, W0, W1, W2, W3):
     return ContextWeights.apply(lr, hr, W0, W1, W2, W3, 0)
 
 
+# The operand contract of a head family, stated once: the plain op's Function.forward and the family's _stats and _mode ops all
+# go through it, under their own name `who`.  Refusals come in one order -- device and dtype, c and the sizes, the mode radius
+# (where one is given), then, with the operands contiguous, the other tensors' shapes -- and all before any launch.  Each
+# returns the contiguous operands, the sizes (NH, B, Dl, h, w, H, W), the head stride of c and the checked radius.
+_NO_RADIUS = object()      # the op takes no mode radius
+
+
+def _volume_operands(who, c, m5, mt3, scale, radius=_NO_RADIUS):
+    _chk(c, m5, mt3)
+    _need(c.dim() == 5 and scale >= 1 and c.numel() > 0, lambda: f"{who}: c {tuple(c.shape)}, scale {scale}")
+    if radius is not _NO_RADIUS:
+        radius = check_mode_radius(radius)
+    c, m5, mt3 = _c(c), _c(m5), _c(mt3)
+    NH, B, Dl, h, w = c.shape
+    H, W = h * scale, w * scale
+    _need(tuple(m5.shape) == (B, 5, H, W) and tuple(mt3.shape) == (B, 3, H, W),
+          lambda: f"{who}: m5 {tuple(m5.shape)} / mt3 {tuple(mt3.shape)} for c {tuple(c.shape)} at scale {scale}: "
+                  "want [B,5,h*scale,w*scale] and [B,3,h*scale,w*scale]")
+    return (c, m5, mt3), (NH, B, Dl, h, w, H, W), C.c_longlong(B * Dl * h * w), radius
+
+
+def _trilinear_operands(who, c, Do, H, W, radius=_NO_RADIUS):
+    _chk(c)
+    _need(c.dim() == 5 and c.numel() > 0 and Do >= 1 and H >= 1 and W >= 1,
+          lambda: f"{who}: c {tuple(c.shape)} -> ({Do}, {H}, {W})")
+    if radius is not _NO_RADIUS:
+        radius = check_mode_radius(radius)
+    c = _c(c)
+    NH, B, Dl, h, w = c.shape
+    return c, (NH, B, Dl, h, w, H, W), C.c_longlong(B * Dl * h * w), radius
+
+
+def _eight_operands(kind, c, w9, scale, radius=_NO_RADIUS):
+    """Of ecm_aggregate9_<kind>.  Also launches the head's first kernel, the column softmax that stores its normalisers:
+    -> ..., d, lse [NH,B,h,w]."""
+    who = f"ecm_aggregate9_{kind}"
+    _chk(c, w9)
+    _need(c.dim() == 5 and c.numel() > 0 and scale >= 1, lambda: f"{who}: c {tuple(c.shape)}, scale {scale}: want [heads,B,D,h,w]")
+    if radius is not _NO_RADIUS:
+        radius = check_mode_radius(radius, scale)
+    c, w9 = _c(c), _c(w9)
+    NH, B, D, h, w = c.shape
+    H, W = h * scale, w * scale
+    _need(tuple(w9.shape) == (B, 9, H, W),
+          lambda: f"{who}: w9 {tuple(w9.shape)} for c {tuple(c.shape)} at scale {scale}: want [B,9,h*scale,w*scale]")
+    d = torch.empty(NH, B, h, w, device=c.device, dtype=c.dtype)
+    lse = torch.empty(NH, B, h, w, device=c.device, dtype=c.dtype)
+    hs = C.c_longlong(B * D * h * w)
+    _lib.call("ecm_softargmin_heads_lse_fwd", _p(c), hs, _p(d), _p(lse), NH, B, D, h * w, _stream())
+    return (c, w9), (NH, B, D, h, w, H, W), hs, radius, d, lse
+
+
+def _head_out(c, sizes, planes=None):
+    """[NH,B,H,W], or the [NH,planes,B,H,W] of a stats / modal buffer, beside c."""
+    NH, B, H, W = sizes[0], sizes[1], sizes[5], sizes[6]
+    return torch.empty((NH, B, H, W) if planes is None else (NH, planes, B, H, W), device=c.device, dtype=c.dtype)
+
+
 class VolumeMapping(torch.autograd.Function):
     """Fused volume-mapping head (cmfsm_sub_16.py:767-801): c [NH,B,Dl,h,w], m5 [B,5,H,W], mt3 [B,3,H,W] -> [NH,B,H,W]."""
 
     @staticmethod
     def forward(ctx, c, m5, mt3, scale):
-        _chk(c, m5, mt3)
-        _need(c.dim() == 5 and scale >= 1 and c.numel() > 0, lambda: f"volume_mapping: c {tuple(c.shape)}, scale {scale}")
-        c, m5, mt3 = _c(c), _c(m5), _c(mt3)
-        NH, B, Dl, h, w = c.shape
-        _need(tuple(m5.shape) == (B, 5, h * scale, w * scale) and tuple(mt3.shape) == (B, 3, h * scale, w * scale),
-              lambda: f"volume_mapping: m5 {tuple(m5.shape)} / mt3 {tuple(mt3.shape)} for c {tuple(c.shape)} at scale {scale}: "
-                      "want [B,5,h*scale,w*scale] and [B,3,h*scale,w*scale]")
-        out = torch.empty(NH, B, h * scale, w * scale, device=c.device, dtype=c.dtype)
-        _lib.call("ecm_volume_mapping_fwd", _p(c), C.c_longlong(B * Dl * h * w), _p(m5), _p(mt3), _p(out), NH, B, Dl, h, w,
-                  scale, _stream())
+        (c, m5, mt3), sizes, hs, _ = _volume_operands("volume_mapping", c, m5, mt3, scale)
+        out = _head_out(c, sizes)
+        _lib.call("ecm_volume_mapping_fwd", _p(c), hs, _p(m5), _p(mt3), _p(out), *sizes[:5], scale, _stream())
         ctx.save_for_backward(c, m5, mt3)
         ctx.scale = scale
         return out
@@ -422,14 +473,9 @@ class TrilinearSoftArgmin(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, c, Do, H, W):
-        _chk(c)
-        _need(c.dim() == 5 and c.numel() > 0 and Do >= 1 and H >= 1 and W >= 1,
-              lambda: f"trilinear_softargmin: c {tuple(c.shape)} -> ({Do}, {H}, {W})")
-        c = _c(c)
-        NH, B, Dl, h, w = c.shape
-        out = torch.empty(NH, B, H, W, device=c.device, dtype=c.dtype)
-        _lib.call("ecm_trilinear_softargmin_fwd", _p(c), C.c_longlong(B * Dl * h * w), _p(out), NH, B, Dl, h, w, Do, H, W,
-                  _stream())
+        c, sizes, hs, _ = _trilinear_operands("trilinear_softargmin", c, Do, H, W)
+        out = _head_out(c, sizes)
+        _lib.call("ecm_trilinear_softargmin_fwd", _p(c), hs, _p(out), *sizes[:5], Do, H, W, _stream())
         ctx.save_for_backward(c)
         ctx.dims = (Do, H, W)
         return out
@@ -463,19 +509,9 @@ def ecm_aggregate9_stats(c, w9, scale):
     """The eight-neighbour head (softargmin_heads + ecm_aggregate9) on c [NH,B,D,h,w] raw classifier outputs and w9 [B,9,H,W],
     with the statistics of each HR pixel's mixture of its valid neighbours' low-resolution distributions."""
     scale = int(scale)
-    _chk(c, w9)
-    _need(c.dim() == 5 and c.numel() > 0 and scale >= 1, lambda: f"ecm_aggregate9_stats: c {tuple(c.shape)}, scale {scale}: want [heads,B,D,h,w]")
-    c, w9 = _c(c.detach()), _c(w9.detach())
-    NH, B, D, h, w = c.shape
-    H, W = h * scale, w * scale
-    _need(tuple(w9.shape) == (B, 9, H, W),
-          lambda: f"ecm_aggregate9_stats: w9 {tuple(w9.shape)} for c {tuple(c.shape)} at scale {scale}: want [B,9,h*scale,w*scale]")
-    d = torch.empty(NH, B, h, w, device=c.device, dtype=c.dtype)
-    lse = torch.empty(NH, B, h, w, device=c.device, dtype=c.dtype)
-    disp = torch.empty(NH, B, H, W, device=c.device, dtype=c.dtype)
-    stats = torch.empty(NH, 3, B, H, W, device=c.device, dtype=c.dtype)
-    hs = C.c_longlong(B * D * h * w)
-    _lib.call("ecm_softargmin_heads_lse_fwd", _p(c), hs, _p(d), _p(lse), NH, B, D, h * w, _stream())
+    (c, w9), sizes, hs, _, d, lse = _eight_operands("stats", c.detach(), w9.detach(), scale)
+    NH, B, D, h, w = sizes[:5]
+    disp, stats = _head_out(c, sizes), _head_out(c, sizes, 3)
     _lib.call("ecm_aggregate9_fwd", _p(d), _p(w9), _p(disp), NH, B, h, w, scale, _stream())
     _lib.call("ecm_aggregate9_stats_fwd", _p(c), hs, _p(lse), _p(w9), _p(stats), NH, B, D, h, w, scale, _stream())
     return _stats_planes(disp, stats)
@@ -485,18 +521,9 @@ def ecm_aggregate9_stats(c, w9, scale):
 def volume_mapping_stats(c, m5, mt3, scale):
     """volume_mapping with the statistics of its softmax over the Dl * scale fused logits."""
     scale = int(scale)
-    _chk(c, m5, mt3)
-    _need(c.dim() == 5 and scale >= 1 and c.numel() > 0, lambda: f"volume_mapping_stats: c {tuple(c.shape)}, scale {scale}")
-    c, m5, mt3 = _c(c.detach()), _c(m5.detach()), _c(mt3.detach())
-    NH, B, Dl, h, w = c.shape
-    H, W = h * scale, w * scale
-    _need(tuple(m5.shape) == (B, 5, H, W) and tuple(mt3.shape) == (B, 3, H, W),
-          lambda: f"volume_mapping_stats: m5 {tuple(m5.shape)} / mt3 {tuple(mt3.shape)} for c {tuple(c.shape)} at scale {scale}: "
-                  "want [B,5,h*scale,w*scale] and [B,3,h*scale,w*scale]")
-    disp = torch.empty(NH, B, H, W, device=c.device, dtype=c.dtype)
-    stats = torch.empty(NH, 3, B, H, W, device=c.device, dtype=c.dtype)
-    _lib.call("ecm_volume_mapping_stats_fwd", _p(c), C.c_longlong(B * Dl * h * w), _p(m5), _p(mt3), _p(disp), _p(stats), NH, B,
-              Dl, h, w, scale, _stream())
+    (c, m5, mt3), sizes, hs, _ = _volume_operands("volume_mapping_stats", c.detach(), m5.detach(), mt3.detach(), scale)
+    disp, stats = _head_out(c, sizes), _head_out(c, sizes, 3)
+    _lib.call("ecm_volume_mapping_stats_fwd", _p(c), hs, _p(m5), _p(mt3), _p(disp), _p(stats), *sizes[:5], scale, _stream())
     return _stats_planes(disp, stats)
 
 
@@ -504,15 +531,9 @@ def volume_mapping_stats(c, m5, mt3, scale):
 def trilinear_softargmin_stats(c, Do, H, W):
     """trilinear_softargmin with the statistics of its softmax over the Do interpolated logits."""
     Do, H, W = int(Do), int(H), int(W)
-    _chk(c)
-    _need(c.dim() == 5 and c.numel() > 0 and Do >= 1 and H >= 1 and W >= 1,
-          lambda: f"trilinear_softargmin_stats: c {tuple(c.shape)} -> ({Do}, {H}, {W})")
-    c = _c(c.detach())
-    NH, B, Dl, h, w = c.shape
-    disp = torch.empty(NH, B, H, W, device=c.device, dtype=c.dtype)
-    stats = torch.empty(NH, 3, B, H, W, device=c.device, dtype=c.dtype)
-    _lib.call("ecm_trilinear_softargmin_stats_fwd", _p(c), C.c_longlong(B * Dl * h * w), _p(disp), _p(stats), NH, B, Dl, h, w,
-              Do, H, W, _stream())
+    c, sizes, hs, _ = _trilinear_operands("trilinear_softargmin_stats", c.detach(), Do, H, W)
+    disp, stats = _head_out(c, sizes), _head_out(c, sizes, 3)
+    _lib.call("ecm_trilinear_softargmin_stats_fwd", _p(c), hs, _p(disp), _p(stats), *sizes[:5], Do, H, W, _stream())
     return _stats_planes(disp, stats)
 
 
@@ -543,20 +564,9 @@ def ecm_aggregate9_mode(c, w9, scale, radius):
     """(mode, mass, index) of each HR pixel's mixture of its valid neighbours' low-resolution distributions (the operands of
     ecm_aggregate9_stats); radius must be a multiple of scale."""
     scale = int(scale)
-    _chk(c, w9)
-    _need(c.dim() == 5 and c.numel() > 0 and scale >= 1, lambda: f"ecm_aggregate9_mode: c {tuple(c.shape)}, scale {scale}: want [heads,B,D,h,w]")
-    radius = check_mode_radius(radius, scale)
-    c, w9 = _c(c.detach()), _c(w9.detach())
-    NH, B, D, h, w = c.shape
-    H, W = h * scale, w * scale
-    _need(tuple(w9.shape) == (B, 9, H, W),
-          lambda: f"ecm_aggregate9_mode: w9 {tuple(w9.shape)} for c {tuple(c.shape)} at scale {scale}: want [B,9,h*scale,w*scale]")
-    d = torch.empty(NH, B, h, w, device=c.device, dtype=c.dtype)
-    lse = torch.empty(NH, B, h, w, device=c.device, dtype=c.dtype)
-    modal = torch.empty(NH, 3, B, H, W, device=c.device, dtype=c.dtype)
-    hs = C.c_longlong(B * D * h * w)
-    _lib.call("ecm_softargmin_heads_lse_fwd", _p(c), hs, _p(d), _p(lse), NH, B, D, h * w, _stream())
-    _lib.call("ecm_aggregate9_mode_fwd", _p(c), hs, _p(lse), _p(w9), _p(modal), NH, B, D, h, w, scale, radius, _stream())
+    (c, w9), sizes, hs, radius, _, lse = _eight_operands("mode", c.detach(), w9.detach(), scale, radius)
+    modal = _head_out(c, sizes, 3)
+    _lib.call("ecm_aggregate9_mode_fwd", _p(c), hs, _p(lse), _p(w9), _p(modal), *sizes[:5], scale, radius, _stream())
     return _mode_planes(modal)
 
 
@@ -564,18 +574,10 @@ def ecm_aggregate9_mode(c, w9, scale, radius):
 def volume_mapping_mode(c, m5, mt3, scale, radius):
     """(mode, mass, index) of volume_mapping's softmax over the Dl * scale fused logits."""
     scale = int(scale)
-    _chk(c, m5, mt3)
-    _need(c.dim() == 5 and scale >= 1 and c.numel() > 0, lambda: f"volume_mapping_mode: c {tuple(c.shape)}, scale {scale}")
-    radius = check_mode_radius(radius)
-    c, m5, mt3 = _c(c.detach()), _c(m5.detach()), _c(mt3.detach())
-    NH, B, Dl, h, w = c.shape
-    H, W = h * scale, w * scale
-    _need(tuple(m5.shape) == (B, 5, H, W) and tuple(mt3.shape) == (B, 3, H, W),
-          lambda: f"volume_mapping_mode: m5 {tuple(m5.shape)} / mt3 {tuple(mt3.shape)} for c {tuple(c.shape)} at scale {scale}: "
-                  "want [B,5,h*scale,w*scale] and [B,3,h*scale,w*scale]")
-    modal = torch.empty(NH, 3, B, H, W, device=c.device, dtype=c.dtype)
-    _lib.call("ecm_volume_mapping_mode_fwd", _p(c), C.c_longlong(B * Dl * h * w), _p(m5), _p(mt3), _p(modal), NH, B, Dl, h, w,
-              scale, radius, _stream())
+    (c, m5, mt3), sizes, hs, radius = _volume_operands("volume_mapping_mode", c.detach(), m5.detach(), mt3.detach(), scale,
+                                                       radius)
+    modal = _head_out(c, sizes, 3)
+    _lib.call("ecm_volume_mapping_mode_fwd", _p(c), hs, _p(m5), _p(mt3), _p(modal), *sizes[:5], scale, radius, _stream())
     return _mode_planes(modal)
 
 
@@ -583,15 +585,9 @@ def volume_mapping_mode(c, m5, mt3, scale, radius):
 def trilinear_softargmin_mode(c, Do, H, W, radius):
     """(mode, mass, index) of trilinear_softargmin's softmax over the Do interpolated logits."""
     Do, H, W = int(Do), int(H), int(W)
-    _chk(c)
-    _need(c.dim() == 5 and c.numel() > 0 and Do >= 1 and H >= 1 and W >= 1,
-          lambda: f"trilinear_softargmin_mode: c {tuple(c.shape)} -> ({Do}, {H}, {W})")
-    radius = check_mode_radius(radius)
-    c = _c(c.detach())
-    NH, B, Dl, h, w = c.shape
-    modal = torch.empty(NH, 3, B, H, W, device=c.device, dtype=c.dtype)
-    _lib.call("ecm_trilinear_softargmin_mode_fwd", _p(c), C.c_longlong(B * Dl * h * w), _p(modal), NH, B, Dl, h, w, Do, H, W,
-              radius, _stream())
+    c, sizes, hs, radius = _trilinear_operands("trilinear_softargmin_mode", c.detach(), Do, H, W, radius)
+    modal = _head_out(c, sizes, 3)
+    _lib.call("ecm_trilinear_softargmin_mode_fwd", _p(c), hs, _p(modal), *sizes[:5], Do, H, W, radius, _stream())
     return _mode_planes(modal)
 
 

@@ -2,8 +2,8 @@
 include/ecm_geometry.h and include/ecm_rectify.h).
 
 The product path has NO fallback: if the library is missing or a call fails, a RuntimeError is
-raised.  Prototypes below mirror include/ecm_hip.h one to one: tests/test_abi_types.py parses the header and compares every
-return type and every parameter type, in order; tests/test_abi.py compares the names with the built library's exports; and
+raised.  Each table below mirrors its header one to one: tests/test_abi_types.py parses every header of TABLES and compares
+every return type and every parameter type, in order, and the names with the built library's exports; and
 tests/test_hip_abi_calls.py checks the values that ops.py hands to them on the device.
 """
 from __future__ import annotations
@@ -146,9 +146,8 @@ PROTOTYPES = {
     "ecm_deconv3d_k3s2_split_fwd": (_I, [_P, _P, _P] + [_I] * 9 + [_P]),     # cmfsm.py:262-268
 }
 
-# The geometry entries (include/ecm_geometry.h, prefix ecmg_): a table of their own, held to their own header by
-# tests/test_disp_reproject_cpu.py.  PROTOTYPES stays the image of include/ecm_hip.h (the network and its post-filters); call(),
-# query() and missing_symbols() serve both.
+# The geometry entries (include/ecm_geometry.h, prefix ecmg_): a table of their own.  PROTOTYPES stays the image of
+# include/ecm_hip.h (the network and its post-filters); call(), query() and missing_symbols() serve every table of TABLES.
 GEOMETRY_PROTOTYPES = {
     "ecmg_reproject_fwd": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _F, _F, _P]),
     "ecmg_point_cloud_tile": (_I, []),
@@ -156,7 +155,7 @@ GEOMETRY_PROTOTYPES = {
     "ecmg_point_cloud_fwd": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _F, _F, _P]),
 }
 
-# The rectification entries (include/ecm_rectify.h, prefix ecmr_): a third table, held to its header by tests/test_rectify_cpu.py.
+# The rectification entries (include/ecm_rectify.h, prefix ecmr_): a third table.
 RECTIFY_PROTOTYPES = {
     "ecmr_rectify_map_params": (_I, []),
     "ecmr_tile_width": (_I, []),
@@ -165,8 +164,18 @@ RECTIFY_PROTOTYPES = {
 }
 
 
+# header file under include/ -> (its table, the prefix its names bear): the registry that load(), missing_symbols() and the census
+# of tests/test_abi_types.py go through.  The values ARE the three dicts above (tests mutate them in place); a fourth header is a
+# fourth row here and nothing else.
+TABLES = {
+    "ecm_hip.h": (PROTOTYPES, "ecm_"),
+    "ecm_geometry.h": (GEOMETRY_PROTOTYPES, "ecmg_"),
+    "ecm_rectify.h": (RECTIFY_PROTOTYPES, "ecmr_"),
+}
+
+
 def _tables():
-    return list(PROTOTYPES.items()) + list(GEOMETRY_PROTOTYPES.items()) + list(RECTIFY_PROTOTYPES.items())
+    return [row for table, _ in TABLES.values() for row in table.items()]
 
 
 _lib = None

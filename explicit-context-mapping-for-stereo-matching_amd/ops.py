@@ -79,12 +79,20 @@ def _host(ctype, values):
     return C.cast((ctype * len(values))(*values), C.c_void_p)
 
 
+_CPU_TENSOR = "ecm ops run only on the MI355X HIP path: got a CPU tensor (no CPU fallback exists)"
+
+
+def _on_device(*ts):
+    for t in ts:
+        if not t.is_cuda:
+            raise RuntimeError(_CPU_TENSOR)
+
+
 def _chk(*ts):
     for t in ts:
         if t is None:
             continue
-        if not t.is_cuda:
-            raise RuntimeError("ecm ops run only on the MI355X HIP path: got a CPU tensor (no CPU fallback exists)")
+        _on_device(t)
         if t.dtype != torch.float32:
             raise RuntimeError(f"ecm ops are fp32 (got {t.dtype})")
 
@@ -104,6 +112,71 @@ def _c(t):
     if t.data_ptr() % 16:
         t = t.clone()
     return t
+
+
+# ---- the operand contract of the post-processing ops (lr_check .. remap_pair, the check_* functions), stated once.  Parameters
+# are refused with ValueError before any tensor is touched; tensors with RuntimeError (_need) before any launch.  Every message
+# is formed only when it is raised.
+_FLT_MAX = 3.4028234663852886e38
+
+
+def _is_real(v, bound=None, fp32=False):
+    """v is a real number, not a bool, finite (fp32: as an fp32 value too) and, where bound is "> 0" or ">= 0", within it."""
+    return not (isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or (fp32 and abs(v) > _FLT_MAX)
+                or (bound == "> 0" and v <= 0) or (bound == ">= 0" and v < 0))
+
+
+def _real(who, name, v, bound=None, fp32=False):
+    """v as a float, or ValueError "<who>: <name> <v>: a finite number[ <bound>]"."""
+    if not _is_real(v, bound, fp32):
+        raise ValueError(f"{who}: {name} {v!r}: a finite number" + (f" {bound}" if bound else ""))
+    return float(v)
+
+
+def _is_int(v):
+    return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+
+
+def _integer(who, name, v, lo, hi=None):
+    """v as an int, or ValueError "<who>: <name> <v>: an integer in <lo>..<hi>" (hi None: "an integer >= <lo>")."""
+    if not _is_int(v) or v < lo or (hi is not None and v > hi):
+        raise ValueError(f"{who}: {name} {v!r}: an integer " + (f">= {lo}" if hi is None else f"in {lo}..{hi}"))
+    return int(v)
+
+
+def _bhw(t):
+    """A [B,1,H,W] tensor as its [B,H,W] view; any other shape as it is, for the caller's _need to name."""
+    return t[:, 0] if t.dim() == 4 and t.shape[1] == 1 else t
+
+
+def _disp_plane(who, disp, want="want [B,H,W] or [B,1,H,W]"):
+    """disp, fp32 on the device, [B,H,W] or [B,1,H,W] and not empty, as its [B,H,W] view."""
+    _chk(disp)
+    disp = _bhw(disp)
+    _need(disp.dim() == 3 and disp.numel() > 0, lambda: f"{who}: disp {tuple(disp.shape)}: {want}")
+    return disp
+
+
+def _plane_like(who, name, t, disp, dtypes, want):
+    """t, on the device and of one of `dtypes` (`want` names them), as a [B,H,W] view of the shape of the plane disp."""
+    _on_device(t)
+    _need(t.dtype in dtypes, lambda: f"{who}: {name} is {t.dtype}: want {want}")
+    t = _bhw(t)
+    _need(t.shape == disp.shape, lambda: f"{who}: {name} {tuple(t.shape)} against disp {tuple(disp.shape)}")
+    return t.detach()
+
+
+def _mask_plane(who, valid, disp):
+    """valid, bool or uint8 of disp's shape, as a contiguous uint8 plane (a bool is one byte, 0 or 1: viewed, not copied)."""
+    valid = _plane_like(who, "valid", valid, disp, (torch.bool, torch.uint8), "bool or uint8").contiguous()
+    return valid.view(torch.uint8) if valid.dtype == torch.bool else valid
+
+
+def _guide(who, guide, d):
+    """guide [B,C,H,W], C in 1..4 (fp32 on the device: the caller's _chk), against the plane d [B,H,W]: contiguous and aligned."""
+    _need(guide.dim() == 4 and guide.shape[0] == d.shape[0] and 1 <= guide.shape[1] <= 4 and guide.shape[2:] == d.shape[1:],
+          lambda: f"{who}: guide {tuple(guide.shape)} against disp {tuple(d.shape)}: want [B,C,H,W], C in 1..4")
+    return _c(guide.detach())
 
 
 def _empty_like(t):
@@ -544,7 +617,7 @@ def trilinear_softargmin_stats(c, Do, H, W):
 def check_mode_radius(radius, scale=1):
     """radius as an int: a non-negative integer number of full-resolution pixels, a multiple of `scale` where the levels of p
     are `scale` pixels apart (the eight-neighbour head)."""
-    if isinstance(radius, bool) or not isinstance(radius, numbers.Integral):
+    if not _is_int(radius):
         raise ValueError(f"mode radius {radius!r}: an integer number of full-resolution pixels")
     radius = int(radius)
     if radius < 0:
@@ -604,12 +677,7 @@ def lr_check_max_width():
 
 def check_lr_tolerances(threshold, rel):
     """(threshold, rel) as floats: both finite and >= 0 (pixels; a share of the disparity)."""
-    out = []
-    for name, v in (("threshold", threshold), ("rel", rel)):
-        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v < 0:
-            raise ValueError(f"lr_check: {name} {v!r}: a finite number >= 0")
-        out.append(float(v))
-    return tuple(out)
+    return _real("lr_check", "threshold", threshold, ">= 0"), _real("lr_check", "rel", rel, ">= 0")
 
 
 @torch.no_grad()
@@ -623,10 +691,7 @@ def lr_check(disp_l, disp_r, threshold=1.0, rel=0.0, mirrored=False, with_source
     has none); src (int32, with_source=True) the column it came from, -1 for none."""
     threshold, rel = check_lr_tolerances(threshold, rel)               # before any device work
     _chk(disp_l, disp_r)
-    if disp_l.dim() == 4 and disp_l.shape[1] == 1:
-        disp_l = disp_l[:, 0]
-    if disp_r.dim() == 4 and disp_r.shape[1] == 1:
-        disp_r = disp_r[:, 0]
+    disp_l, disp_r = _bhw(disp_l), _bhw(disp_r)
     _need(disp_l.dim() == 3 and disp_l.numel() > 0 and disp_r.shape == disp_l.shape,
           lambda: f"lr_check: disp_l {tuple(disp_l.shape)}, disp_r {tuple(disp_r.shape)}: want two equal [B,H,W] or [B,1,H,W]")
     B, H, W = disp_l.shape
@@ -652,10 +717,7 @@ def disp_filter_max_radius(kind):
 
 
 def _check_filter_radius(who, kind, radius):
-    top = disp_filter_max_radius(kind)
-    if isinstance(radius, bool) or not isinstance(radius, numbers.Integral) or not 1 <= radius <= top:
-        raise ValueError(f"{who}: radius {radius!r}: an integer in 1..{top}")
-    return int(radius)
+    return _integer(who, "radius", radius, 1, disp_filter_max_radius(kind))
 
 
 def check_median_radius(radius, who="disparity_median"):
@@ -665,31 +727,14 @@ def check_median_radius(radius, who="disparity_median"):
 
 def check_bilateral_parameters(radius, sigma_space, sigma_color, who="disparity_bilateral"):
     """(radius, sigma_space, sigma_color): an int in 1..disp_filter_max_radius("bilateral") and two finite floats > 0."""
-    radius = _check_filter_radius(who, "bilateral", radius)
-    out = []
-    for name, v in (("sigma_space", sigma_space), ("sigma_color", sigma_color)):
-        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v <= 0:
-            raise ValueError(f"{who}: {name} {v!r}: a finite number > 0")
-        out.append(float(v))
-    return (radius,) + tuple(out)
+    return (_check_filter_radius(who, "bilateral", radius), _real(who, "sigma_space", sigma_space, "> 0"),
+            _real(who, "sigma_color", sigma_color, "> 0"))
 
 
 def _filter_planes(who, disp, valid):
     """disp as a contiguous [B,H,W] plane and valid as a contiguous uint8 plane of the same shape (or None)."""
-    _chk(disp)
-    if disp.dim() == 4 and disp.shape[1] == 1:
-        disp = disp[:, 0]
-    _need(disp.dim() == 3 and disp.numel() > 0, lambda: f"{who}: disp {tuple(disp.shape)}: want [B,H,W] or [B,1,H,W]")
-    if valid is not None:
-        _need(valid.is_cuda, "ecm ops run only on the MI355X HIP path: got a CPU tensor (no CPU fallback exists)")
-        _need(valid.dtype in (torch.bool, torch.uint8), lambda: f"{who}: valid is {valid.dtype}: want bool or uint8")
-        if valid.dim() == 4 and valid.shape[1] == 1:
-            valid = valid[:, 0]
-        _need(valid.shape == disp.shape, lambda: f"{who}: valid {tuple(valid.shape)} against disp {tuple(disp.shape)}")
-        valid = valid.detach().contiguous()
-        if valid.dtype == torch.bool:
-            valid = valid.view(torch.uint8)                            # a bool is one byte, 0 or 1: no copy
-    return _c(disp.detach()), valid
+    disp = _disp_plane(who, disp)
+    return _c(disp.detach()), None if valid is None else _mask_plane(who, valid, disp)
 
 
 @torch.no_grad()
@@ -718,9 +763,7 @@ def disparity_bilateral(disp, guide, valid=None, radius=4, sigma_space=2.0, sigm
     _chk(guide)
     d, v = _filter_planes("disparity_bilateral", disp, valid)
     B, H, W = d.shape
-    _need(guide.dim() == 4 and guide.shape[0] == B and 1 <= guide.shape[1] <= 4 and tuple(guide.shape[2:]) == (H, W),
-          lambda: f"disparity_bilateral: guide {tuple(guide.shape)} against disp {tuple(d.shape)}: want [B,C,H,W], C in 1..4")
-    g = _c(guide.detach())
+    g = _guide("disparity_bilateral", guide, d)
     out = torch.empty(2, B, H, W, device=d.device, dtype=d.dtype)
     _lib.call("ecm_disp_bilateral_fwd", _p(d), _p(v), _p(g), _p(out), B, g.shape[1], H, W, radius, sigma_space, sigma_color, _stream())
     return (out[0], out[1]) if with_weight else out[0]
@@ -731,11 +774,7 @@ def disparity_bilateral(disp, guide, valid=None, radius=4, sigma_space=2.0, sigm
 # |d[p] - d[q]| <= max_diff), each pixel's segment label and size, and the map with the segments of at most max_size pixels removed.
 def check_speckle_parameters(max_size, max_diff, who="disparity_speckle"):
     """(max_size, max_diff) as an int and a float: an integer >= 0 (pixels) and a finite number >= 0 (pixels of disparity)."""
-    if isinstance(max_size, bool) or not isinstance(max_size, numbers.Integral) or max_size < 0:
-        raise ValueError(f"{who}: max_size {max_size!r}: an integer >= 0")
-    if isinstance(max_diff, bool) or not isinstance(max_diff, numbers.Real) or not math.isfinite(max_diff) or max_diff < 0:
-        raise ValueError(f"{who}: max_diff {max_diff!r}: a finite number >= 0")
-    return int(max_size), float(max_diff)
+    return _integer(who, "max_size", max_size, 0), _real(who, "max_diff", max_diff, ">= 0")
 
 
 @torch.no_grad()
@@ -764,14 +803,8 @@ WLS_MAX_ITERATIONS = 8
 
 def check_wls_parameters(lam, sigma_color, iterations, who="disparity_wls"):
     """(lam, sigma_color, iterations): two finite floats > 0 and an int in 1..8."""
-    out = []
-    for name, v in (("lam", lam), ("sigma_color", sigma_color)):
-        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v <= 0:
-            raise ValueError(f"{who}: {name} {v!r}: a finite number > 0")
-        out.append(float(v))
-    if isinstance(iterations, bool) or not isinstance(iterations, numbers.Integral) or not 1 <= iterations <= WLS_MAX_ITERATIONS:
-        raise ValueError(f"{who}: iterations {iterations!r}: an integer in 1..{WLS_MAX_ITERATIONS}")
-    return out[0], out[1], int(iterations)
+    return (_real(who, "lam", lam, "> 0"), _real(who, "sigma_color", sigma_color, "> 0"),
+            _integer(who, "iterations", iterations, 1, WLS_MAX_ITERATIONS))
 
 
 @torch.no_grad()
@@ -790,16 +823,9 @@ def disparity_wls(disp, guide, confidence=None, lam=8000.0, sigma_color=0.25, it
     B, H, W = d.shape
     conf = confidence
     if conf is not None:
-        _need(conf.is_cuda, "ecm ops run only on the MI355X HIP path: got a CPU tensor (no CPU fallback exists)")
-        _need(conf.dtype in (torch.float32, torch.bool, torch.uint8),
-              lambda: f"disparity_wls: confidence is {conf.dtype}: want float32, bool or uint8")
-        if conf.dim() == 4 and conf.shape[1] == 1:
-            conf = conf[:, 0]
-        _need(conf.shape == d.shape, lambda: f"disparity_wls: confidence {tuple(conf.shape)} against disp {tuple(d.shape)}")
-        conf = _c(conf.detach().to(torch.float32))
-    _need(guide.dim() == 4 and guide.shape[0] == B and 1 <= guide.shape[1] <= 4 and tuple(guide.shape[2:]) == (H, W),
-          lambda: f"disparity_wls: guide {tuple(guide.shape)} against disp {tuple(d.shape)}: want [B,C,H,W], C in 1..4")
-    g = _c(guide.detach())
+        conf = _c(_plane_like("disparity_wls", "confidence", conf, d, (torch.float32, torch.bool, torch.uint8),
+                              "float32, bool or uint8").to(torch.float32))
+    g = _guide("disparity_wls", guide, d)
     out = torch.empty(2, B, H, W, device=d.device, dtype=d.dtype)
     scratch = _scratch(_lib.query("ecm_disp_wls_scratch_bytes", B, H, W), d.device)
     # B * H * W >= 2^31 is refused by the library before any launch (ECM_EUNSUP -> RuntimeError)
@@ -825,10 +851,7 @@ def disparity_splat(disp, with_source=False):
     Fed to lr_check(disp, right, mirrored=False) it marks the occlusions that disp's own geometry implies, from one inference:
     every in-view pixel reads only columns it wrote to, so r >= d, error = r - d and kind 2 never occurs.  Integer maxima only:
     bit-reproducible."""
-    _chk(disp)
-    if disp.dim() == 4 and disp.shape[1] == 1:
-        disp = disp[:, 0]
-    _need(disp.dim() == 3 and disp.numel() > 0, lambda: f"disparity_splat: disp {tuple(disp.shape)}: want a non-empty [B,H,W] or [B,1,H,W]")
+    disp = _disp_plane("disparity_splat", disp, "want a non-empty [B,H,W] or [B,1,H,W]")
     B, H, W = disp.shape
     d = _c(disp.detach())
     right = torch.empty(B, H, W, device=d.device, dtype=d.dtype)
@@ -842,7 +865,6 @@ def disparity_splat(disp, with_source=False):
 # DESIGN.md section 23; include/ecm_geometry.h.  Forward only: [X Y Z W]^T = Q [x y d 1]^T in fp64 on the device, the point
 # (X/W, Y/W, Z/W) rounded once to fp32 -- OpenCV's reprojectImageTo3D -- as a dense map and as a packed cloud.
 REPROJECT_MAX_ATTRIBUTES = 4
-_FLT_MAX = 3.4028234663852886e38
 
 
 def q_matrix(focal, baseline, cx, cy, cx_right=None, x0=0, y0=0):
@@ -853,8 +875,7 @@ def q_matrix(focal, baseline, cx, cy, cx_right=None, x0=0, y0=0):
     that the disparity map covers (what frame_prep was given as crop_x0, crop_y0)."""
     vals = {"focal": focal, "baseline": baseline, "cx": cx, "cy": cy, "cx_right": cx if cx_right is None else cx_right, "x0": x0, "y0": y0}
     for name, v in vals.items():
-        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v):
-            raise ValueError(f"q_matrix: {name} {v!r}: a finite number")
+        _real("q_matrix", name, v)
     if focal <= 0 or baseline <= 0:
         raise ValueError(f"q_matrix: focal {focal!r} and baseline {baseline!r}: both > 0")
     f, b = float(focal), float(baseline)
@@ -875,8 +896,7 @@ def check_reproject_parameters(Q, min_disp=0.0, max_disp=None, n_attributes=0, w
         raise ValueError(f"{who}: Q {what}: a floating-point [4,4] or [B,4,4] tensor")
     if not Q.is_cuda and not bool(torch.isfinite(Q).all()):
         raise ValueError(f"{who}: Q has a non-finite entry")
-    if isinstance(min_disp, bool) or not isinstance(min_disp, numbers.Real) or not math.isfinite(min_disp) or abs(min_disp) > _FLT_MAX:
-        raise ValueError(f"{who}: min_disp {min_disp!r}: a finite number")
+    _real(who, "min_disp", min_disp, fp32=True)
     if max_disp is None:
         max_disp = _FLT_MAX
     if isinstance(max_disp, bool) or not isinstance(max_disp, numbers.Real) or not max_disp >= min_disp:
@@ -1914,8 +1934,7 @@ def _frame_prep(frames, crop_y0, crop_x0, th, tw, split, tail, mean, std, want_i
     packed = isinstance(frames, (tuple, list))
     if packed:
         rgb, dsp = frames
-        if not (rgb.is_cuda and dsp.is_cuda):
-            raise RuntimeError("ecm ops run only on the MI355X HIP path: got a CPU tensor (no CPU fallback exists)")
+        _on_device(rgb, dsp)
         if rgb.dtype != torch.uint8 or dsp.dtype not in (torch.float16, torch.float32) or rgb.shape[-1] != 6 \
                 or tuple(rgb.shape[:3]) != tuple(dsp.shape):
             raise RuntimeError(f"packed shard must be (uint8 [B,H,W,6], fp16|fp32 [B,H,W]), got {rgb.dtype} {tuple(rgb.shape)} / "
@@ -1984,7 +2003,7 @@ def _camera(who, name, K, D):
 
 def _hw(who, name, size):
     if not isinstance(size, (tuple, list)) or len(size) != 2 or \
-            any(isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 1 for v in size):
+            any(not _is_int(v) or v < 1 for v in size):
         raise ValueError(f"{who}: {name} {size!r}: (H, W), two positive ints")
     return int(size[0]), int(size[1])
 
@@ -2051,10 +2070,9 @@ def stereo_rectify(K1, D1, K2, D2, R, T, size, new_size=None, focal=None, center
     R, T = _calib(who, "R", R, (3, 3)), _calib(who, "T", T, (3,))
     H, W = _hw(who, "size", size)
     Hn, Wn = (H, W) if new_size is None else _hw(who, "new_size", new_size)
-    if focal is not None and (isinstance(focal, bool) or not isinstance(focal, numbers.Real) or not math.isfinite(focal) or focal <= 0):
+    if focal is not None and not _is_real(focal, "> 0"):
         raise ValueError(f"{who}: focal {focal!r}: None or a finite number > 0")
-    if center is not None and (not isinstance(center, (tuple, list)) or len(center) != 2 or any(
-            isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) for v in center)):
+    if center is not None and (not isinstance(center, (tuple, list)) or len(center) != 2 or not all(_is_real(v) for v in center)):
         raise ValueError(f"{who}: center {center!r}: None or (cx, cy), two finite numbers")
     eye = torch.eye(3, dtype=torch.float64)
     if float((R @ R.T - eye).abs().max()) > 1e-6 or float(torch.linalg.det(R)) < 0:
@@ -2122,8 +2140,7 @@ def rectify_map(K, D, R, P, new_size, device):
 
 
 def _norm3(who, name, values, nonzero):
-    if not isinstance(values, (tuple, list)) or len(values) != 3 or any(
-            isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or (nonzero and v == 0) for v in values):
+    if not isinstance(values, (tuple, list)) or len(values) != 3 or not all(_is_real(v) and not (nonzero and v == 0) for v in values):
         raise ValueError(f"{who}: {name} {values!r}: three finite numbers" + (", none zero" if nonzero else ""))
     return [float(v) for v in values]
 
@@ -2143,7 +2160,7 @@ def remap_pair(left_raw, right_raw, map_left, map_right, mean=FLYING3D_MEAN, std
     who = "remap_pair"
     for t in (left_raw, right_raw, map_left, map_right):
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise RuntimeError("ecm ops run only on the MI355X HIP path: got a CPU tensor (no CPU fallback exists)")
+            raise RuntimeError(_CPU_TENSOR)
     u8 = left_raw.dtype == torch.uint8
     _need(left_raw.dim() == 4 and ((u8 and left_raw.shape[3] == 3) or (left_raw.dtype == torch.float32 and left_raw.shape[1] == 3))
           and left_raw.numel() > 0,
@@ -2157,8 +2174,7 @@ def remap_pair(left_raw, right_raw, map_left, map_right, mean=FLYING3D_MEAN, std
     _need(map_right.dtype == torch.float32 and map_right.shape == map_left.shape,
           lambda: f"{who}: map_right {map_right.dtype} {tuple(map_right.shape)} against map_left {tuple(map_left.shape)}")
     m3, s3 = _norm3(who, "mean", mean, False), _norm3(who, "std", std, True)
-    if isinstance(border, bool) or not isinstance(border, numbers.Real) or not math.isfinite(border) or abs(border) > _FLT_MAX:
-        raise ValueError(f"{who}: border {border!r}: a finite number")
+    _real(who, "border", border, fp32=True)
     Ho, Wo = map_left.shape[-2:]
     lr, rr, ml, mr = left_raw.detach().contiguous(), right_raw.detach().contiguous(), _c(map_left.detach()), _c(map_right.detach())
     dev = lr.device
@@ -2244,11 +2260,7 @@ def check_sparsification_parameters(n_measures, steps, maxdisp=192, who="eval_sp
     max_k, max_steps = eval_sparsification_limits()
     if not 1 <= n_measures <= max_k:
         raise ValueError(f"{who}: {n_measures} measures: 1..{max_k}")
-    if isinstance(steps, bool) or not isinstance(steps, numbers.Integral) or not 1 <= steps <= max_steps:
-        raise ValueError(f"{who}: steps {steps!r}: an integer in 1..{max_steps}")
-    if isinstance(maxdisp, bool) or not isinstance(maxdisp, numbers.Real) or not math.isfinite(maxdisp) or maxdisp <= 0:
-        raise ValueError(f"{who}: maxdisp {maxdisp!r}: a finite number > 0")
-    return int(steps), float(maxdisp)
+    return _integer(who, "steps", steps, 1, max_steps), _real(who, "maxdisp", maxdisp, "> 0")
 
 
 def sparsification_areas(curve, oracle):

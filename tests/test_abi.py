@@ -3,28 +3,15 @@ include/ecm_hip.h declares, and the ctypes prototypes cover exactly that set (th
 calls."""
 import ctypes
 import os
-import re
 
 import pytest
 
 from conftest import ROOT
-
-HEADER = os.path.join(ROOT, "include", "ecm_hip.h")
+from test_abi_types import declared, lib_mod  # noqa: F401  (lib_mod: the fixture that builds the library where it is missing)
 
 
 def declared_functions():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(ecm_[a-z0-9_]+)\s*\(", src)))
-
-
-@pytest.fixture(scope="module")
-def lib_mod():
-    import ecm_amd
-    if not os.path.exists(ecm_amd._lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return ecm_amd._lib
+    return sorted(declared("ecm_hip.h"))
 
 
 def test_header_declares_functions():

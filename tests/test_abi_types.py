@@ -1,11 +1,12 @@
-"""The ctypes prototypes of ecm_amd._lib against include/ecm_hip.h, type by type, and the entry-point names the package passes
-against the prototype table.  The header is the truth: the kernels are compiled against it (csrc/common.h includes it), while
-PROTOTYPES is written by hand.  Needs neither a device nor the built library: the header and the Python sources are read as
-text, `ecm_amd._lib` is imported for its table only.
+"""The ctypes prototypes of ecm_amd._lib against the headers under include/, type by type, and the entry-point names the package
+passes against the prototype tables: one census, run once per row of ecm_amd._lib.TABLES (header -> table).  The header is the
+truth: the kernels are compiled against it (csrc/common.h includes it), while the tables are written by hand.  The header and the
+Python sources are read as text; only the export check opens the built library, and nothing here needs a device.
 
 tests/test_hip_abi_calls.py is the GPU half: it checks the VALUES that ops.py hands to these prototypes."""
 import ast
 import ctypes as C
+import importlib
 import os
 import re
 
@@ -13,7 +14,7 @@ import pytest
 
 from conftest import ROOT
 
-HEADER = os.path.join(ROOT, "include", "ecm_hip.h")
+INCLUDE = os.path.join(ROOT, "include")
 PACKAGE = os.path.join(ROOT, "explicit-context-mapping-for-stereo-matching_amd")
 
 # The one table from C value types to ctypes classes.  Every pointer PARAMETER is c_void_p (ops.py passes addresses as integers),
@@ -134,34 +135,96 @@ def compare(header, prototypes):
     return bad
 
 
-def prototypes():
+# ---- the registry -------------------------------------------------------------------------------------------------------------
+# The census below runs once per header of ecm_amd._lib.TABLES.  The names are spelled out here because parametrize needs them
+# before the package is imported; test_the_census_covers_every_table holds this list to the registry.
+HEADERS = ("ecm_hip.h", "ecm_geometry.h", "ecm_rectify.h")
+TABLE_NAME = {"ecm_hip.h": "PROTOTYPES", "ecm_geometry.h": "GEOMETRY_PROTOTYPES", "ecm_rectify.h": "RECTIFY_PROTOTYPES"}
+ENTRIES_IN = {"ecm_geometry.h": "test_disp_reproject_cpu", "ecm_rectify.h": "test_rectify_cpu"}   # modules with an ENTRIES list
+census = pytest.mark.parametrize("header", HEADERS)
+
+
+def registry():
     import ecm_amd
-    return ecm_amd._lib.PROTOTYPES
+    return ecm_amd._lib.TABLES
 
 
-def header_prototypes():
-    with open(HEADER) as f:
+def prototypes(header="ecm_hip.h"):
+    return registry()[header][0]
+
+
+def header_prototypes(header="ecm_hip.h"):
+    with open(os.path.join(INCLUDE, header)) as f:
         return parse_header(f.read())
 
 
-# ---- the real header ---------------------------------------------------------------------------------------------------------
-
-def test_every_declaration_parses_and_is_counted():
-    PROTOTYPES = prototypes()
-    from test_abi import declared_functions
-    parsed = header_prototypes()                                                    # an unknown type raises, naming the declaration
-    assert sorted(parsed) == declared_functions()
-    assert len(parsed) == len(declared_functions()) == len(PROTOTYPES)
+def declared(header="ecm_hip.h"):
+    """The set of names `header` declares, by a plain search of its text without comments: what a per-op test asks "is my entry
+    declared" of, and the count that the census holds parse_header to."""
+    with open(os.path.join(INCLUDE, header)) as f:
+        return set(re.findall(rf"\b({registry()[header][1]}[a-z0-9_]+)\s*\(", _strip(f.read())))
 
 
-def test_prototypes_match_header_type_by_type():
-    PROTOTYPES = prototypes()
-    parsed = header_prototypes()
-    bad = compare(parsed, PROTOTYPES)
+@pytest.fixture(scope="module")
+def lib_mod():
+    import ecm_amd
+    if not os.path.exists(ecm_amd._lib.LIB_PATH):
+        import __graft_entry__
+        __graft_entry__.build()
+    return ecm_amd._lib
+
+
+# ---- the census: every header against its table --------------------------------------------------------------------------------
+
+def test_the_census_covers_every_table():
+    import ecm_amd
+    assert tuple(registry()) == HEADERS and all(os.path.exists(os.path.join(INCLUDE, h)) for h in HEADERS)
+    assert all(registry()[h][0] is getattr(ecm_amd._lib, TABLE_NAME[h]) for h in HEADERS)    # the dicts that tests mutate in place
+
+
+@census
+def test_every_declaration_parses_and_is_counted(header):
+    table, prefix = registry()[header]
+    parsed = header_prototypes(header)                                              # an unknown type raises, naming the declaration
+    assert sorted(parsed) == sorted(declared(header)) == sorted(table)
+    assert len(parsed) == len(declared(header)) == len(table) > 0
+    assert all(n.startswith(prefix) for n in parsed)
+    if header in ENTRIES_IN:
+        assert sorted(parsed) == sorted(importlib.import_module(ENTRIES_IN[header]).ENTRIES)
+    tables = [set(t) for t, _ in registry().values()]
+    for i, a in enumerate(tables):                                                  # all the tables, pairwise disjoint
+        for b in tables[i + 1:]:
+            assert not a & b, sorted(a & b)
+
+
+@census
+def test_prototypes_match_header_type_by_type(header):
+    table, parsed = prototypes(header), header_prototypes(header)
+    bad = compare(parsed, table)
     assert not bad, "\n".join(f"{n}: {'return' if i == -1 else 'names' if i is None else f'parameter {i}'}: header {h}, _lib.py {p}"
                               for n, i, h, p in bad)
-    compared = [n for n in parsed if PROTOTYPES[n] == parsed[n]]                    # the equality the table is used by, row by row
-    assert len(compared) == len(parsed) == len(PROTOTYPES)
+    compared = [n for n in parsed if table[n] == parsed[n]]                         # the equality the table is used by, row by row
+    assert len(compared) == len(parsed) == len(table)
+
+
+@census
+def test_library_exports_every_row_and_load_types_it(header, lib_mod):
+    table, prefix = registry()[header]
+    lib = C.CDLL(lib_mod.LIB_PATH)
+    assert [n for n in sorted(declared(header)) if not hasattr(lib, n)] == []
+    assert lib_mod.missing_symbols() == []
+    real = dict(table)
+    try:                                                                            # missing_symbols() covers this table, in place
+        table[prefix + "not_there"] = (C.c_int, [])
+        assert lib_mod.missing_symbols() == [prefix + "not_there"]
+    finally:
+        table.clear()
+        table.update(real)
+    loaded = lib_mod.load()
+    for name, (res, args) in table.items():                                         # load() typed them
+        assert getattr(loaded, name).restype is res and list(getattr(loaded, name).argtypes) == args, name
+    with pytest.raises(RuntimeError, match="does not export"):
+        lib_mod.call(prefix + "not_there")
 
 
 def test_parser_reads_the_forms_the_header_uses():
@@ -262,11 +325,11 @@ ABI_ONLY = {
 }
 
 
-def package_entry_names():
-    """{name: ["file:line", ...]} of every entry point the package's Python sources name: a whole string literal ecm_* (what
-    _lib.call, _lib.query, _call_scratch, _gn_launch and the tables they are fed from receive).  The sources are walked as
-    syntax trees, so comments do not count; docstrings, pieces of f-strings (labels of error messages) and the PROTOTYPES table
-    itself are left out."""
+def package_entry_names(pattern=r"ecm_[a-z0-9_]+", table_name="PROTOTYPES"):
+    """{name: ["file:line", ...]} of every entry point the package's Python sources name: a whole string literal matching
+    `pattern` (what _lib.call, _lib.query, _call_scratch, _gn_launch and the tables they are fed from receive).  The sources are
+    walked as syntax trees, so comments do not count; docstrings, pieces of f-strings (labels of error messages) and the
+    assignment of `table_name` in _lib.py, the table itself, are left out."""
     found = {}
     for fn in sorted(os.listdir(PACKAGE)):
         if not fn.endswith(".py"):
@@ -277,7 +340,7 @@ def package_entry_names():
         for node in ast.walk(tree):
             if fn == "_lib.py" and isinstance(node, (ast.Assign, ast.AnnAssign)):
                 tgt = node.targets[0] if isinstance(node, ast.Assign) else node.target
-                if isinstance(tgt, ast.Name) and tgt.id == "PROTOTYPES":
+                if isinstance(tgt, ast.Name) and tgt.id == table_name:
                     skip.update(id(n) for n in ast.walk(node))
             if isinstance(node, ast.JoinedStr):
                 skip.update(id(n) for n in ast.walk(node))
@@ -287,16 +350,23 @@ def package_entry_names():
         for node in ast.walk(tree):
             if id(node) in skip:
                 continue
-            if isinstance(node, ast.Constant) and isinstance(node.value, str) and re.fullmatch(r"ecm_[a-z0-9_]+", node.value):
+            if isinstance(node, ast.Constant) and isinstance(node.value, str) and re.fullmatch(pattern, node.value):
                 found.setdefault(node.value, []).append(f"{fn}:{node.lineno}")
     return found
 
 
-def test_every_name_the_package_passes_is_a_prototype():
-    found = package_entry_names()
-    assert len(found) >= 100, len(found)                                            # the walk sees the call sites at all
-    unknown = {n: at for n, at in found.items() if n not in prototypes()}
-    assert not unknown, f"named in the package but absent from PROTOTYPES: {unknown}"
+def entry_names_of(header):
+    return package_entry_names(registry()[header][1] + "[a-z0-9_]+", TABLE_NAME[header])
+
+
+@census
+def test_every_name_the_package_passes_is_a_prototype(header):
+    found, table = entry_names_of(header), prototypes(header)
+    assert len(found) >= (100 if header == "ecm_hip.h" else len(table)), len(found)  # the walk sees the call sites at all
+    unknown = {n: at for n, at in found.items() if n not in table}
+    assert not unknown, f"named in the package but absent from {TABLE_NAME[header]}: {unknown}"
+    if header != "ecm_hip.h":                                                       # the small tables: ops.py alone names them
+        assert all(a.startswith("ops.py:") for at in found.values() for a in at), found
 
 
 def test_no_entry_name_is_built_from_pieces():
@@ -318,13 +388,16 @@ def test_no_entry_name_is_built_from_pieces():
     assert not built, f"entry-point names built from pieces at {built}"
 
 
-def test_every_prototype_is_reached_or_accounted_for():
-    found, table = set(package_entry_names()), set(prototypes())
-    stale = sorted(set(ABI_ONLY) & found)
+@census
+def test_every_prototype_is_reached_or_accounted_for(header):
+    """Every row is named by the package or, in ecm_hip.h alone, accounted for in ABI_ONLY: the other tables have no such rows."""
+    found, table = set(entry_names_of(header)), set(prototypes(header))
+    abi_only = set(ABI_ONLY) if header == "ecm_hip.h" else set()
+    stale = sorted(abi_only & found)
     assert not stale, f"in ABI_ONLY although the package calls them: {stale}"
-    assert not set(ABI_ONLY) - table, sorted(set(ABI_ONLY) - table)
-    orphans = sorted(table - found - set(ABI_ONLY))
-    assert not orphans, f"in PROTOTYPES, called by nothing in the package and not in ABI_ONLY: {orphans}"
+    assert not abi_only - table, sorted(abi_only - table)
+    orphans = sorted(table - found - abi_only)
+    assert not orphans, f"in {TABLE_NAME[header]}, called by nothing in the package and not in ABI_ONLY: {orphans}"
     assert all(reason and caller for reason, caller in ABI_ONLY.values())
 
 

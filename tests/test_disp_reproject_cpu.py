@@ -1,14 +1,13 @@
 """Disparity reprojection, the part that needs no GPU: `reproject_t` and `cloud_t` below, fp64 torch
 restatements of the definition in include/ecm_geometry.h -- the reference of tests/test_hip_disp_reproject.py -- checked against
-closed forms and at the edges of the predicate; then the census of the second ABI table (_lib.GEOMETRY_PROTOTYPES against
-include/ecm_geometry.h, with the parser and the comparer of tests/test_abi_types.py) and the refusals of ops.q_matrix,
+closed forms and at the edges of the predicate; then the signatures of the second ABI table's entries (ENTRIES below; the census
+of _lib.GEOMETRY_PROTOTYPES against include/ecm_geometry.h is tests/test_abi_types.py's) and the refusals of ops.q_matrix,
 ops.disparity_reproject, ops.point_cloud and _ECMNet.point_cloud that come before any device work.
 
 Definition.  For pixel (x, y) of image b with disparity d: row r of Q_b [x y d 1]^T is ((Q[r][0] x + Q[r][1] y) + Q[r][2] d) + Q[r][3],
 every operation one fp64 operation; the point is (X/W, Y/W, Z/W), each rounded once to fp32.  Usable: d finite, valid != 0,
 min_disp < d <= max_disp in fp32, W finite and non-zero.  Unusable pixels are +0.0 in the dense planes; the cloud is the usable
 pixels in row-major order, image after image."""
-import ast
 import ctypes as C
 import inspect
 import os
@@ -17,10 +16,8 @@ import re
 import pytest
 import torch
 
-from conftest import ROOT
-from test_abi_types import PACKAGE, compare, parse_header
+from test_abi_types import PACKAGE, header_prototypes, lib_mod  # noqa: F401  (lib_mod: a fixture)
 
-HEADER = os.path.join(ROOT, "include", "ecm_geometry.h")
 ENTRIES = ("ecmg_point_cloud_fwd", "ecmg_point_cloud_scratch_bytes", "ecmg_point_cloud_tile", "ecmg_reproject_fwd")
 NAN, INF = float("nan"), float("inf")
 FLT_MAX = 3.4028234663852886e38
@@ -189,79 +186,16 @@ def test_well_conditioned_says_no():
     assert not well_conditioned(skew, 40, 60)
 
 
-# ---- the census of the second ABI table --------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def lib_mod():
-    import ecm_amd
-    if not os.path.exists(ecm_amd._lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return ecm_amd._lib
-
-
+# ---- the second ABI table: the census is tests/test_abi_types.py's, run over every table; what is this op's own stays here -----------
 def geometry_header():
-    with open(HEADER) as f:
-        return parse_header(f.read())
+    return header_prototypes("ecm_geometry.h")
 
 
-def test_geometry_prototypes_match_their_header_type_by_type(lib_mod):
+def test_geometry_prototypes_match_their_header_type_by_type():
     parsed = geometry_header()
-    assert sorted(parsed) == sorted(ENTRIES) == sorted(lib_mod.GEOMETRY_PROTOTYPES)
-    assert compare(parsed, lib_mod.GEOMETRY_PROTOTYPES) == []
-    assert all(lib_mod.GEOMETRY_PROTOTYPES[n] == parsed[n] for n in parsed)
-    assert not set(lib_mod.GEOMETRY_PROTOTYPES) & set(lib_mod.PROTOTYPES)
-    assert all(n.startswith("ecmg_") for n in parsed)
     _I, _LL, _F, _P = C.c_int, C.c_longlong, C.c_float, C.c_void_p
     assert parsed["ecmg_point_cloud_scratch_bytes"] == (_LL, [_I, _I, _I]) and parsed["ecmg_point_cloud_tile"] == (_I, [])
     assert parsed["ecmg_reproject_fwd"] == (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _F, _F, _P])
-
-
-def test_library_exports_every_geometry_symbol(lib_mod):
-    lib = C.CDLL(lib_mod.LIB_PATH)
-    assert [n for n in geometry_header() if not hasattr(lib, n)] == []
-    assert lib_mod.missing_symbols() == []
-    real = dict(lib_mod.GEOMETRY_PROTOTYPES)
-    try:                                                                                  # missing_symbols() covers the second table
-        lib_mod.GEOMETRY_PROTOTYPES["ecmg_not_there"] = (C.c_int, [])
-        assert lib_mod.missing_symbols() == ["ecmg_not_there"]
-    finally:
-        lib_mod.GEOMETRY_PROTOTYPES.clear()
-        lib_mod.GEOMETRY_PROTOTYPES.update(real)
-    loaded = lib_mod.load()
-    for name, (res, args) in lib_mod.GEOMETRY_PROTOTYPES.items():                          # load() typed them
-        assert getattr(loaded, name).restype is res and list(getattr(loaded, name).argtypes) == args, name
-
-
-def package_geometry_names():
-    """{name: ["file:line", ...]} of every whole string literal ecmg_* in the package's Python sources, walked as syntax trees
-    as tests/test_abi_types.py::package_entry_names does for ecm_*: the table itself, docstrings and f-strings are left out."""
-    found = {}
-    for fn in sorted(os.listdir(PACKAGE)):
-        if not fn.endswith(".py"):
-            continue
-        with open(os.path.join(PACKAGE, fn)) as f:
-            tree = ast.parse(f.read(), fn)
-        skip = set()
-        for node in ast.walk(tree):
-            if fn == "_lib.py" and isinstance(node, ast.Assign) and isinstance(node.targets[0], ast.Name) \
-                    and node.targets[0].id == "GEOMETRY_PROTOTYPES":
-                skip.update(id(n) for n in ast.walk(node))
-            if isinstance(node, ast.JoinedStr):
-                skip.update(id(n) for n in ast.walk(node))
-            if isinstance(node, (ast.Module, ast.ClassDef, ast.FunctionDef, ast.AsyncFunctionDef)) and node.body \
-                    and isinstance(node.body[0], ast.Expr) and isinstance(node.body[0].value, ast.Constant):
-                skip.add(id(node.body[0].value))
-        for node in ast.walk(tree):
-            if id(node) not in skip and isinstance(node, ast.Constant) and isinstance(node.value, str) \
-                    and re.fullmatch(r"ecmg_[a-z0-9_]+", node.value):
-                found.setdefault(node.value, []).append(f"{fn}:{node.lineno}")
-    return found
-
-
-def test_every_geometry_literal_is_in_the_table_and_vice_versa(lib_mod):
-    found = package_geometry_names()
-    assert sorted(found) == sorted(lib_mod.GEOMETRY_PROTOTYPES), found
-    assert all(at[0].startswith("ops.py:") for at in found.values())
 
 
 def test_null_pointers_are_rejected_without_touching_the_gpu(lib_mod):

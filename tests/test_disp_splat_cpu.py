@@ -19,6 +19,7 @@ import pytest
 import torch
 
 from conftest import ROOT
+from test_abi_types import declared
 from test_lr_check_cpu import lr_check_t
 
 NEW_ENTRIES = ("ecm_disp_splat_fwd", "ecm_disp_splat_max_width")
@@ -241,10 +242,8 @@ def lib_mod():
 
 
 def test_header_and_prototypes_hold_the_new_entries(lib_mod):
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ecm_hip.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(ecm_[a-z0-9_]+)\s*\(", src))
     for name in NEW_ENTRIES:
-        assert name in declared and name in lib_mod.PROTOTYPES, name
+        assert name in declared() and name in lib_mod.PROTOTYPES, name
         assert hasattr(lib_mod.load(), name), name
     assert lib_mod.missing_symbols() == []
     assert lib_mod.query("ecm_abi_version") >= 14

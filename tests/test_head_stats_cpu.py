@@ -9,14 +9,13 @@ softmax over the fused full-resolution logits.  eight: p is the mixture sum_n w9
 softmaxes of the neighbours ecm_aggregate9 does not skip, and std is in full-resolution pixels (s times the mixture's)."""
 import math
 import os
-import re
 
 import pytest
 import torch
 import torch.nn.functional as F
 
 import oracle.ecm_oracle as O
-from conftest import ROOT
+from test_abi_types import declared
 from oracle.weights import seeded
 from test_hip_variants_fullsize import soft_argmin_t, volume_mapping_t
 
@@ -147,10 +146,8 @@ def lib_mod():
 
 
 def test_header_and_prototypes_hold_the_new_entries(lib_mod):
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ecm_hip.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(ecm_[a-z0-9_]+)\s*\(", src))
     for name in NEW_ENTRIES:
-        assert name in declared and name in lib_mod.PROTOTYPES, name
+        assert name in declared() and name in lib_mod.PROTOTYPES, name
     assert lib_mod.missing_symbols() == []
     assert lib_mod.query("ecm_abi_version") >= 8
     # arguments of the parents plus the new buffers

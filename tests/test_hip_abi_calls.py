@@ -80,19 +80,25 @@ def check_arguments(name, args, argtypes, tensors, problems):
 
 
 @contextlib.contextmanager
-def recording(ecm, case):
+def recording(ecm, case, table=None):
     """Wrap _lib.call and _lib.query (and ops._p / ops._c, to know which addresses are tensors and which were promised
-    aligned) for the block; on exit every recorded call has been checked and the device has reported no asynchronous error."""
+    aligned) for the block; on exit every recorded call has been checked and the device has reported no asynchronous error.
+    table: the table of _lib.TABLES whose calls are recorded and checked (default PROTOTYPES); a name of another table passes
+    through, a name of none is a problem.  Only PROTOTYPES feeds this module's closing test (RECORDED, CASES, INT_MAX)."""
     lib, ops = ecm._lib, ecm.ops
+    table = lib.PROTOTYPES if table is None else table
+    own = table is lib.PROTOTYPES
     real_call, real_query, real_p, real_c = lib.call, lib.query, ops._p, ops._c
     calls, problems, tensors, aligned = [], [], {}, set()
 
     def record(name, args):
-        calls.append(name)
-        if name not in lib.PROTOTYPES:
-            problems.append(f"{name}: not in PROTOTYPES")
-        else:
-            check_arguments(name, args, lib.PROTOTYPES[name][1], tensors, problems)
+        if name in table:
+            calls.append(name)
+            check_arguments(name, args, table[name][1], tensors, problems)
+            if not own:
+                INT_MAX.pop(name, None)                            # the table of largest ints is about this module's cases
+        elif not any(name in t for t, _ in lib.TABLES.values()):
+            problems.append(f"{name}: in no table")
 
     def call(name, *args):
         record(name, args)
@@ -121,8 +127,9 @@ def recording(ecm, case):
         lib.call, lib.query, ops._p, ops._c = real_call, real_query, real_p, real_c
     assert calls, "nothing went through _lib.call"
     assert not problems, f"{len(problems)} bad arguments, the first 20:\n" + "\n".join(problems[:20])
-    RECORDED.update(calls)
-    CASES.add(case)
+    if own:
+        RECORDED.update(calls)
+        CASES.add(case)
 
 
 _models = {}

@@ -6,14 +6,12 @@ fp64 expression with a relative error of a few 2^-53, so the only way to another
 while nothing cancels in fp64, which `well_conditioned` asserts on every fixture matrix.  The shapes are the smallest at which a
 rank can go wrong: one pixel, a width that is no multiple of the wave, exactly one tile, one tile plus a pixel, several tiles per
 image with the last partial."""
-import contextlib
 import ctypes as C
 
 import pytest
 import torch
 
 from test_disp_reproject_cpu import cloud_t, reproject_t, well_conditioned
-from test_hip_abi_calls import check_arguments
 import test_hip_abi_calls as abi_calls
 
 pytestmark = pytest.mark.gpu
@@ -265,62 +263,18 @@ def test_runs_on_the_current_stream(ecm, TILE):
 
 
 # ---- what ops.py hands to the second table ----------------------------------------------------------------------------------------------
-@contextlib.contextmanager
-def recording_geometry(ecm):
-    """tests/test_hip_abi_calls.py::recording for _lib.GEOMETRY_PROTOTYPES: its check_arguments, which takes the argtypes as a
-    parameter, behind the same wrappers of _lib.call / _lib.query and ops._p / ops._c."""
-    lib, ops = ecm._lib, ecm.ops
-    real_call, real_query, real_p, real_c = lib.call, lib.query, ops._p, ops._c
-    calls, problems, tensors, aligned = [], [], {}, set()
-
-    def record(name, args):
-        if name in lib.GEOMETRY_PROTOTYPES:
-            calls.append(name)
-            check_arguments(name, args, lib.GEOMETRY_PROTOTYPES[name][1], tensors, problems)
-            abi_calls.INT_MAX.pop(name, None)                     # that module's table of largest ints is about its own cases
-        elif name not in lib.PROTOTYPES:
-            problems.append(f"{name}: in neither table")
-
-    def call(name, *args):
-        record(name, args)
-        return real_call(name, *args)
-
-    def query(name, *args):
-        record(name, args)
-        return real_query(name, *args)
-
-    def _c(t):
-        out = real_c(t)
-        aligned.add(out.data_ptr())
-        return out
-
-    def _p(t):
-        p = real_p(t)
-        if t is not None:
-            tensors[id(p)] = (p, t.data_ptr(), t.element_size(), t.is_contiguous(), t.is_cuda, t.data_ptr() in aligned)
-        return p
-
-    lib.call, lib.query, ops._p, ops._c = call, query, _p, _c
-    try:
-        yield calls, problems
-        ops.check_async_errors()
-    finally:
-        lib.call, lib.query, ops._p, ops._c = real_call, real_query, real_p, real_c
-
-
 def test_every_geometry_prototype_is_called_with_well_typed_arguments(ecm, TILE):
     B, H, W = shapes(TILE)["several_tiles"]
     d, Q = disparity(B, H, W, 31).to(DEV), matrices(ecm, B, H, W)
     valid = pattern("random0.9", B, H, W, TILE).to(DEV)
     colors = torch.rand(B, 3, H, W, device=DEV)
-    with recording_geometry(ecm) as (calls, problems):
+    with abi_calls.recording(ecm, "geometry", ecm._lib.GEOMETRY_PROTOTYPES) as calls:
         ecm.ops.point_cloud_tile()
         ecm.ops.disparity_reproject(d, Q, valid, with_mask=True)
         ecm.ops.disparity_reproject(d[:, :, 1:], Q[0].float())                            # a view: made contiguous and aligned
         ecm.ops.point_cloud(d, Q, colors, valid, min_disp=1, max_disp=None, with_dense=True)
         ecm.ops.point_cloud(d.unsqueeze(1), Q, None, None, max_disp=INF)                  # +inf reaches the library as the largest float
         ecm.ops.point_cloud(d, Q, colors.transpose(2, 3).contiguous().transpose(2, 3), valid.view(torch.uint8))
-    assert not problems, "\n".join(problems[:20])
     assert set(calls) == set(ecm._lib.GEOMETRY_PROTOTYPES), sorted(set(ecm._lib.GEOMETRY_PROTOTYPES) - set(calls))
     assert not set(abi_calls.INT_MAX) & set(ecm._lib.GEOMETRY_PROTOTYPES)
 

@@ -1,8 +1,8 @@
 """Stereo rectification, the part that needs no GPU: `rectify_map_t` and `remap_t` below, torch restatements
 of the definitions in include/ecm_rectify.h -- the references of tests/test_hip_rectify.py -- checked against closed forms and at
-the edges of the mask; ops.stereo_rectify's properties and its closed loop through the camera model; the census of the third ABI
-table (_lib.RECTIFY_PROTOTYPES against include/ecm_rectify.h, with the parser and the comparer of tests/test_abi_types.py); and
-the refusals that come before any device work.
+the edges of the mask; ops.stereo_rectify's properties and its closed loop through the camera model; the signatures of the third
+ABI table's entries (ENTRIES below; the census of _lib.RECTIFY_PROTOTYPES against include/ecm_rectify.h is
+tests/test_abi_types.py's); and the refusals that come before any device work.
 
 The map.  For output pixel (u, v): [X Y W] = iR [u v 1] with iR = (P[:, :3] R)^-1, x = X/W, y = Y/W, the rational radial and
 tangential distortion of (x, y), then mx = fx xd + cx, my = fy yd + cy: every operation one fp64 operation in the order the
@@ -10,20 +10,15 @@ header gives, the two results rounded once to fp32.
 The remap.  x0 = floor(mx), ax = mx - x0 (fp32, exact), likewise in y; the four taps as fp32, `border` outside the source;
 top = t00 + ax (t01 - t00), bot = t10 + ax (t11 - t10), s = top + ay (bot - top); out = (s / 255 - mean) / std; mask = finite and
 all four taps inside."""
-import ast
 import ctypes as C
 import inspect
 import math
-import os
-import re
 
 import pytest
 import torch
 
-from conftest import ROOT
-from test_abi_types import PACKAGE, compare, parse_header
+from test_abi_types import header_prototypes, lib_mod  # noqa: F401  (lib_mod: a fixture)
 
-HEADER = os.path.join(ROOT, "include", "ecm_rectify.h")
 ENTRIES = ("ecmr_rectify_map_fwd", "ecmr_rectify_map_params", "ecmr_remap_pair_fwd", "ecmr_tile_width")
 NAN, INF = float("nan"), float("inf")
 MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
@@ -315,84 +310,16 @@ def test_boundary_coordinates_land_on_the_documented_side():
                 assert abs(float(image[0, ch, 0, k]) * 255.0 - float(value(line[ch].tolist(), e))) < 1e-12, (k, ch)
 
 
-# ---- the third table --------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def lib_mod():
-    import ecm_amd
-    if not os.path.exists(ecm_amd._lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return ecm_amd._lib
-
-
+# ---- the third ABI table: the census is tests/test_abi_types.py's, run over every table; what is this op's own stays here -------------
 def rectify_header():
-    with open(HEADER) as f:
-        return parse_header(f.read())
+    return header_prototypes("ecm_rectify.h")
 
 
-def test_rectify_prototypes_match_their_header_type_by_type(lib_mod):
+def test_rectify_prototypes_match_their_header_type_by_type():
     parsed = rectify_header()
-    assert sorted(parsed) == sorted(ENTRIES) == sorted(lib_mod.RECTIFY_PROTOTYPES)
-    assert compare(parsed, lib_mod.RECTIFY_PROTOTYPES) == []
-    assert all(lib_mod.RECTIFY_PROTOTYPES[n] == parsed[n] for n in parsed)
-    tables = (lib_mod.PROTOTYPES, lib_mod.GEOMETRY_PROTOTYPES, lib_mod.RECTIFY_PROTOTYPES)
-    for i, a in enumerate(tables):                                                          # pairwise disjoint
-        for b in tables[i + 1:]:
-            assert not set(a) & set(b)
-    assert all(n.startswith("ecmr_") for n in parsed)
     _I, _F, _P = C.c_int, C.c_float, C.c_void_p
     assert parsed["ecmr_rectify_map_fwd"] == (_I, [_P, _P, _I, _I, _P]) and parsed["ecmr_tile_width"] == (_I, [])
     assert parsed["ecmr_remap_pair_fwd"] == (_I, [_P, _P, _I, _P, _P, _I] + [_P] * 5 + [_I] * 5 + [_P, _P, _F, _P])
-
-
-def test_library_exports_every_rectify_symbol(lib_mod):
-    lib = C.CDLL(lib_mod.LIB_PATH)
-    assert [n for n in rectify_header() if not hasattr(lib, n)] == []
-    assert lib_mod.missing_symbols() == []
-    real = dict(lib_mod.RECTIFY_PROTOTYPES)
-    try:                                                                                    # missing_symbols() covers the third table
-        lib_mod.RECTIFY_PROTOTYPES["ecmr_not_there"] = (C.c_int, [])
-        assert lib_mod.missing_symbols() == ["ecmr_not_there"]
-    finally:
-        lib_mod.RECTIFY_PROTOTYPES.clear()
-        lib_mod.RECTIFY_PROTOTYPES.update(real)
-    loaded = lib_mod.load()
-    for name, (res, args) in lib_mod.RECTIFY_PROTOTYPES.items():                            # load() typed them
-        assert getattr(loaded, name).restype is res and list(getattr(loaded, name).argtypes) == args, name
-    with pytest.raises(RuntimeError, match="does not export"):
-        lib_mod.call("ecmr_not_there")
-
-
-def package_rectify_names():
-    """{name: ["file:line", ...]} of every whole string literal ecmr_* in the package's Python sources, walked as syntax trees as
-    tests/test_abi_types.py::package_entry_names does for ecm_*: the table itself, docstrings and f-strings are left out."""
-    found = {}
-    for fn in sorted(os.listdir(PACKAGE)):
-        if not fn.endswith(".py"):
-            continue
-        with open(os.path.join(PACKAGE, fn)) as f:
-            tree = ast.parse(f.read(), fn)
-        skip = set()
-        for node in ast.walk(tree):
-            if fn == "_lib.py" and isinstance(node, ast.Assign) and isinstance(node.targets[0], ast.Name) \
-                    and node.targets[0].id == "RECTIFY_PROTOTYPES":
-                skip.update(id(n) for n in ast.walk(node))
-            if isinstance(node, ast.JoinedStr):
-                skip.update(id(n) for n in ast.walk(node))
-            if isinstance(node, (ast.Module, ast.ClassDef, ast.FunctionDef, ast.AsyncFunctionDef)) and node.body \
-                    and isinstance(node.body[0], ast.Expr) and isinstance(node.body[0].value, ast.Constant):
-                skip.add(id(node.body[0].value))
-        for node in ast.walk(tree):
-            if id(node) not in skip and isinstance(node, ast.Constant) and isinstance(node.value, str) \
-                    and re.fullmatch(r"ecmr_[a-z0-9_]+", node.value):
-                found.setdefault(node.value, []).append(f"{fn}:{node.lineno}")
-    return found
-
-
-def test_every_rectify_literal_is_in_the_table_and_vice_versa(lib_mod):
-    found = package_rectify_names()
-    assert sorted(found) == sorted(lib_mod.RECTIFY_PROTOTYPES), found
-    assert all(a.startswith("ops.py:") for at in found.values() for a in at)
 
 
 def test_queries_need_no_gpu(lib_mod):

@@ -23,6 +23,7 @@ import pytest
 import torch
 
 from conftest import ROOT
+from test_abi_types import declared
 
 NEW_ENTRIES = ("ecm_eval_sparsify", "ecm_eval_sparsify_scratch_bytes", "ecm_eval_sparsify_max_measures", "ecm_eval_sparsify_max_steps")
 NAN, INF = float("nan"), float("inf")
@@ -317,10 +318,8 @@ def lib_mod():
 
 
 def test_header_and_prototypes_hold_the_new_entries(lib_mod):
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ecm_hip.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(ecm_[a-z0-9_]+)\s*\(", src))
     for name in NEW_ENTRIES:
-        assert name in declared and name in lib_mod.PROTOTYPES, name
+        assert name in declared() and name in lib_mod.PROTOTYPES, name
         assert hasattr(lib_mod.load(), name), name
     assert lib_mod.missing_symbols() == []
     assert lib_mod.query("ecm_abi_version") >= 15

@@ -246,7 +246,8 @@ __global__ __launch_bounds__(256) void conv2d_c1_wgrad(const float* __restrict__
     }
 }
 
-// out[i] = sum_p partial[p][i] for i < n, fixed order: 4 waves take the rows p = wave, wave + 4, ..., then the waves in order
+// out[i] = sum_p partial[p][i] for i < n, fixed order: 4 waves take the rows p = wave, wave + 4, ..., then the waves in order.
+// Deliberately not ecm_sum_partials (partial_sum.h): another order of additions (other bits), and the bias is split off here.
 __global__ __launch_bounds__(256) void c1_reduce(const float* __restrict__ partial, float* __restrict__ gw,
                                                  float* __restrict__ gb, int n, int P) {
     __shared__ float sm[4][64];
@@ -314,7 +315,17 @@ inline bool c1_geom_ok(int B, int Ci, int H, int W) {
     return tiles <= 0x7fffffffLL && Ci <= 4096;
 }
 
-inline int c1_strips(int H) { return (H + C1_TY * C1_SUB - 1) / (C1_TY * C1_SUB); }
+// The weight gradient's launch plan, read by its scratch query and its launcher: one workgroup, and one partial of
+// n = Ci * 9 + 1 floats (the bias gradient last), per strip of C1_SUB tiles down the image.
+struct C1WgPlan { int tiles_x, strips_y, n; long long P; };
+inline C1WgPlan c1_wgrad_plan(int B, int Ci, int H, int W) {
+    C1WgPlan p;
+    p.tiles_x = (W + C1_TX - 1) / C1_TX;
+    p.strips_y = (H + C1_TY * C1_SUB - 1) / (C1_TY * C1_SUB);
+    p.P = (long long)B * p.strips_y * p.tiles_x;           // <= the tile count that c1_geom_ok bounds by 2^31
+    p.n = Ci * 9 + 1;
+    return p;
+}
 
 }  // namespace
 
@@ -338,19 +349,19 @@ extern "C" int ecm_conv2d_c1_dgrad(const float* gy, const float* y, const float*
 
 extern "C" long long ecm_conv2d_c1_wgrad_scratch_bytes(int B, int Ci, int H, int W) {
     if (!c1_geom_ok(B, Ci, H, W)) return 0;
-    return (long long)B * c1_strips(H) * ((W + C1_TX - 1) / C1_TX) * (Ci * 9 + 1) * (long long)sizeof(float);
+    const C1WgPlan p = c1_wgrad_plan(B, Ci, H, W);
+    return p.P * p.n * (long long)sizeof(float);
 }
 
 extern "C" int ecm_conv2d_c1_wgrad(const float* x, const float* gy, const float* y, float* gw, float* gb, void* scratch,
                                    long long scratch_bytes, int B, int Ci, int H, int W, void* stream) {
     ECM_CHECK_ARG(x && gy && y && gw && gb && scratch && c1_geom_ok(B, Ci, H, W));
-    if (scratch_bytes < ecm_conv2d_c1_wgrad_scratch_bytes(B, Ci, H, W)) return ECM_ESCRATCH;
+    const C1WgPlan p = c1_wgrad_plan(B, Ci, H, W);
+    if (scratch_bytes < p.P * p.n * (long long)sizeof(float)) return ECM_ESCRATCH;
     hipStream_t st = ecm_stream(stream);
-    const int tx = (W + C1_TX - 1) / C1_TX, sy = c1_strips(H);
-    const int P = B * sy * tx, n = Ci * 9 + 1;
     float* partial = static_cast<float*>(scratch);
-    hipLaunchKernelGGL(conv2d_c1_wgrad, dim3((unsigned)P), dim3(256), 0, st, x, gy, y, partial, Ci, H, W, tx, sy);
-    hipLaunchKernelGGL(c1_reduce, dim3((n + 63) / 64), dim3(256), 0, st, partial, gw, gb, n, P);
+    hipLaunchKernelGGL(conv2d_c1_wgrad, dim3((unsigned)p.P), dim3(256), 0, st, x, gy, y, partial, Ci, H, W, p.tiles_x, p.strips_y);
+    hipLaunchKernelGGL(c1_reduce, dim3((p.n + 63) / 64), dim3(256), 0, st, partial, gw, gb, p.n, (int)p.P);
     return ECM_LAUNCH_RESULT();
 }
 

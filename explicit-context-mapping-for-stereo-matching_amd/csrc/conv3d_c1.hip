@@ -9,6 +9,8 @@
 // Both are then bound by reading x once (212 MB at 576x960) instead of by ~92 GFLOP of padded MFMA work.
 #include "common.h"
 #include "bf16.h"
+#include "fp32_conv_stage.h"      // stage_launch
+#include "partial_sum.h"
 #include <cstdlib>
 
 namespace {
@@ -503,38 +505,16 @@ __global__ __launch_bounds__(256) void conv3d_c1_wgrad(const float* __restrict__
     }
 }
 
-// gw[i] = sum_p partial[p][i] in a fixed order: 32 outputs per workgroup, 8 lane groups each sum every 8th partial
-// (same scheme as wgrad_reduce in conv3d_wgrad.hip; one thread per output walking 512 partials took ~0.1 ms).
-__global__ __launch_bounds__(256) void c1_wgrad_reduce(const float* __restrict__ partial, float* __restrict__ gw, int n, int P) {
-    __shared__ float sm[8][32];
-    const int o = threadIdx.x & 31, grp = threadIdx.x >> 5;
-    const int i = blockIdx.x * 32 + o;
-    float s = 0.f;
-    if (i < n) {
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        int p = grp;
-        for (; p + 24 < P; p += 32) {
-            s0 += partial[(size_t)p * n + i];
-            s1 += partial[(size_t)(p + 8) * n + i];
-            s2 += partial[(size_t)(p + 16) * n + i];
-            s3 += partial[(size_t)(p + 24) * n + i];
-        }
-        for (; p < P; p += 8) s0 += partial[(size_t)p * n + i];
-        s = (s0 + s1) + (s2 + s3);
-    }
-    sm[grp][o] = s;
-    __syncthreads();
-    if (grp == 0 && i < n) {
-        float t = 0.f;
-#pragma unroll
-        for (int g = 0; g < 8; ++g) t += sm[g][o];
-        gw[i] = t;
-    }
-}
-
-inline int c1_workers(long long ntiles) { return (int)(ntiles < 512 ? ntiles : 512); }
-inline long long c1_tiles(int B, int D, int H, int W) {
-    return (long long)B * ((D + GTD - 1) / GTD) * ((H + GTH - 1) / GTH) * ((W + GTW - 1) / GTW);
+// The weight gradient's launch plan, read by its scratch query and its launcher: up to 512 persistent workgroups (two per CU)
+// walk the tiles and leave one partial [Ci][27] each; ecm_sum_partials (partial_sum.h) adds them in a fixed order.
+struct C1WgPlan { int tiles_d, tiles_h, tiles_w, P; long long ntiles, n; };
+inline C1WgPlan c1_wgrad_plan(int B, int Ci, int D, int H, int W) {
+    C1WgPlan p;
+    p.tiles_d = (D + GTD - 1) / GTD; p.tiles_h = (H + GTH - 1) / GTH; p.tiles_w = (W + GTW - 1) / GTW;
+    p.ntiles = (long long)B * p.tiles_d * p.tiles_h * p.tiles_w;
+    p.P = (int)(p.ntiles < 512 ? p.ntiles : 512);
+    p.n = (long long)Ci * 27;
+    return p;
 }
 
 }  // namespace
@@ -604,27 +584,24 @@ extern "C" int ecm_conv3d_c1_dgrad(const float* gy, const float* w, float* gx, i
 
 extern "C" long long ecm_conv3d_c1_wgrad_scratch_bytes(int B, int Ci, int D, int H, int W) {
     if (B <= 0 || Ci <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
-    return (long long)c1_workers(c1_tiles(B, D, H, W)) * Ci * 27 * (long long)sizeof(float);
+    const C1WgPlan p = c1_wgrad_plan(B, Ci, D, H, W);
+    return p.P * p.n * (long long)sizeof(float);
 }
 
 namespace {
 template <bool GN>
 int launch_c1_wgrad(const float* x, const float* gy, float* gw, void* scratch, long long scratch_bytes, int B, int Ci, int D, int H,
                     int W, const float* mean_rstd, const float* gamma, const float* beta, void* stream) {
-    if (Ci > 32 || (long long)D * H * W * 4 * 32 >= 0x7fffffffLL || c1_tiles(B, D, H, W) >= 0x7fffffffLL) return ECM_EUNSUP;
-    if (scratch_bytes < ecm_conv3d_c1_wgrad_scratch_bytes(B, Ci, D, H, W)) return ECM_ESCRATCH;
-    const int tiles_d = (D + GTD - 1) / GTD, tiles_h = (H + GTH - 1) / GTH, tiles_w = (W + GTW - 1) / GTW;
-    const int P = c1_workers(c1_tiles(B, D, H, W));
+    const C1WgPlan p = c1_wgrad_plan(B, Ci, D, H, W);
+    if (Ci > 32 || (long long)D * H * W * 4 * 32 >= 0x7fffffffLL || p.ntiles >= 0x7fffffffLL) return ECM_EUNSUP;
+    if (scratch_bytes < p.P * p.n * (long long)sizeof(float)) return ECM_ESCRATCH;
     hipStream_t st = ecm_stream(stream);
-    {
-        const hipError_t e = ecm_allow_lds(reinterpret_cast<const void*>(conv3d_c1_wgrad<GN>), G_LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-    }
     float* partial = static_cast<float*>(scratch);
-    hipLaunchKernelGGL(conv3d_c1_wgrad<GN>, dim3(P), dim3(256), G_LDS_BYTES, st, x, gy, partial, B, Ci, D, H, W, tiles_d, tiles_h,
-                       tiles_w, mean_rstd, gamma, beta);
-    const int n = Ci * 27;
-    hipLaunchKernelGGL(c1_wgrad_reduce, dim3((n + 31) / 32), dim3(256), 0, st, partial, gw, n, P);
+    const int rc = stage_launch(conv3d_c1_wgrad<GN>, p.P, 1, 256, G_LDS_BYTES, (long long)D * H * W, st, x, gy, partial, B, Ci, D, H, W,
+                                p.tiles_d, p.tiles_h, p.tiles_w, mean_rstd, gamma, beta);
+    if (rc != 0) return rc;
+    const int n = (int)p.n;
+    hipLaunchKernelGGL(ecm_sum_partials<>, dim3((n + 31) / 32), dim3(256), 0, st, partial, gw, n, p.P);
     return ECM_LAUNCH_RESULT();
 }
 }  // namespace

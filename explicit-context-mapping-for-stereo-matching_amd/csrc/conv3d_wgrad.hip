@@ -11,6 +11,8 @@
 // registers: 27 taps x 16 regs split over the 4 waves), write one partial [Co][Ci][27] each, and a
 // second kernel sums the partials in a fixed order (deterministic, no float atomics).
 #include "common.h"
+#include "fp32_conv_stage.h"      // stage_launch
+#include "partial_sum.h"
 
 #ifdef WG_PROFILE
 __device__ unsigned long long wg_prof[4 * 8];     // [wave][phase] cycles of workgroup (0,0); debugging aid only
@@ -30,9 +32,15 @@ constexpr int TWV = 16;       // output voxels per tile row
 // (the encoder's convbn, cmfsm.py:37-47) -- same staging, 9 taps.
 // KH x KW taps with dilation DIL in the plane (KD = 1 only: the encoder's dilated / strided / 1x1 layers and the sheared
 // 3x5 class convolution of the collapsed cost volume, conv2d.hip); the 3-D layers are always 3x3x3, dilation 1.
-template <int STRIDE, int TD, int TH, int KD, int KH = 3, int KW = 3, int DIL = 1>
+// TD x TH x TWV output voxels per tile.  This struct is the ONE statement of a kernel's tile shape, tap count, partials per
+// worker and occupancy: the kernel, its launcher and its scratch query (through plan<Cfg>) all read it.
+template <int STRIDE, int TD_, int TH_, int KD_, int KH_ = 3, int KW_ = 3, int DIL_ = 1>
 struct WgCfg {
+    static constexpr int S = STRIDE, TD = TD_, TH = TH_, KD = KD_, KH = KH_, KW = KW_, DIL = DIL_;
     static_assert(KD == 1 || (KH == 3 && KW == 3 && DIL == 1), "3-D layers are 3x3x3, dilation 1");
+    // persistent workgroups per CU (3-D: the 27 x 16 accumulator registers leave room for one): the kernel's __launch_bounds__
+    // and the worker count of plan() are this one number
+    static constexpr int OCC = KD == 3 ? 1 : 2;
     static constexpr int NTAPS = KH * KW * KD, PADD = KD / 2;
     // wave plan: 27 taps -> 4 tap groups of 7 (the last has 6), every wave runs all k-steps;
     //            15 taps -> 4 tap groups of 4 (the last has 3);  9 taps -> 2 tap groups (5 + 4) x 2 halves of the k-steps
@@ -191,8 +199,8 @@ __device__ __forceinline__ void wg_tile_wino(const float* __restrict__ gaw, cons
 }
 
 template <int STRIDE, int TD, int TH, int KD, int KH = 3, int KW = 3, int DIL = 1, bool WINO = false>
-__global__ __launch_bounds__(256, KD == 3 ? 1 : 2) void conv3d_wgrad_mfma(const float* __restrict__ x, const float* __restrict__ gy,
-                                                         float* __restrict__ partial, int B, int Ci, int Co, int D,
+__global__ __launch_bounds__(256, (WgCfg<STRIDE, TD, TH, KD, KH, KW, DIL>::OCC)) void conv3d_wgrad_mfma(
+                                                         const float* __restrict__ x, const float* __restrict__ gy, float* __restrict__ partial, int B, int Ci, int Co, int D,
                                                          int H, int W, int Do, int Ho, int Wo, int tiles_d, int tiles_h,
                                                          int tiles_w, int ci_tiles, int pad_top, int pad_left) {
     using Cfg = WgCfg<STRIDE, TD, TH, KD, KH, KW, DIL>;
@@ -373,36 +381,6 @@ __global__ __launch_bounds__(256, KD == 3 ? 1 : 2) void conv3d_wgrad_mfma(const 
     }
 }
 
-// gw[i] = sum_p partial[p][i] in a FIXED order (deterministic): a workgroup owns 32 outputs, its 8 lane groups each sum
-// every 8th partial, and the 8 group sums are added in order.  (One thread per output walking all P partials was
-// latency-bound: up to 1024 partials x few thousand outputs for the 2-D layers.)
-__global__ __launch_bounds__(256) void wgrad_reduce(const float* __restrict__ partial, float* __restrict__ gw, int n, int P) {
-    __shared__ float sm[8][32];
-    const int o = threadIdx.x & 31, grp = threadIdx.x >> 5;
-    const int i = blockIdx.x * 32 + o;
-    float s = 0.f;
-    if (i < n) {
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        int p = grp;
-        for (; p + 24 < P; p += 32) {
-            s0 += partial[(size_t)p * n + i];
-            s1 += partial[(size_t)(p + 8) * n + i];
-            s2 += partial[(size_t)(p + 16) * n + i];
-            s3 += partial[(size_t)(p + 24) * n + i];
-        }
-        for (; p < P; p += 8) s0 += partial[(size_t)p * n + i];
-        s = (s0 + s1) + (s2 + s3);
-    }
-    sm[grp][o] = s;
-    __syncthreads();
-    if (grp == 0 && i < n) {
-        float t = 0.f;
-#pragma unroll
-        for (int g = 0; g < 8; ++g) t += sm[g][o];
-        gw[i] = t;
-    }
-}
-
 // gU [16][KD][Co][Ci] (summed partials, Winograd domain) -> gw [Co][Ci][KD][3][3] = G^T gU G,
 // G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]]
 __global__ void wgrad_wino_finish(const float* __restrict__ gU, float* __restrict__ gw, int Co, int Ci, int KD) {
@@ -430,76 +408,114 @@ __global__ void wgrad_wino_finish(const float* __restrict__ gU, float* __restric
     }
 }
 
-inline int wgrad_workers(int Ci, int Co, long long ntiles, int occ = 1) {
-    const int ytiles = ((Ci + CT - 1) / CT) * ((Co + CT - 1) / CT);
-    long long p = 256 * occ / ytiles;           // `occ` persistent workgroups per CU in total (3-D: 1, 2-D: 2)
-    if (p < 1) p = 1;
-    if (p > ntiles) p = ntiles;
-    return (int)p;
+// ---- the launch plan: what the scratch query promises and what the launcher does, computed in one place (host only, no GPU
+// state: the queries answer on a machine without one) ---------------------------------------------------------------------------
+// The general 2-D query has always promised room for this many partials per worker, whatever the row's KG is; callers cache
+// by its answer, so the bound stays and the launcher checks that no 2-D kernel writes more.
+constexpr int WG2_MAX_KG = 4;
+
+struct WgPlan {
+    int Do, Ho, Wo;                          // output extents
+    int tiles_d, tiles_h, tiles_w, ci_tiles, co_tiles;
+    long long ntiles;                        // B * tiles_d * tiles_h * tiles_w (the entry points refuse >= 2^31)
+    int P;                                   // persistent workers: grid.x
+    long long partials, n, scratch_floats;   // partials written (of n floats each); n outputs the reduction produces
+};
+
+inline int wg_out(int n, int stride) { return (n - 1) / stride + 1; }
+
+// WINO: the Winograd form of Cfg (stride 1): one partial per worker in the 16-frequency domain, plus the summed gU behind them
+template <class Cfg, bool WINO = false>
+WgPlan plan(int B, int Ci, int Co, int Do, int Ho, int Wo) {
+    WgPlan p;
+    p.Do = Do; p.Ho = Ho; p.Wo = Wo;
+    p.tiles_d = (Do + Cfg::TD - 1) / Cfg::TD; p.tiles_h = (Ho + Cfg::TH - 1) / Cfg::TH; p.tiles_w = (Wo + TWV - 1) / TWV;
+    p.ntiles = (long long)B * p.tiles_d * p.tiles_h * p.tiles_w;
+    p.ci_tiles = (Ci + CT - 1) / CT; p.co_tiles = (Co + CT - 1) / CT;
+    long long workers = 256 * Cfg::OCC / (p.ci_tiles * p.co_tiles);     // OCC persistent workgroups per CU in total
+    if (workers < 1) workers = 1;
+    if (workers > p.ntiles) workers = p.ntiles;
+    p.P = (int)workers;
+    p.partials = WINO ? p.P : (long long)p.P * Cfg::KG;
+    p.n = (WINO ? 16LL * Cfg::KD : (long long)Cfg::NTAPS) * Co * Ci;
+    p.scratch_floats = WINO ? (p.P + 1LL) * p.n : Cfg::KD == 3 ? p.partials * p.n : (long long)p.P * WG2_MAX_KG * p.n;
+    return p;
 }
 
-template <int STRIDE, int TD, int TH, int KD, int KH = 3, int KW = 3, int DIL = 1>
-int launch_wgrad(const float* x, const float* gy, float* gw, float* partial, int B, int Ci, int Co, int D, int H, int W,
-                 hipStream_t st, int Ho = 0, int Wo = 0, int pad_top = 1, int pad_left = 1) {
-    using Cfg = WgCfg<STRIDE, TD, TH, KD, KH, KW, DIL>;
-    const int Do = (D - 1) / STRIDE + 1;
-    if (Ho <= 0) Ho = (H - 1) / STRIDE + 1;
-    if (Wo <= 0) Wo = (W - 1) / STRIDE + 1;
-    const int tiles_d = (Do + TD - 1) / TD, tiles_h = (Ho + TH - 1) / TH, tiles_w = (Wo + TWV - 1) / TWV;
-    const long long ntiles = (long long)B * tiles_d * tiles_h * tiles_w;
-    const int ci_tiles = (Ci + CT - 1) / CT, co_tiles = (Co + CT - 1) / CT;
-    const int P = wgrad_workers(Ci, Co, ntiles, KD == 3 ? 1 : 2);
-    auto kern = conv3d_wgrad_mfma<STRIDE, TD, TH, KD, KH, KW, DIL>;
-    {
-        const hipError_t e = ecm_allow_lds(reinterpret_cast<const void*>(kern), Cfg::LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(kern, dim3(P, ci_tiles * co_tiles), dim3(256), Cfg::LDS_BYTES, st, x, gy, partial, B, Ci, Co, D, H,
-                       W, Do, Ho, Wo, tiles_d, tiles_h, tiles_w, ci_tiles, pad_top, pad_left);
-    const int n = Co * Ci * Cfg::NTAPS;
-    hipLaunchKernelGGL(wgrad_reduce, dim3((n + 31) / 32), dim3(256), 0, st, partial, gw, n, P * Cfg::KG);
+// A runtime layer as its compile-time WgCfg, in the style of ecm_dispatch: f(Cfg{}) for the first Cfg of the list that `match`
+// accepts, and f's own status; ECM_EUNSUP, with f not called, when none does.  One list per family:
+template <class... Cfgs, class M, class F>
+int wg_select(M&& match, F&& f) {
+    int rc = ECM_EUNSUP;
+    (void)((match(Cfgs{}) && ((rc = f(Cfgs{})), true)) || ...);
+    return rc;
+}
+template <class F>      // direct 3-D, by stride
+int wg3_select(int stride, F&& f) {
+    return wg_select<WgCfg<1, 2, 8, 3>, WgCfg<2, 1, 4, 3>>([&](auto c) { return decltype(c)::S == stride; }, f);
+}
+template <class F>      // Winograd (stride 1), by depth taps: 3x3x3 | 3x3 on D independent planes
+int wgw_select(int kd, F&& f) {
+    return wg_select<WgCfg<1, 2, 8, 3>, WgCfg<1, 1, 16, 1>>([&](auto c) { return decltype(c)::KD == kd; }, f);
+}
+template <int KH, int KW, int S, int DL, int TH> using Wg2 = WgCfg<S, 1, TH, 1, KH, KW, DL>;
+template <class F>      // general 2-D, by (kh, kw, stride, dil); dil < 0: the row at any dilation (nothing in plan() depends on it)
+int wg2_select(int kh, int kw, int stride, int dil, F&& f) {
+    return wg_select<Wg2<3, 3, 1, 1, 16>, Wg2<3, 3, 1, 2, 16>, Wg2<3, 3, 1, 4, 16>, Wg2<3, 3, 2, 1, 8>, Wg2<3, 5, 1, 1, 16>,
+                     Wg2<1, 1, 1, 1, 16>, Wg2<1, 1, 2, 1, 8>>(
+        [&](auto c) {
+            using Cfg = decltype(c);
+            return Cfg::KH == kh && Cfg::KW == kw && Cfg::S == stride && (dil < 0 || Cfg::DIL == dil);
+        }, f);
+}
+
+template <class Cfg>
+int launch_wgrad(const float* x, const float* gy, float* gw, float* partial, const WgPlan& p, int B, int Ci, int Co, int D, int H,
+                 int W, hipStream_t st, int pad_top = 1, int pad_left = 1) {
+    static_assert(Cfg::KD == 3 || Cfg::KG <= WG2_MAX_KG, "the 2-D scratch query sizes WG2_MAX_KG partials per worker");
+    // (stage_launch's own extent guards cannot bind: the entry points have refused such volumes already)
+    const int rc = stage_launch(conv3d_wgrad_mfma<Cfg::S, Cfg::TD, Cfg::TH, Cfg::KD, Cfg::KH, Cfg::KW, Cfg::DIL>, p.P,
+                                p.ci_tiles * p.co_tiles, 256, Cfg::LDS_BYTES, (long long)D * H * W, st, x, gy, partial, B, Ci, Co, D,
+                                H, W, p.Do, p.Ho, p.Wo, p.tiles_d, p.tiles_h, p.tiles_w, p.ci_tiles, pad_top, pad_left);
+    if (rc != 0) return rc;
+    const int n = (int)p.n;
+    hipLaunchKernelGGL(ecm_sum_partials<>, dim3((n + 31) / 32), dim3(256), 0, st, partial, gw, n, (int)p.partials);
     return ECM_LAUNCH_RESULT();
 }
 
-template <int TD, int TH, int KD>
-int launch_wgrad_wino(const float* x, const float* gy, float* gw, float* scratch, int B, int Ci, int Co, int D, int H, int W,
-                      hipStream_t st) {
-    using Cfg = WgCfg<1, TD, TH, KD>;
-    const int tiles_d = (D + TD - 1) / TD, tiles_h = (H + TH - 1) / TH, tiles_w = (W + TWV - 1) / TWV;
-    const long long ntiles = (long long)B * tiles_d * tiles_h * tiles_w;
-    const int ci_tiles = (Ci + CT - 1) / CT, co_tiles = (Co + CT - 1) / CT;
-    const int P = wgrad_workers(Ci, Co, ntiles, KD == 3 ? 1 : 2);
-    auto kern = conv3d_wgrad_mfma<1, TD, TH, KD, 3, 3, 1, true>;
-    {
-        const hipError_t e = ecm_allow_lds(reinterpret_cast<const void*>(kern), Cfg::LDS_BYTES);
-        if (e != hipSuccess) return (int)e;
-    }
-    const int n = 16 * KD * Co * Ci;
-    float* partial = scratch;
-    float* gU = scratch + (size_t)P * n;
-    hipLaunchKernelGGL(kern, dim3(P, ci_tiles * co_tiles), dim3(256), Cfg::LDS_BYTES, st, x, gy, partial, B, Ci, Co, D, H,
-                       W, D, H, W, tiles_d, tiles_h, tiles_w, ci_tiles, 1, 1);
-    hipLaunchKernelGGL(wgrad_reduce, dim3((n + 31) / 32), dim3(256), 0, st, partial, gU, n, P);
-    hipLaunchKernelGGL(wgrad_wino_finish, dim3((Co * Ci * KD + 255) / 256), dim3(256), 0, st, gU, gw, Co, Ci, KD);
+template <class Cfg>
+int launch_wgrad_wino(const float* x, const float* gy, float* gw, float* scratch, const WgPlan& p, int B, int Ci, int Co, int D,
+                      int H, int W, hipStream_t st) {
+    const int n = (int)p.n;
+    float* partial = scratch;                            // [P][n], then gU [n]: the (P + 1) * n floats of the plan
+    float* gU = scratch + (size_t)p.P * n;
+    const int rc = stage_launch(conv3d_wgrad_mfma<1, Cfg::TD, Cfg::TH, Cfg::KD, 3, 3, 1, true>, p.P, p.ci_tiles * p.co_tiles, 256,
+                                Cfg::LDS_BYTES, (long long)D * H * W, st, x, gy, partial, B, Ci, Co, D, H, W, D, H, W, p.tiles_d,
+                                p.tiles_h, p.tiles_w, p.ci_tiles, 1, 1);
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(ecm_sum_partials<>, dim3((n + 31) / 32), dim3(256), 0, st, partial, gU, n, (int)p.partials);
+    hipLaunchKernelGGL(wgrad_wino_finish, dim3((Co * Ci * Cfg::KD + 255) / 256), dim3(256), 0, st, gU, gw, Co, Ci, Cfg::KD);
     return ECM_LAUNCH_RESULT();
 }
 
-inline long long ntiles_wino(int B, int D, int H, int W, int kd) {
-    const int TD = kd == 3 ? 2 : 1, TH = kd == 3 ? 8 : 16;
-    return (long long)B * ((D + TD - 1) / TD) * ((H + TH - 1) / TH) * ((W + TWV - 1) / TWV);
-}
-
-inline long long ntiles_for(int B, int D, int H, int W, int stride) {
-    const int Do = (D - 1) / stride + 1, Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
-    const int TD = stride == 1 ? 2 : 1, TH = stride == 1 ? 8 : 4;
-    return (long long)B * ((Do + TD - 1) / TD) * ((Ho + TH - 1) / TH) * ((Wo + TWV - 1) / TWV);
+// The plan the general 2-D query reads: the row of (kh, kw, stride).  Outside the table there is no kernel (the entry point
+// answers ECM_EUNSUP), but the query has always answered there too, with the tile of the stride -- which every row of a stride
+// shares -- and the caller's own kh * kw taps; that number stays: such rows borrow the 3x3 row of their stride, and any stride
+// but 1 counts as 2.
+inline WgPlan wg2_query_plan(int B, int Ci, int Co, int Ho, int Wo, int kh, int kw, int stride) {
+    WgPlan p{};
+    auto take = [&](auto c) { p = plan<decltype(c)>(B, Ci, Co, 1, Ho, Wo); return 0; };
+    if (wg2_select(kh, kw, stride, -1, take) != 0) wg2_select(3, 3, stride == 1 ? 1 : 2, -1, take);
+    return p;
 }
 
 }  // namespace
 
 extern "C" long long ecm_conv3d_wgrad_scratch_bytes(int B, int Ci, int Co, int D, int H, int W, int stride) {
     if (B <= 0 || Ci <= 0 || Co <= 0 || D <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return 0;
-    return (long long)wgrad_workers(Ci, Co, ntiles_for(B, D, H, W, stride)) * Co * Ci * 27 * (long long)sizeof(float);
+    WgPlan p{};
+    wg3_select(stride, [&](auto c) { p = plan<decltype(c)>(B, Ci, Co, wg_out(D, stride), wg_out(H, stride), wg_out(W, stride)); return 0; });
+    return p.scratch_floats * (long long)sizeof(float);
 }
 
 extern "C" int ecm_conv3d_k3_wgrad(const float* x, const float* gy, float* gw, void* scratch, long long scratch_bytes,
@@ -507,26 +523,20 @@ extern "C" int ecm_conv3d_k3_wgrad(const float* x, const float* gy, float* gw, v
     ECM_CHECK_ARG(x && gy && gw && scratch && B > 0 && Ci > 0 && Co > 0 && D > 0 && H > 0 && W > 0);
     if (stride != 1 && stride != 2) return ECM_EUNSUP;
     if ((long long)D * H * W * 4 * 32 >= 0x7fffffffLL) return ECM_EUNSUP;  // 32-bit buffer offsets over a 32-channel tile
-    if (ntiles_for(B, D, H, W, stride) >= 0x7fffffffLL) return ECM_EUNSUP;   // 32-bit tile counter
-    if (scratch_bytes < ecm_conv3d_wgrad_scratch_bytes(B, Ci, Co, D, H, W, stride)) return ECM_ESCRATCH;
-    float* partial = static_cast<float*>(scratch);
-    hipStream_t st = ecm_stream(stream);
-    if (stride == 1) return launch_wgrad<1, 2, 8, 3>(x, gy, gw, partial, B, Ci, Co, D, H, W, st);
-    return launch_wgrad<2, 1, 4, 3>(x, gy, gw, partial, B, Ci, Co, D, H, W, st);
+    return wg3_select(stride, [&](auto c) {
+        using Cfg = decltype(c);
+        const WgPlan p = plan<Cfg>(B, Ci, Co, wg_out(D, stride), wg_out(H, stride), wg_out(W, stride));
+        if (p.ntiles >= 0x7fffffffLL) return (int)ECM_EUNSUP;                // 32-bit tile counter
+        if (scratch_bytes < p.scratch_floats * (long long)sizeof(float)) return (int)ECM_ESCRATCH;
+        return launch_wgrad<Cfg>(x, gy, gw, static_cast<float*>(scratch), p, B, Ci, Co, D, H, W, ecm_stream(stream));
+    });
 }
 
 // ---- general 2-D weight gradient: KH x KW in {3x3, 3x5, 1x1}, stride 1|2, dilation 1|2|4, explicit padding / output size
-namespace {
-inline long long ntiles2d_ex(int B, int Ho, int Wo, int stride) {
-    const int th = stride == 1 ? 16 : 8;
-    return (long long)B * ((Ho + th - 1) / th) * ((Wo + TWV - 1) / TWV);
-}
-}  // namespace
-
 extern "C" long long ecm_conv2d_wgrad_ex_scratch_bytes(int B, int Ci, int Co, int Ho, int Wo, int kh, int kw, int stride) {
     if (B <= 0 || Ci <= 0 || Co <= 0 || Ho <= 0 || Wo <= 0 || kh <= 0 || kw <= 0) return 0;
-    // every worker writes KG <= 4 partials of [Co][Ci][taps]
-    return (long long)wgrad_workers(Ci, Co, ntiles2d_ex(B, Ho, Wo, stride), 2) * 4 * Co * Ci * kh * kw * (long long)sizeof(float);
+    // == plan().scratch_floats for a row of the table; stated with kh * kw so that it also holds outside it
+    return (long long)wg2_query_plan(B, Ci, Co, Ho, Wo, kh, kw, stride).P * WG2_MAX_KG * Co * Ci * kh * kw * (long long)sizeof(float);
 }
 
 extern "C" int ecm_conv2d_wgrad_ex(const float* x, const float* gy, float* gw, void* scratch, long long scratch_bytes, int B,
@@ -534,37 +544,33 @@ extern "C" int ecm_conv2d_wgrad_ex(const float* x, const float* gy, float* gw, v
                                    int pad_left, int Ho, int Wo, void* stream) {
     ECM_CHECK_ARG(x && gy && gw && scratch && B > 0 && Ci > 0 && Co > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0);
     if ((long long)H * W * 4 * 32 >= 0x7fffffffLL || (long long)Ho * Wo * 4 * 32 >= 0x7fffffffLL) return ECM_EUNSUP;
-    if (ntiles2d_ex(B, Ho, Wo, stride) >= 0x7fffffffLL) return ECM_EUNSUP;
+    if (wg2_query_plan(B, Ci, Co, Ho, Wo, kh, kw, stride).ntiles >= 0x7fffffffLL) return ECM_EUNSUP;
     if (scratch_bytes < ecm_conv2d_wgrad_ex_scratch_bytes(B, Ci, Co, Ho, Wo, kh, kw, stride)) return ECM_ESCRATCH;
-    float* partial = static_cast<float*>(scratch);
-    hipStream_t st = ecm_stream(stream);
-#define WG2(KH, KW, S, DL, TH) if (kh == KH && kw == KW && stride == S && dil == DL) \
-        return launch_wgrad<S, 1, TH, 1, KH, KW, DL>(x, gy, gw, partial, B, Ci, Co, 1, H, W, st, Ho, Wo, pad_top, pad_left)
-    WG2(3, 3, 1, 1, 16);
-    WG2(3, 3, 1, 2, 16);
-    WG2(3, 3, 1, 4, 16);
-    WG2(3, 3, 2, 1, 8);
-    WG2(3, 5, 1, 1, 16);
-    WG2(1, 1, 1, 1, 16);
-    WG2(1, 1, 2, 1, 8);
-#undef WG2
-    return ECM_EUNSUP;
+    return wg2_select(kh, kw, stride, dil, [&](auto c) {
+        using Cfg = decltype(c);
+        return launch_wgrad<Cfg>(x, gy, gw, static_cast<float*>(scratch), plan<Cfg>(B, Ci, Co, 1, Ho, Wo), B, Ci, Co, 1, H, W,
+                                 ecm_stream(stream), pad_top, pad_left);
+    });
 }
 
 // ---- Winograd F(2x2,3x3) weight gradient of the stride-1 3x3x3 Conv3d (kd = 3) / 3x3 Conv2d (kd = 1, D = 1) ------------------
 extern "C" long long ecm_conv_wino_wgrad_scratch_bytes(int B, int Ci, int Co, int D, int H, int W, int kd) {
     if (B <= 0 || Ci <= 0 || Co <= 0 || D <= 0 || H <= 0 || W <= 0 || (kd != 1 && kd != 3)) return 0;
-    const long long P = wgrad_workers(Ci, Co, ntiles_wino(B, D, H, W, kd), kd == 3 ? 1 : 2);
-    return (P + 1) * 16LL * kd * Co * Ci * (long long)sizeof(float);
+    WgPlan p{};
+    wgw_select(kd, [&](auto c) { p = plan<decltype(c), true>(B, Ci, Co, D, H, W); return 0; });
+    return p.scratch_floats * (long long)sizeof(float);
 }
 
 extern "C" int ecm_conv_wino_wgrad(const float* x, const float* gy, float* gw, void* scratch, long long scratch_bytes, int B,
                                    int Ci, int Co, int D, int H, int W, int kd, void* stream) {
     ECM_CHECK_ARG(x && gy && gw && scratch && B > 0 && Ci > 0 && Co > 0 && D > 0 && H > 0 && W > 0);
     if (kd != 1 && kd != 3) return ECM_EUNSUP;
-    if ((long long)D * H * W * 4 * 32 >= 0x7fffffffLL || ntiles_wino(B, D, H, W, kd) >= 0x7fffffffLL) return ECM_EUNSUP;
-    if (scratch_bytes < ecm_conv_wino_wgrad_scratch_bytes(B, Ci, Co, D, H, W, kd)) return ECM_ESCRATCH;
-    hipStream_t st = ecm_stream(stream);
-    if (kd == 3) return launch_wgrad_wino<2, 8, 3>(x, gy, gw, static_cast<float*>(scratch), B, Ci, Co, D, H, W, st);
-    return launch_wgrad_wino<1, 16, 1>(x, gy, gw, static_cast<float*>(scratch), B, Ci, Co, D, H, W, st);   // D independent planes
+    return wgw_select(kd, [&](auto c) {
+        using Cfg = decltype(c);
+        const WgPlan p = plan<Cfg, true>(B, Ci, Co, D, H, W);                // kd = 1: D independent planes
+        if ((long long)D * H * W * 4 * 32 >= 0x7fffffffLL || p.ntiles >= 0x7fffffffLL) return (int)ECM_EUNSUP;
+        if (scratch_bytes < p.scratch_floats * (long long)sizeof(float)) return (int)ECM_ESCRATCH;
+        return launch_wgrad_wino<Cfg>(x, gy, gw, static_cast<float*>(scratch), p, B, Ci, Co, D, H, W, ecm_stream(stream));
+    });
 }
+

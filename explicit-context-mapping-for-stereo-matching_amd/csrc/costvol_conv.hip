@@ -25,6 +25,73 @@ constexpr int NCP = 15, NCQ = 6;
 
 __device__ __forceinline__ int edge_of(int d, int D) { return d == 0 ? 0 : (d == D - 1 ? 2 : 1); }
 
+// ---- the class rules, stated once ---------------------------------------------------------------------------------------------
+// Each takes its operands through an accessor -- a functor (class or d, column) -> float over global memory (the element-wise
+// kernels) or over the LDS image of a row (the row-staged kernels) -- so both forms run the same additions in the same order
+// and give the same bits by construction.  The kernels keep only their indexing, staging and stores.
+
+// forward: y(d, x) = P[classP(d, x)][x] + Qp[classQ(d, x)][x - d + 2], 0 beyond the wedge; e = edge_of(d, D)
+template <class PA, class QA>
+__device__ __forceinline__ float cv_fwd_value(int d, int x, int e, int w, PA&& P, QA&& Q) {
+    const int delta = d - x;
+    float acc = 0.f;
+    if (delta < 3) {
+        const int dc = (delta < -2 ? -2 : delta) + 2;
+        acc = P(dc * 3 + e, x) + Q(e * 2 + (x == w - 1 ? 1 : 0), x - d + 2);
+    }
+    return acc;
+}
+
+// adjoint, reference half: out[cls] = sum over d with classP(d, x) == cls of G(d, x), the 15 classes of column x
+template <class GA>
+__device__ __forceinline__ void cv_ref_sums(int x, int D, GA&& G, float (&out)[NCP]) {
+#pragma unroll
+    for (int c = 0; c < NCP; ++c) out[c] = 0.f;
+    // d - x <= -2: every tap passes the wedge test; split by depth edge
+    const int da = x - 2 < D - 1 ? x - 2 : D - 1;           // last d of this region
+    if (da >= 0) out[0] = G(0, x);
+    {
+        float s = 0.f;
+        const int hi = da < D - 2 ? da : D - 2;
+        for (int d = 1; d <= hi; ++d) s += G(d, x);
+        out[1] = s;
+    }
+    if (da >= D - 1) out[2] = G(D - 1, x);
+    // d - x = -1, 0, 1, 2: one plane each
+#pragma unroll
+    for (int k = 1; k <= 4; ++k) {
+        const int d = x - 2 + k;
+        if (d >= 0 && d < D) {
+            const float v = G(d, x);
+            const int e = edge_of(d, D);
+            out[k * 3 + 0] = e == 0 ? v : 0.f;
+            out[k * 3 + 1] = e == 1 ? v : 0.f;
+            out[k * 3 + 2] = e == 2 ? v : 0.f;
+        }
+    }
+}
+
+// adjoint, target half: out[cls] = sum over d with x = (j - 2) + d in [0, w) and classQ(d, x) == cls of G(d, x), the 6 classes
+// (edge * 2 + right border) of apron column j: sums along the diagonal x = u + d
+template <class GA>
+__device__ __forceinline__ void cv_tgt_sums(int j, int D, int w, GA&& G, float (&out)[NCQ]) {
+    const int u = j - 2;
+    float first = 0.f, mid = 0.f, last = 0.f, firstr = 0.f, midr = 0.f, lastr = 0.f;      // (edge, right-border) sums
+    const int d0 = u < 0 ? -u : 0;                          // x = u + d >= 0
+    const int d1 = w - 1 - u < D - 1 ? w - 1 - u : D - 1;   // x <= w - 1
+    for (int d = d0; d <= d1; ++d) {
+        const int x = u + d;
+        const float v = G(d, x);
+        const bool rb = x == w - 1;
+        if (d == 0) { if (rb) firstr += v; else first += v; }
+        else if (d == D - 1) { if (rb) lastr += v; else last += v; }
+        else { if (rb) midr += v; else mid += v; }
+    }
+    out[0] = first; out[1] = firstr;
+    out[2] = mid;   out[3] = midr;
+    out[4] = last;  out[5] = lastr;
+}
+
 template <bool VEC4>
 __global__ __launch_bounds__(256) void costvol_conv_assemble(const float* __restrict__ P, const float* __restrict__ Qp,
                                                              float* __restrict__ y, int Co, int D, int h, int w,
@@ -43,17 +110,11 @@ __global__ __launch_bounds__(256) void costvol_conv_assemble(const float* __rest
     const size_t hw = (size_t)h * w, hq = (size_t)h * (w + 2);
     const float* Pb = P + (((size_t)b * NCP) * Co + co) * hw + (size_t)yy * w;
     const float* Qb = Qp + (((size_t)b * NCQ) * Co + co) * hq + (size_t)yy * (w + 2);
+    const auto Pg = [&](int c, int x) { return Pb[(size_t)c * Co * hw + x]; };
+    const auto Qg = [&](int c, int j) { return Qb[(size_t)c * Co * hq + j]; };
     float v[V];
 #pragma unroll
-    for (int k = 0; k < V; ++k) {
-        const int x = x0 + k, delta = d - x;
-        float acc = 0.f;
-        if (delta < 3) {
-            const int dc = (delta < -2 ? -2 : delta) + 2;
-            acc = Pb[(size_t)(dc * 3 + e) * Co * hw + x] + Qb[(size_t)(e * 2 + (x == w - 1 ? 1 : 0)) * Co * hq + (x - d + 2)];
-        }
-        v[k] = acc;
-    }
+    for (int k = 0; k < V; ++k) v[k] = cv_fwd_value(d, x0 + k, e, w, Pg, Qg);
     if (VEC4) *reinterpret_cast<float4*>(y + i * 4) = make_float4(v[0], v[1], v[2], v[3]);
     else y[i] = v[0];
 }
@@ -69,32 +130,9 @@ __global__ __launch_bounds__(256) void costvol_conv_gp(const float* __restrict__
     const int co = (int)(r % Co);
     const int b = (int)(r / Co);
     const size_t hw = (size_t)h * w;
-    const float* g = gy + (((size_t)b * Co + co) * D) * hw + (size_t)yy * w + x;
+    const float* g = gy + (((size_t)b * Co + co) * D) * hw + (size_t)yy * w;
     float out[NCP];
-#pragma unroll
-    for (int c = 0; c < NCP; ++c) out[c] = 0.f;
-    // d - x <= -2: every tap passes the wedge test; split by depth edge
-    const int da = x - 2 < D - 1 ? x - 2 : D - 1;           // last d of this region
-    if (da >= 0) out[0] = g[0];
-    {
-        float s = 0.f;
-        const int hi = da < D - 2 ? da : D - 2;
-        for (int d = 1; d <= hi; ++d) s += g[(size_t)d * hw];
-        out[1] = s;
-    }
-    if (da >= D - 1) out[2] = g[(size_t)(D - 1) * hw];
-    // d - x = -1, 0, 1, 2: one plane each
-#pragma unroll
-    for (int k = 1; k <= 4; ++k) {
-        const int d = x - 2 + k;
-        if (d >= 0 && d < D) {
-            const float v = g[(size_t)d * hw];
-            const int e = edge_of(d, D);
-            out[k * 3 + 0] = e == 0 ? v : 0.f;
-            out[k * 3 + 1] = e == 1 ? v : 0.f;
-            out[k * 3 + 2] = e == 2 ? v : 0.f;
-        }
-    }
+    cv_ref_sums(x, D, [&](int d, int xx) { return g[(size_t)d * hw + xx]; }, out);
     float* o = gP + (((size_t)b * NCP) * Co + co) * hw + (size_t)yy * w + x;
 #pragma unroll
     for (int c = 0; c < NCP; ++c) o[(size_t)c * Co * hw] = out[c];
@@ -114,23 +152,12 @@ __global__ __launch_bounds__(256) void costvol_conv_gq(const float* __restrict__
     const int b = (int)(r / Co);
     const size_t hw = (size_t)h * w;
     const float* g = gy + (((size_t)b * Co + co) * D) * hw + (size_t)yy * w;
-    const int u = j - 2;
-    float first = 0.f, mid = 0.f, last = 0.f, firstr = 0.f, midr = 0.f, lastr = 0.f;      // (edge, right-border) sums
-    const int d0 = u < 0 ? -u : 0;                          // x = u + d >= 0
-    const int d1 = w - 1 - u < D - 1 ? w - 1 - u : D - 1;   // x <= w - 1
-    for (int d = d0; d <= d1; ++d) {
-        const int x = u + d;
-        const float v = g[(size_t)d * hw + x];
-        const bool rb = x == w - 1;
-        if (d == 0) { if (rb) firstr += v; else first += v; }
-        else if (d == D - 1) { if (rb) lastr += v; else last += v; }
-        else { if (rb) midr += v; else mid += v; }
-    }
+    float out[NCQ];
+    cv_tgt_sums(j, D, w, [&](int d, int x) { return g[(size_t)d * hw + x]; }, out);
     const size_t hq = (size_t)h * wq;
     float* o = gQp + (((size_t)b * NCQ) * Co + co) * hq + (size_t)yy * wq + j;
-    o[0 * Co * hq] = first; o[1 * Co * hq] = firstr;
-    o[2 * Co * hq] = mid;   o[3 * Co * hq] = midr;
-    o[4 * Co * hq] = last;  o[5 * Co * hq] = lastr;
+#pragma unroll
+    for (int c = 0; c < NCQ; ++c) o[(size_t)c * Co * hq] = out[c];
 }
 
 
@@ -138,9 +165,9 @@ __global__ __launch_bounds__(256) void costvol_conv_gq(const float* __restrict__
 // The element-wise kernels above issue two 4-byte gathers per output (forward, 2.4 TB/s of unique traffic) and read gy twice
 // (backward: once per class family, 3.7 TB/s).  Here one workgroup owns one (b, co, y) row set: forward stages the 15 P rows
 // and 6 Qp rows (21 w + 12 floats) in LDS with 16-byte coalesced loads and writes the D x w outputs as 16-byte streaming
-// stores; backward stages the D x w gradients once and produces both class families from LDS.  Same per-element arithmetic and
-// the same order of additions as the element-wise kernels (bit-identical results); those stay as the path for rows that do not
-// fit (LDS) or are not a multiple of 4 wide.
+// stores; backward stages the D x w gradients once and produces both class families from LDS.  The class rules are the
+// element-wise kernels' own (cv_fwd_value, cv_ref_sums, cv_tgt_sums over the LDS image): bit-identical results.  The
+// element-wise kernels stay as the path for rows that do not fit (LDS) or are not a multiple of 4 wide.
 __global__ __launch_bounds__(256) void costvol_conv_assemble_rows(const float* __restrict__ P, const float* __restrict__ Qp,
                                                                   float* __restrict__ y, int Co, int D, int h, int w) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -165,20 +192,14 @@ __global__ __launch_bounds__(256) void costvol_conv_assemble_rows(const float* _
     }
     __syncthreads();
     float* yb = y + (((size_t)b * Co + co) * D) * hw + (size_t)yy * w;
+    const auto Pl = [&](int c, int x) { return Ps[c * w + x]; };
+    const auto Ql = [&](int c, int j) { return Qs[c * wq + j]; };
     for (int i = threadIdx.x; i < D * w4; i += 256) {
         const int d = i / w4, x0 = (i - d * w4) * 4;
         const int e = edge_of(d, D);
         float v[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int x = x0 + k, delta = d - x;
-            float acc = 0.f;
-            if (delta < 3) {
-                const int dc = (delta < -2 ? -2 : delta) + 2;
-                acc = Ps[(dc * 3 + e) * w + x] + Qs[(e * 2 + (x == w - 1 ? 1 : 0)) * wq + (x - d + 2)];
-            }
-            v[k] = acc;
-        }
+        for (int k = 0; k < 4; ++k) v[k] = cv_fwd_value(d, x0 + k, e, w, Pl, Ql);
         ecm_st_stream(yb + (size_t)d * hw + x0, make_float4(v[0], v[1], v[2], v[3]));
     }
 }
@@ -200,53 +221,20 @@ __global__ __launch_bounds__(256) void costvol_conv_grad_rows(const float* __res
         reinterpret_cast<float4*>(G + d * w)[x4] = reinterpret_cast<const float4*>(gb + (size_t)d * hw)[x4];
     }
     __syncthreads();
-    // reference half: the adjoint of the 15 wedge / depth-edge classes (same order of additions as costvol_conv_gp)
-    for (int x = threadIdx.x; x < w; x += 256) {
+    const auto Gl = [&](int d, int x) { return G[d * w + x]; };
+    for (int x = threadIdx.x; x < w; x += 256) {             // reference half: the 15 wedge / depth-edge classes
         float out[NCP];
-#pragma unroll
-        for (int c = 0; c < NCP; ++c) out[c] = 0.f;
-        const int da = x - 2 < D - 1 ? x - 2 : D - 1;
-        if (da >= 0) out[0] = G[x];
-        {
-            float s = 0.f;
-            const int hi = da < D - 2 ? da : D - 2;
-            for (int d = 1; d <= hi; ++d) s += G[d * w + x];
-            out[1] = s;
-        }
-        if (da >= D - 1) out[2] = G[(D - 1) * w + x];
-#pragma unroll
-        for (int k = 1; k <= 4; ++k) {
-            const int d = x - 2 + k;
-            if (d >= 0 && d < D) {
-                const float v = G[d * w + x];
-                const int e = edge_of(d, D);
-                out[k * 3 + 0] = e == 0 ? v : 0.f;
-                out[k * 3 + 1] = e == 1 ? v : 0.f;
-                out[k * 3 + 2] = e == 2 ? v : 0.f;
-            }
-        }
+        cv_ref_sums(x, D, Gl, out);
         float* o = gP + (((size_t)b * NCP) * Co + co) * hw + (size_t)yy * w + x;
 #pragma unroll
         for (int c = 0; c < NCP; ++c) o[(size_t)c * Co * hw] = out[c];
     }
-    // target half: sums along the diagonals x = u + d (same order as costvol_conv_gq)
-    for (int j = threadIdx.x; j < wq; j += 256) {
-        const int u = j - 2;
-        float first = 0.f, mid = 0.f, last = 0.f, firstr = 0.f, midr = 0.f, lastr = 0.f;
-        const int d0 = u < 0 ? -u : 0;
-        const int d1 = w - 1 - u < D - 1 ? w - 1 - u : D - 1;
-        for (int d = d0; d <= d1; ++d) {
-            const int x = u + d;
-            const float v = G[d * w + x];
-            const bool rb = x == w - 1;
-            if (d == 0) { if (rb) firstr += v; else first += v; }
-            else if (d == D - 1) { if (rb) lastr += v; else last += v; }
-            else { if (rb) midr += v; else mid += v; }
-        }
+    for (int j = threadIdx.x; j < wq; j += 256) {            // target half: the 6 classes along the diagonals
+        float out[NCQ];
+        cv_tgt_sums(j, D, w, Gl, out);
         float* o = gQp + (((size_t)b * NCQ) * Co + co) * hq + (size_t)yy * wq + j;
-        o[0 * Co * hq] = first; o[1 * Co * hq] = firstr;
-        o[2 * Co * hq] = mid;   o[3 * Co * hq] = midr;
-        o[4 * Co * hq] = last;  o[5 * Co * hq] = lastr;
+#pragma unroll
+        for (int c = 0; c < NCQ; ++c) o[(size_t)c * Co * hq] = out[c];
     }
 }
 

@@ -15,6 +15,7 @@
 // Kernel D: fixed-order sum of the per-workgroup partials -> gW (deterministic).
 #include "common.h"
 #include "ecm_nbr.h"
+#include "partial_sum.h"
 
 namespace {
 
@@ -158,13 +159,11 @@ __global__ __launch_bounds__(128) void ecm_weights_bwd_cells(const float* __rest
     for (int u = 0; u < 8; ++u) pc[u] = a[u];
 }
 
-// Kernel D: gW = [gW0 (32x66) | gW1 (16x32) | gW2 (8x16) | gW3 (8)], fixed-order sums of the partials: a workgroup owns
-// 32 outputs, its 8 lane groups each sum every 8th partial, and the 8 group sums are added in order (one thread per
-// output walking up to ~1000 partials was latency-bound: 0.56 ms).
+// Kernel D: gW = [gW0 (32x66) | gW1 (16x32) | gW2 (8x16) | gW3 (8)], fixed-order sums of the partials (partial_sum.h) around a
+// table of where output k's partials lie: kernel C's [nC][1024] or a field of kernel B's [nB][PB_N].
 __global__ __launch_bounds__(256) void ecm_weights_bwd_reduce(const float* __restrict__ partB, int nB,
                                                               const float* __restrict__ partC, int nC,
                                                               float* __restrict__ gW) {
-    __shared__ float sm[8][32];
     const int o = threadIdx.x & 31, grp = threadIdx.x >> 5;
     const int k = blockIdx.x * 32 + o;
     float s = 0.f;
@@ -180,25 +179,9 @@ __global__ __launch_bounds__(256) void ecm_weights_bwd_reduce(const float* __res
         } else if (k < 2624) { src = partB + PB_W1 + (k - 2112); stride = PB_N; n = nB; }
         else if (k < 2752) { src = partB + PB_W2 + (k - 2624); stride = PB_N; n = nB; }
         else { src = partB + PB_W3 + (k - 2752); stride = PB_N; n = nB; }
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        int p = grp;
-        for (; p + 24 < n; p += 32) {
-            s0 += src[(size_t)p * stride];
-            s1 += src[(size_t)(p + 8) * stride];
-            s2 += src[(size_t)(p + 16) * stride];
-            s3 += src[(size_t)(p + 24) * stride];
-        }
-        for (; p < n; p += 8) s0 += src[(size_t)p * stride];
-        s = (s0 + s1) + (s2 + s3);
+        s = partial_group_sum(src, stride, n, grp);
     }
-    sm[grp][o] = s;
-    __syncthreads();
-    if (grp == 0 && k < 2760) {
-        float t = 0.f;
-#pragma unroll
-        for (int g = 0; g < 8; ++g) t += sm[g][o];
-        gW[k] = t;
-    }
+    partial_tail(s, o, grp, k < 2760, gW + k);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

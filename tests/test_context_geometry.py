@@ -45,8 +45,14 @@ def test_weight_kernel_constants_are_those_of_the_sources():
     assert int(_one(bwd, r"p\.nC = \(int\)\(\(\(long long\)B \* h \* w \+ 127\) / (\d+)\);", "nC")) == T.CELL_BLOCK
     assert int(_one(bwd, r"const long long i = \(long long\)blockIdx\.x \* (\d+) \+ threadIdx\.x;\n    const bool valid", "cells block")) == T.CELL_BLOCK
     assert _one(bwd, r"const int lpc = (4 \* s);", "lanes per cell") and _one(bwd, r"const int hw = h \* w, rpc = (s / TY),", "rpc")
-    # the reduce kernel: 8 lane groups, an unrolled loop of 4 strides, a tail loop
-    assert _one(bwd, r"for \(; (p \+ 24 < n; p \+= 32)\)", "unrolled loop") and _one(bwd, r"for \(; (p < n; p \+= 8)\)", "tail loop")
+    # the reduce kernel: 8 lane groups, an unrolled loop of 4 strides, a tail loop -- the one statement of partial_sum.h, which
+    # the kernel calls around its source table
+    psum = _source("partial_sum.h")
+    assert _one(psum, r"for \(; (p \+ 24 < n; p \+= 32)\)", "unrolled loop") and _one(psum, r"for \(; (p < n; p \+= 8)\)", "tail loop")
+    assert _one(psum, r"(return \(s0 \+ s1\) \+ \(s2 \+ s3\);)", "pairing") and _one(psum, r"(__shared__ float sm\[8\]\[32\];)", "tail")
+    assert _one(bwd, r"(s = partial_group_sum\(src, stride, n, grp\);)", "the call") and _one(bwd, r"(partial_tail\(s, o, grp, k < 2760, gW \+ k\);)", "tail")
+    all_src = "".join(_source(f) for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".h")))
+    assert all_src.count("p + 24 <") == 1 and all_src.count("sm[8][32]") == 1          # one eight-group partial sum in the library
     # the backward's gate, in the size query and in the entry point
     gate = "(s != 4 && s != 8 && s != 16)"
     assert bwd.count(gate) == 2 and T.BWD_SCALES == (4, 8, 16)

@@ -110,22 +110,35 @@ def test_winograd_rule_is_that_of_the_source():
 def test_weight_gradient_dispatch_is_that_of_the_source():
     src = _read("csrc", "conv3d_wgrad.hip")
     assert (_constexpr(src, "CT", "conv3d_wgrad.hip"), _constexpr(src, "TWV", "conv3d_wgrad.hip")) == (T.CT, T.TWV)
+    # the table of the general 2-D family: one Wg2<KH, KW, S, DL, TH> per instantiation, in wg2_select alone
+    sel = _body(src, "int wg2_select(")
+    got = {tuple(map(int, m[:4])): int(m[4]) for m in re.findall(r"Wg2<(\d+), (\d+), (\d+), (\d+), (\d+)>", sel)}
+    assert got == T.WG2_TH and len(re.findall(r"Wg2<\d", src)) == len(T.WG2_TH) == 7
+    assert "template <int KH, int KW, int S, int DL, int TH> using Wg2 = WgCfg<S, 1, TH, 1, KH, KW, DL>;" in src
+    assert "Cfg::KH == kh && Cfg::KW == kw && Cfg::S == stride && (dil < 0 || Cfg::DIL == dil);" in sel
     body = _body(src, 'extern "C" int ecm_conv2d_wgrad_ex(')
-    got = {tuple(map(int, m[:4])): int(m[4]) for m in re.findall(r"^    WG2\((\d+), (\d+), (\d+), (\d+), (\d+)\);", body, re.M)}
-    assert got == T.WG2_TH and len(re.findall(r"^    WG2\(", body, re.M)) == len(T.WG2_TH) == 7
-    assert "return launch_wgrad<S, 1, TH, 1, KH, KW, DL>(x, gy, gw, partial, B, Ci, Co, 1, H, W, st, Ho, Wo, pad_top, pad_left)" in body
-    nt = _body(src, "inline long long ntiles2d_ex(")
-    assert "const int th = stride == 1 ? 16 : 8;" in nt and "return (long long)B * ((Ho + th - 1) / th) * ((Wo + TWV - 1) / TWV);" in nt
-    workers = _body(src, "inline int wgrad_workers(")
-    assert "((Ci + CT - 1) / CT) * ((Co + CT - 1) / CT)" in workers
-    assert _ints(workers, r"long long p = (\d+) \* occ / ytiles;", "wgrad_workers") == (T.WGRAD_WORKERS,)
-    assert "if (p < 1) p = 1;" in workers and "if (p > ntiles) p = ntiles;" in workers
-    assert src.count("wgrad_workers(Ci, Co, ntiles, KD == 3 ? 1 : 2);") == 2 and T.WGRAD_OCC2D == 2
-    assert "wgrad_workers(Ci, Co, ntiles2d_ex(B, Ho, Wo, stride), 2)" in src
-    wino = _body(src, 'extern "C" int ecm_conv_wino_wgrad(')
-    assert "    return launch_wgrad_wino<%d, %d, %d>(" % T.WGW_INST in wino
-    assert "const int TD = kd == 3 ? 2 : 1, TH = kd == 3 ? 8 : 16;" in src
-    assert "tiles_d = (D + TD - 1) / TD, tiles_h = (H + TH - 1) / TH, tiles_w = (W + TWV - 1) / TWV;" in _body(src, "int launch_wgrad_wino(")
+    assert ("return launch_wgrad<Cfg>(x, gy, gw, static_cast<float*>(scratch), plan<Cfg>(B, Ci, Co, 1, Ho, Wo), B, Ci, Co, 1, H, W,\n"
+            "                                 ecm_stream(stream), pad_top, pad_left);") in body
+    assert "return wg2_select(kh, kw, stride, dil, [&](auto c) {" in body
+    assert "conv3d_wgrad_mfma<Cfg::S, Cfg::TD, Cfg::TH, Cfg::KD, Cfg::KH, Cfg::KW, Cfg::DIL>" in _body(src, "int launch_wgrad(")
+    # the query: the row of (kh, kw, stride) at any dilation; outside the table the 3x3 row of the stride (TH 16 | 8)
+    q = _body(src, "inline WgPlan wg2_query_plan(")
+    assert "p = plan<decltype(c)>(B, Ci, Co, 1, Ho, Wo);" in q
+    assert "if (wg2_select(kh, kw, stride, -1, take) != 0) wg2_select(3, 3, stride == 1 ? 1 : 2, -1, take);" in q
+    assert (T.WG2_TH[(3, 3, 1, 1)], T.WG2_TH[(3, 3, 2, 1)]) == (16, 8)
+    assert len({th for (kh, kw, s, d), th in T.WG2_TH.items() if s == 1}) == len({th for (kh, kw, s, d), th in T.WG2_TH.items() if s == 2}) == 1
+    assert _ints(src, r"^constexpr int WG2_MAX_KG = (\d+);", "WG2_MAX_KG") == (4,)
+    assert "wg2_query_plan(B, Ci, Co, Ho, Wo, kh, kw, stride).P * WG2_MAX_KG * Co * Ci * kh * kw * (long long)sizeof(float);" in src
+    assert "static_assert(Cfg::KD == 3 || Cfg::KG <= WG2_MAX_KG," in _body(src, "int launch_wgrad(")
+    workers = _body(src, "WgPlan plan(")
+    assert "p.ci_tiles = (Ci + CT - 1) / CT; p.co_tiles = (Co + CT - 1) / CT;" in workers
+    assert _ints(workers, r"long long workers = (\d+) \* Cfg::OCC / \(p\.ci_tiles \* p\.co_tiles\);", "workers") == (T.WGRAD_WORKERS,)
+    assert "if (workers < 1) workers = 1;" in workers and "if (workers > p.ntiles) workers = p.ntiles;" in workers
+    assert src.count("static constexpr int OCC = KD == 3 ? 1 : 2;") == 1 and src.count("KD == 3 ? 1 : 2") == 1 and T.WGRAD_OCC2D == 2
+    assert "wg_select<WgCfg<1, 2, 8, 3>, WgCfg<1, %d, %d, %d>>(" % T.WGW_INST in _body(src, "int wgw_select(")
+    assert ("p.tiles_d = (Do + Cfg::TD - 1) / Cfg::TD; p.tiles_h = (Ho + Cfg::TH - 1) / Cfg::TH; p.tiles_w = (Wo + TWV - 1) / TWV;"
+            in workers)
+    assert "true>(B, Ci, Co, D, H, W);" in _body(src, 'extern "C" int ecm_conv_wino_wgrad(')
     ops = _read("ops.py")
     assert '"ecm_conv2d_wgrad_ex",\n                          _p(gy), _p(x), _p(gw), _SCRATCH, B, Co, Ci, Ho, Wo, 3, 3, 2, 1, 1, 1, H, W, _stream())' in ops
 
@@ -145,10 +158,12 @@ def test_deconv_and_c1_constants_are_those_of_the_sources():
     assert _ints(c1, r"^constexpr int C1_TX = (\d+), C1_TY = (\d+);", "C1_TX, C1_TY") == (T.C1_TX, T.C1_TY)
     got = {n: _constexpr(c1, n, "conv2d_c1.hip") for n in ("C1_CC", "C1_SUB", "C1_CHUNK")}
     assert got == {n: getattr(T, n) for n in got}
-    assert "inline int c1_strips(int H) { return (H + C1_TY * C1_SUB - 1) / (C1_TY * C1_SUB); }" in c1
+    plan = _body(c1, "inline C1WgPlan c1_wgrad_plan(")                  # read by the scratch query and by the launcher
+    assert "p.strips_y = (H + C1_TY * C1_SUB - 1) / (C1_TY * C1_SUB);" in plan and "p.tiles_x = (W + C1_TX - 1) / C1_TX;" in plan
+    assert "p.P = (long long)B * p.strips_y * p.tiles_x;" in plan and "p.n = Ci * 9 + 1;" in plan
+    assert c1.count("c1_wgrad_plan(B, Ci, H, W);") == 2 and "c1_strips" not in c1
     wg = _body(c1, 'extern "C" int ecm_conv2d_c1_wgrad(')
-    assert "const int tx = (W + C1_TX - 1) / C1_TX, sy = c1_strips(H);" in wg and "const int P = B * sy * tx, n = Ci * 9 + 1;" in wg
-    assert "dim3((unsigned)P)" in wg                                    # one workgroup per strip: the worker count is not capped
+    assert "dim3((unsigned)p.P)" in wg                                  # one workgroup per strip: the worker count is not capped
     assert c1.count("const int tx = (W + C1_TX - 1) / C1_TX, ty = (H + C1_TY - 1) / C1_TY;") == 2
     cs = _body(c1, 'extern "C" int ecm_channel_sum(')
     assert "const long long chunks = (HW + C1_CHUNK - 1) / C1_CHUNK;" in cs

@@ -82,20 +82,33 @@ def test_direct_forward_dispatch_is_that_of_the_source():
 def test_weight_gradient_dispatch_is_that_of_the_source():
     src = _read("csrc", "conv3d_wgrad.hip")
     assert (_constexpr(src, "CT", "conv3d_wgrad.hip"), _constexpr(src, "TWV", "conv3d_wgrad.hip")) == (T.CT, T.TWV)
-    body = _body(src, 'extern "C" int ecm_conv3d_k3_wgrad(')
-    assert "if (stride == 1) return launch_wgrad<%d, %d, %d, %d>(" % T.WGRAD_INST["s1"] in body
-    assert "    return launch_wgrad<%d, %d, %d, %d>(" % T.WGRAD_INST["s2"] in body
-    assert len(re.findall(r"launch_wgrad<", body)) == 2
-    wino = _body(src, 'extern "C" int ecm_conv_wino_wgrad(')
-    assert "if (kd == 3) return launch_wgrad_wino<%d, %d, %d>(" % T.WGRAD_INST["wino"] in wino
-    workers = _body(src, "inline int wgrad_workers(")
-    assert "int occ = 1" in workers and "((Ci + CT - 1) / CT) * ((Co + CT - 1) / CT)" in workers
-    assert _ints(workers, r"long long p = (\d+) \* occ / ytiles;", "wgrad_workers") == (T.WGRAD_WORKERS,)
-    assert "if (p < 1) p = 1;" in workers and "if (p > ntiles) p = ntiles;" in workers
-    assert src.count("wgrad_workers(Ci, Co, ntiles, KD == 3 ? 1 : 2);") == 2 and T.WGRAD_OCC3D == 1
-    # tile counts: TWV columns; the Winograd form tiles the (stride-1) volume itself
-    assert "tiles_d = (Do + TD - 1) / TD, tiles_h = (Ho + TH - 1) / TH, tiles_w = (Wo + TWV - 1) / TWV;" in _body(src, "int launch_wgrad(")
-    assert "tiles_d = (D + TD - 1) / TD, tiles_h = (H + TH - 1) / TH, tiles_w = (W + TWV - 1) / TWV;" in _body(src, "int launch_wgrad_wino(")
+    # one selector per family names the instantiations; the query and the entry point both go through it to plan<Cfg>
+    sel = _body(src, "int wg3_select(")
+    assert "wg_select<WgCfg<%d, %d, %d, %d>, WgCfg<%d, %d, %d, %d>>(" % (T.WGRAD_INST["s1"] + T.WGRAD_INST["s2"]) in sel
+    assert "decltype(c)::S == stride" in sel and len(re.findall(r"WgCfg<", sel)) == 2
+    assert "wg_select<WgCfg<1, %d, %d, %d>, WgCfg<" % T.WGRAD_INST["wino"] in _body(src, "int wgw_select(")
+    assert "decltype(c)::KD == kd" in _body(src, "int wgw_select(")
+    for fn in ('extern "C" long long ecm_conv3d_wgrad_scratch_bytes(', 'extern "C" int ecm_conv3d_k3_wgrad('):
+        assert "wg3_select(stride, [&](auto c) {" in _body(src, fn)
+        assert "(B, Ci, Co, wg_out(D, stride), wg_out(H, stride), wg_out(W, stride));" in _body(src, fn)
+    assert "inline int wg_out(int n, int stride) { return (n - 1) / stride + 1; }" in src
+    assert "return launch_wgrad<Cfg>(" in _body(src, 'extern "C" int ecm_conv3d_k3_wgrad(')
+    assert "conv3d_wgrad_mfma<Cfg::S, Cfg::TD, Cfg::TH, Cfg::KD, Cfg::KH, Cfg::KW, Cfg::DIL>" in _body(src, "int launch_wgrad(")
+    assert "conv3d_wgrad_mfma<1, Cfg::TD, Cfg::TH, Cfg::KD, 3, 3, 1, true>" in _body(src, "int launch_wgrad_wino(")
+    for fn in ('extern "C" long long ecm_conv_wino_wgrad_scratch_bytes(', 'extern "C" int ecm_conv_wino_wgrad('):
+        assert "wgw_select(kd, [&](auto c) {" in _body(src, fn) and "true>(B, Ci, Co, D, H, W);" in _body(src, fn)
+    workers = _body(src, "WgPlan plan(")
+    assert "p.ci_tiles = (Ci + CT - 1) / CT; p.co_tiles = (Co + CT - 1) / CT;" in workers
+    assert _ints(workers, r"long long workers = (\d+) \* Cfg::OCC / \(p\.ci_tiles \* p\.co_tiles\);", "workers") == (T.WGRAD_WORKERS,)
+    assert "if (workers < 1) workers = 1;" in workers and "if (workers > p.ntiles) workers = p.ntiles;" in workers
+    # the occupancy is one number: WgCfg::OCC, read by the kernel's launch bounds and by plan()
+    assert src.count("static constexpr int OCC = KD == 3 ? 1 : 2;") == 1 and src.count("KD == 3 ? 1 : 2") == 1 and T.WGRAD_OCC3D == 1
+    assert "__launch_bounds__(256, (WgCfg<STRIDE, TD, TH, KD, KH, KW, DIL>::OCC)) void conv3d_wgrad_mfma(" in src
+    # tile counts: TWV columns; the Winograd form tiles the (stride-1) volume itself (its plan is given D, H, W)
+    assert ("p.tiles_d = (Do + Cfg::TD - 1) / Cfg::TD; p.tiles_h = (Ho + Cfg::TH - 1) / Cfg::TH; p.tiles_w = (Wo + TWV - 1) / TWV;"
+            in workers)
+    for gone in ("ntiles_for", "ntiles_wino", "ntiles2d_ex", "WG2(", "wgrad_workers", "wgrad_reduce"):
+        assert gone not in src, gone
     # the persistent schedule worker_runs restates
     for line in ("if ((gridDim.x & 7u) == 0u) {", "const unsigned start = xcd * q + (xcd < rr ? xcd : rr);",
                  "tile0 = start + (blockIdx.x >> 3);", "tile_end = start + q + (xcd < rr ? 1u : 0u);", "tile_step = gridDim.x >> 3;",
@@ -134,9 +147,11 @@ def test_deconv_and_c1_constants_are_those_of_the_sources():
     c1 = _read("csrc", "conv3d_c1.hip")
     got = {n: _constexpr(c1, n, "conv3d_c1.hip") for n in ("VT_W", "VT_H", "VT_D", "DTH", "DTW", "GTD", "GTH", "GTW")}
     assert got == {n: getattr(T, n) for n in got}
-    assert _ints(c1, r"inline int c1_workers\(long long ntiles\) \{ return \(int\)\(ntiles < (\d+) \? ntiles : (\d+)\); \}",
-                 "c1_workers") == (T.C1_WORKERS,) * 2
-    assert "((D + GTD - 1) / GTD) * ((H + GTH - 1) / GTH) * ((W + GTW - 1) / GTW);" in c1
+    plan = _body(c1, "inline C1WgPlan c1_wgrad_plan(")                  # read by the scratch query and by the launcher
+    assert _ints(plan, r"p\.P = \(int\)\(p\.ntiles < (\d+) \? p\.ntiles : (\d+)\);", "workers") == (T.C1_WORKERS,) * 2
+    assert "p.tiles_d = (D + GTD - 1) / GTD; p.tiles_h = (H + GTH - 1) / GTH; p.tiles_w = (W + GTW - 1) / GTW;" in plan
+    assert "p.ntiles = (long long)B * p.tiles_d * p.tiles_h * p.tiles_w;" in plan
+    assert c1.count("c1_wgrad_plan(B, Ci, D, H, W);") == 2 and "c1_workers" not in c1 and "c1_tiles" not in c1
     assert "for (unsigned tile = blockIdx.x; tile < (unsigned)ntiles; tile += gridDim.x) {" in c1
     assert "if (valu && Ci % 2 == 0) return launch_c1_fwd_v<false>(" in c1
 

@@ -542,7 +542,10 @@ def test_assembly_constants_are_those_of_the_source():
     assert src.count("    if (w % 4 == 0) {\n        const long long nv = n / 4;") == 1
     assert src.count("const int nP = 15 * Co * C * 9, nQ = 6 * Co * C * 15;") == 1
     assert src.count("const long long n = (long long)Co * C * (15 * 9 + 6 * 15);") == 1
-    assert src.count("delta < 3") == 2 and src.count("x == w - 1") == 4 and src.count("+= 256") == 6
+    # the class rules are stated once (cv_fwd_value, cv_ref_sums, cv_tgt_sums) and called by the element-wise and the row-staged kernels
+    assert src.count("delta < 3") == 1 and src.count("x == w - 1") == 2 and src.count("+= 256") == 6
+    assert src.count("const int hi = da < D - 2 ? da : D - 2;") == 1 and src.count("if (d == 0) { if (rb) firstr += v; else first += v; }") == 1
+    assert src.count("cv_fwd_value(d, x0 + k, e, w, ") == 2 and src.count("cv_ref_sums(x, D, ") == 2 and src.count("cv_tgt_sums(j, D, w, ") == 2
     # the gates at the widths of the case table: 776 is the widest row set that fits, 780 the first that does not; 64 x 256 fits exactly
     assert fwd_lds_bytes(776) == 65232 and fwd_lds_bytes(780) == 65568 and fwd_lds_bytes(776) == (21 * 776 + 12) * 4
     assert bwd_lds_bytes(64, 256) == LDS_MAX and bwd_lds_bytes(64, 260) > LDS_MAX

@@ -223,6 +223,84 @@ def test_frame_preparation(ecm):
         g.check("frame_prep")
 
 
+# ---- the weight gradients' scratch: what the query promises against what the launcher writes -----------------------------------------
+# kind -> (query, entry point, family of the restated plan); a case is (kind, B, Ci, Co, (D, H, W) of x, kh = kw, stride)
+_WG = {"3d": ("ecm_conv3d_wgrad_scratch_bytes", "ecm_conv3d_k3_wgrad"), "wino": ("ecm_conv_wino_wgrad_scratch_bytes", "ecm_conv_wino_wgrad"),
+       "2d": ("ecm_conv2d_wgrad_ex_scratch_bytes", "ecm_conv2d_wgrad_ex"), "c1": ("ecm_conv3d_c1_wgrad_scratch_bytes", "ecm_conv3d_c1_wgrad"),
+       "c1gn": ("ecm_conv3d_c1_wgrad_scratch_bytes", "ecm_conv3d_c1_gn_wgrad"), "c1_2d": ("ecm_conv2d_c1_wgrad_scratch_bytes", "ecm_conv2d_c1_wgrad")}
+_WG_CAP = [("3d", 1, 64, 64, (6, 32, 96), 3, 1), ("3d", 1, 64, 64, (12, 32, 96), 3, 2), ("wino", 1, 64, 64, (6, 32, 96), 3, 1),
+           ("wino", 1, 128, 128, (1, 90, 90), 1, 1), ("2d", 1, 128, 128, (1, 90, 90), 3, 1), ("2d", 1, 128, 128, (1, 140, 140), 1, 2)]
+_WG_REFUSE = _WG_CAP[:1] + _WG_CAP[3:5] + [("c1", 2, 32, 1, (6, 9, 33), 3, 1), ("c1gn", 2, 32, 1, (6, 9, 33), 3, 1), ("c1_2d", 2, 8, 1, (1, 40, 70), 3, 1)]
+
+
+def _wg_setup(ecm, case, alloc):
+    """-> (sizes of the query, entry point, its arguments with ops._SCRATCH in place, gw, (ntiles, P) of the restated plan).  The
+    operands come from torch, the outputs from `alloc` (the guarded proxy's `empty` inside `guarded`)."""
+    import test_wgrad_plan_cpu as WP
+    ops = ecm.ops
+    kind, B, Ci, Co, (D, H, W), k, stride = case
+    p, st = ops._p, ops._stream()
+    Do, Ho, Wo = ((n - 1) // stride + 1 for n in (D, H, W))
+    x = R(B, Ci, D, H, W, seed=40, grad=False)
+    gy = R(B, Co, Do, Ho, Wo, seed=41, grad=False)
+    query, entry = _WG[kind]
+    if kind == "3d":
+        gw = alloc(Co, Ci, 3, 3, 3, device="cuda")
+        return (B, Ci, Co, D, H, W, stride), entry, (p(x), p(gy), p(gw), ops._SCRATCH, B, Ci, Co, D, H, W, stride, st), gw, \
+            (x, gy), WP.plan_3d(B, Ci, Co, D, H, W, stride)[:2]
+    if kind == "wino":
+        gw = alloc(Co, Ci, k, 3, 3, device="cuda")
+        return (B, Ci, Co, D, H, W, k), entry, (p(x), p(gy), p(gw), ops._SCRATCH, B, Ci, Co, D, H, W, k, st), gw, \
+            (x, gy), WP.plan_wino(B, Ci, Co, D, H, W, k)[:2]
+    if kind == "2d":
+        gw = alloc(Co, Ci, k, k, device="cuda")
+        return (B, Ci, Co, Ho, Wo, k, k, stride), entry, \
+            (p(x), p(gy), p(gw), ops._SCRATCH, B, Ci, Co, H, W, k, k, stride, 1, k // 2, k // 2, Ho, Wo, st), gw, \
+            (x, gy), WP.plan_2d(B, Ci, Co, Ho, Wo, k, k, stride)[:2]
+    if kind in ("c1", "c1gn"):
+        gw = alloc(1, Ci, 3, 3, 3, device="cuda")
+        gn = (torch.rand(B, 32, 2, device="cuda") + 0.5, R(Ci, seed=42, grad=False), R(Ci, seed=43, grad=False)) if kind == "c1gn" else ()
+        return (B, Ci, D, H, W), entry, (p(x), *map(p, gn), p(gy), p(gw), ops._SCRATCH, B, Ci, D, H, W, st), gw, \
+            (x, gy, gn), WP.plan_c1_3d(B, Ci, D, H, W)[:2]
+    gw, gb = alloc(1, Ci, 3, 3, device="cuda"), alloc(1, device="cuda")      # c1_2d: x, gy, y (the layer's ReLU output), gw, gb
+    y = R(B, 1, H, W, seed=44, grad=False)
+    return (B, Ci, H, W), entry, (p(x), p(gy), p(y), p(gw), p(gb), ops._SCRATCH, B, Ci, H, W, st), gw, (x, gy, y, gb), \
+        WP.plan_c1_2d(B, Ci, H, W)[:2]
+
+
+@pytest.mark.parametrize("case", _WG_CAP, ids=lambda c: "%s-k%d-s%d-%dx%d" % (c[0], c[5], c[6], c[2], c[3]))
+def test_weight_gradient_where_the_worker_cap_binds(ecm, case):
+    """P < ntiles: every worker walks several tiles and the scratch is P partials, not one per tile.  The scratch these calls get
+    is exactly the queried size (ops._call_scratch allocates it through the guarded proxy), so intact margins show that the query
+    and the launcher read one plan."""
+    ops = ecm.ops
+    with guarded(ecm) as g:
+        sizes, entry, args, gw, keep, (ntiles, P) = _wg_setup(ecm, case, ops.torch.empty)
+        assert P < ntiles, f"{case}: the worker cap no longer binds ({P} workers, {ntiles} tiles)"
+        ops._call_scratch("cuda", _WG[case[0]][0], sizes, entry, *args)
+        g.check(f"weight gradient {case}")
+        assert len(g.records) == 2 and bool(torch.isfinite(gw).all())       # gw and the scratch
+    ops.check_async_errors()
+
+
+@pytest.mark.parametrize("case", _WG_REFUSE, ids=lambda c: "%s-k%d-s%d" % (c[0], c[5], c[6]))
+def test_weight_gradient_refuses_short_scratch(ecm, case):
+    """One byte short of the query: ECM_ESCRATCH (-3) through the C ABI, nothing launched, the output untouched."""
+    import ctypes
+    ops = ecm.ops
+    sizes, entry, args, gw, keep, _ = _wg_setup(ecm, case, torch.empty)
+    nb = ecm._lib.query(_WG[case[0]][0], *sizes)
+    assert nb > 16
+    gw.fill_(777.0)
+    scratch = torch.empty(nb, dtype=torch.uint8, device="cuda")
+    at = next(i for i, a in enumerate(args) if a is ops._SCRATCH)
+    fn = getattr(ecm._lib.load(), entry)
+    assert fn(*args[:at], ops._p(scratch), ctypes.c_longlong(nb - 1), *args[at + 1:]) == -3
+    torch.cuda.synchronize()
+    assert bool((gw == 777.0).all())
+    ops.check_async_errors()
+
+
 def test_the_proxy_catches_an_out_of_bounds_store(ecm):
     """The fixture itself: a store one element past a guarded buffer is reported."""
     with guarded(ecm) as g:

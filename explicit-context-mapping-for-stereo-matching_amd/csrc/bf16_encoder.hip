@@ -140,15 +140,15 @@ extern "C" long long ecm_conv2d_bf16_packed_elems(int Ci, int Co, int k) {
 }
 
 extern "C" int ecm_conv2d_bf16_pack_weight(const float* w, unsigned short* packed, int Ci, int Co, int k, void* stream) {
-    ECM_CHECK_ARG(w && packed && Ci > 0 && Co > 0 && (k == 1 || k == 3));
-    if (Ci % KC != 0) return ECM_EUNSUP;
+    ECM_CHECK_ARG(w && packed && Ci > 0 && Co > 0);
+    if ((k != 1 && k != 3) || Ci % KC != 0) return ECM_EUNSUP;
     return pack_weight_2d(w, packed, Ci, Co, k * k, 0, stream);
 }
 
 extern "C" int ecm_conv2d_bf16_fwd(const unsigned short* x, const unsigned short* wpacked, void* y, int B, int Ci, int Co,
                                    int H, int W, int k, int stride, int dil, int out_f32, void* stream) {
-    ECM_CHECK_ARG(x && wpacked && y && B > 0 && Ci > 0 && Co > 0 && H > 0 && W > 0 && (k == 1 || k == 3)
-                  && (stride == 1 || stride == 2) && dil >= 1);
+    ECM_CHECK_ARG(x && wpacked && y && B > 0 && Ci > 0 && Co > 0 && H > 0 && W > 0);
+    if ((k != 1 && k != 3) || (stride != 1 && stride != 2) || dil < 1) return ECM_EUNSUP;
     if (Ci % KC != 0 || Co % 32 != 0) return ECM_EUNSUP;
     // element offsets inside one sample's planes stay 32-bit
     const long long Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;

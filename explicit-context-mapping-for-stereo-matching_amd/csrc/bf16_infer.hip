@@ -53,7 +53,8 @@ extern "C" int ecm_conv3d_bf16_pack_weight(const float* w, unsigned short* packe
 
 extern "C" int ecm_conv3d_k3_bf16_fwd(const unsigned short* x, const unsigned short* wpacked, unsigned short* y, int B, int Ci,
                                       int Co, int D, int H, int W, int stride, void* stream) {
-    ECM_CHECK_ARG(x && wpacked && y && B > 0 && Ci > 0 && Co > 0 && D > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2));
+    ECM_CHECK_ARG(x && wpacked && y && B > 0 && Ci > 0 && Co > 0 && D > 0 && H > 0 && W > 0);
+    if (stride != 1 && stride != 2) return ECM_EUNSUP;
     if (!conv_shape_ok(Ci, Co, D, H, W)) return ECM_EUNSUP;
     const int Do = (D - 1) / stride + 1, Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
     if ((long long)Co * Do * Ho * Wo * 2 >= 0x7fffffffLL) return ECM_EUNSUP;

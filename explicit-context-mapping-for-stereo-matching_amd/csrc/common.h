@@ -8,6 +8,11 @@
 
 #define ECM_CHECK_ARG(cond) do { if (!(cond)) return ECM_EINVAL; } while (0)
 #define ECM_LAUNCH_RESULT() ((int)hipGetLastError())
+// The head operands of every disparity-head entry, after its ECM_CHECK_ARG and before anything is sized by them: heads are packed
+// at c0 + head * head_stride, so a negative stride is a bad argument, and the kernels are built for one to three heads.
+#define ECM_CHECK_HEADS(head_stride, nheads) do { \
+    if ((head_stride) < 0) return ECM_EINVAL; \
+    if ((nheads) < 1 || (nheads) > 3) return ECM_EUNSUP; } while (0)
 
 static inline hipStream_t ecm_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 

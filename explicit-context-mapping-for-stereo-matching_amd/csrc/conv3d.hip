@@ -145,6 +145,7 @@ int launch_conv(const float* x, const float* wp, float* y, int B, int Ci, int Co
 }  // namespace
 
 extern "C" long long ecm_conv3d_packed_floats(int Ci, int Co) {
+    if (Ci <= 0 || Co <= 0) return 0;
     const long long cop = ((Co + 31) / 32) * 32;
     return 27LL * Ci * cop;
 }
@@ -161,7 +162,7 @@ extern "C" int ecm_conv3d_pack_weight(const float* w, float* packed, int Co, int
 
 extern "C" int ecm_conv3d_k3_fwd(const float* x, const float* wpacked, float* y, int B, int Ci, int Co, int D, int H,
                                  int W, int stride, void* stream) {
-    ECM_CHECK_ARG(x && wpacked && y && B > 0 && D > 0 && H > 0 && W > 0);
+    ECM_CHECK_ARG(x && wpacked && y && B > 0 && Ci > 0 && Co > 0 && D > 0 && H > 0 && W > 0);
     if (Ci % 4 != 0 || Co < 1 || Co > 64 || (stride != 1 && stride != 2)) return ECM_EUNSUP;
     hipStream_t st = ecm_stream(stream);
     const bool two = Co > 32;

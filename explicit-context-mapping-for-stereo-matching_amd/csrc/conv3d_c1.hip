@@ -536,14 +536,14 @@ int launch_c1_fwd_v(const T* x, const float* w, float* y, int B, int Ci, int D, 
 
 extern "C" int ecm_conv3d_c1_gn_fwd(const float* x, const float* mean_rstd, const float* gamma, const float* beta, const float* w,
                                     float* y, int B, int Ci, int D, int H, int W, void* stream) {
-    ECM_CHECK_ARG(x && mean_rstd && gamma && beta && w && y && B > 0 && D > 0 && H > 0 && W > 0);
+    ECM_CHECK_ARG(x && mean_rstd && gamma && beta && w && y && B > 0 && Ci > 0 && D > 0 && H > 0 && W > 0);
     if (Ci != 32 || (long long)D * H * W * 4 * 32 >= 0x7fffffffLL) return ECM_EUNSUP;      // one channel per GroupNorm group
     return launch_c1_fwd_v<true>(x, w, y, B, Ci, D, H, W, mean_rstd, gamma, beta, stream);
 }
 
 extern "C" int ecm_conv3d_c1_gn_fwd_bf16(const unsigned short* x, const float* mean_rstd, const float* gamma, const float* beta,
                                          const float* w, float* y, int B, int Ci, int D, int H, int W, void* stream) {
-    ECM_CHECK_ARG(x && mean_rstd && gamma && beta && w && y && B > 0 && D > 0 && H > 0 && W > 0);
+    ECM_CHECK_ARG(x && mean_rstd && gamma && beta && w && y && B > 0 && Ci > 0 && D > 0 && H > 0 && W > 0);
     if (Ci != 32 || (long long)D * H * W * 2 * 32 >= 0x7fffffffLL) return ECM_EUNSUP;
     return launch_c1_fwd_v<true, unsigned short>(x, w, y, B, Ci, D, H, W, mean_rstd, gamma, beta, stream);
 }
@@ -615,7 +615,7 @@ extern "C" int ecm_conv3d_c1_wgrad(const float* x, const float* gy, float* gw, v
 extern "C" int ecm_conv3d_c1_gn_wgrad(const float* x, const float* mean_rstd, const float* gamma, const float* beta, const float* gy,
                                       float* gw, void* scratch, long long scratch_bytes, int B, int Ci, int D, int H, int W,
                                       void* stream) {
-    ECM_CHECK_ARG(x && mean_rstd && gamma && beta && gy && gw && scratch && B > 0 && D > 0 && H > 0 && W > 0);
+    ECM_CHECK_ARG(x && mean_rstd && gamma && beta && gy && gw && scratch && B > 0 && Ci > 0 && D > 0 && H > 0 && W > 0);
     if (Ci != 32) return ECM_EUNSUP;
     return launch_c1_wgrad<true>(x, gy, gw, scratch, scratch_bytes, B, Ci, D, H, W, mean_rstd, gamma, beta, stream);
 }

@@ -543,6 +543,7 @@ extern "C" int ecm_conv2d_wgrad_ex(const float* x, const float* gy, float* gw, v
                                    int Ci, int Co, int H, int W, int kh, int kw, int stride, int dil, int pad_top,
                                    int pad_left, int Ho, int Wo, void* stream) {
     ECM_CHECK_ARG(x && gy && gw && scratch && B > 0 && Ci > 0 && Co > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0);
+    if (dil < 1) return ECM_EUNSUP;        // a negative dilation is wg2_select's wildcard, not a caller's value
     if ((long long)H * W * 4 * 32 >= 0x7fffffffLL || (long long)Ho * Wo * 4 * 32 >= 0x7fffffffLL) return ECM_EUNSUP;
     if (wg2_query_plan(B, Ci, Co, Ho, Wo, kh, kw, stride).ntiles >= 0x7fffffffLL) return ECM_EUNSUP;
     if (scratch_bytes < ecm_conv2d_wgrad_ex_scratch_bytes(B, Ci, Co, Ho, Wo, kh, kw, stride)) return ECM_ESCRATCH;

@@ -539,7 +539,8 @@ extern "C" long long ecm_conv_wino_packed_floats(int Ci, int Co, int kd) {
 }
 
 extern "C" int ecm_conv_wino_pack_weight(const float* w, float* packed, int Co, int Ci, int kd, int flip_transpose, void* stream) {
-    ECM_CHECK_ARG(w && packed && Co > 0 && Ci > 0 && (kd == 1 || kd == 3));
+    ECM_CHECK_ARG(w && packed && Co > 0 && Ci > 0);
+    if (kd != 1 && kd != 3) return ECM_EUNSUP;
     const int Kin = flip_transpose ? Co : Ci, Kout = flip_transpose ? Ci : Co;
     const int cic = kd == 3 ? WINO_CIC3 : WINO_CIC2;
     const int nchunks = (Kin + cic - 1) / cic;
@@ -550,7 +551,8 @@ extern "C" int ecm_conv_wino_pack_weight(const float* w, float* packed, int Co, 
 }
 
 extern "C" int ecm_conv_wino_pack_weight2(const float* w, float* packed, int Co, int Ci, int kd, void* stream) {
-    ECM_CHECK_ARG(w && packed && Co > 0 && Ci > 0 && (kd == 1 || kd == 3));
+    ECM_CHECK_ARG(w && packed && Co > 0 && Ci > 0);
+    if (kd != 1 && kd != 3) return ECM_EUNSUP;
     const int cic = kd == 3 ? WINO_CIC3 : WINO_CIC2;
     const long long nf = ecm_conv_wino_packed_floats(Ci, Co, kd), nb = ecm_conv_wino_packed_floats(Co, Ci, kd);
     hipLaunchKernelGGL(pack_wino_weight, dim3((unsigned)((nf + nb + 255) / 256)), dim3(256), 0, ecm_stream(stream), w, packed, Co, Ci,

@@ -312,7 +312,7 @@ __global__ __launch_bounds__(256) void class_weights_bwd(const float* __restrict
 
 extern "C" int ecm_costvol_conv_assemble_fwd(const float* P, const float* Qp, float* y, int B, int Co, int D, int h, int w,
                                              void* stream) {
-    ECM_CHECK_ARG(P && Qp && y && B > 0 && Co > 0 && h > 0 && w > 0);
+    ECM_CHECK_ARG(P && Qp && y && B > 0 && Co > 0 && D > 0 && h > 0 && w > 0);
     if (D < 2) return ECM_EUNSUP;
     const long long n = (long long)B * Co * D * h * w;
     hipStream_t st = ecm_stream(stream);
@@ -338,7 +338,7 @@ extern "C" int ecm_costvol_conv_assemble_fwd(const float* P, const float* Qp, fl
 
 extern "C" int ecm_costvol_conv_assemble_bwd(const float* gy, float* gP, float* gQp, int B, int Co, int D, int h, int w,
                                              void* stream) {
-    ECM_CHECK_ARG(gy && gP && gQp && B > 0 && Co > 0 && h > 0 && w > 0);
+    ECM_CHECK_ARG(gy && gP && gQp && B > 0 && Co > 0 && D > 0 && h > 0 && w > 0);
     if (D < 2) return ECM_EUNSUP;
     hipStream_t st = ecm_stream(stream);
     {

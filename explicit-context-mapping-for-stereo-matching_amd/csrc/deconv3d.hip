@@ -148,7 +148,7 @@ extern "C" int ecm_deconv3d_pack_weight(const float* w, float* packed, int Ci, i
 
 extern "C" int ecm_deconv3d_k3s2_fwd(const float* x, const float* wpacked, float* y, int B, int Ci, int Co, int D, int H,
                                      int W, int Do, int Ho, int Wo, void* stream) {
-    ECM_CHECK_ARG(x && wpacked && y && B > 0 && D > 0 && H > 0 && W > 0);
+    ECM_CHECK_ARG(x && wpacked && y && B > 0 && Ci > 0 && Co > 0 && D > 0 && H > 0 && W > 0 && Do > 0 && Ho > 0 && Wo > 0);
     // output extent per dim is 2n (output_padding 1) or 2n-1 (dgrad of a stride-2 conv on an odd extent)
     if (Ci % 4 != 0 || Co < 1 || Co > 64) return ECM_EUNSUP;
     if (Do > 2 * D || Do < 2 * D - 1 || Ho > 2 * H || Ho < 2 * H - 1 || Wo > 2 * W || Wo < 2 * W - 1) return ECM_EUNSUP;
@@ -169,7 +169,7 @@ extern "C" int ecm_deconv2d_pack_weight(const float* w, float* packed, int Ci, i
 
 extern "C" int ecm_deconv2d_k3s2_fwd(const float* x, const float* wpacked, float* y, int B, int Ci, int Co, int H, int W,
                                      int Ho, int Wo, void* stream) {
-    ECM_CHECK_ARG(x && wpacked && y && B > 0 && H > 0 && W > 0);
+    ECM_CHECK_ARG(x && wpacked && y && B > 0 && Ci > 0 && Co > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0);
     if (Ci % 4 != 0 || Co < 1 || Co > 64) return ECM_EUNSUP;
     if (Ho > 2 * H || Ho < 2 * H - 1 || Wo > 2 * W || Wo < 2 * W - 1) return ECM_EUNSUP;
     hipStream_t st = ecm_stream(stream);
@@ -181,7 +181,7 @@ extern "C" int ecm_deconv2d_k3s2_fwd(const float* x, const float* wpacked, float
 // the bias is added to the accumulators before the stores (no second pass over the full-resolution map)
 extern "C" int ecm_deconv2d_k3s2_bias_fwd(const float* x, const float* wpacked, const float* bias, float* y, int B, int Ci,
                                           int Co, int H, int W, int Ho, int Wo, void* stream) {
-    ECM_CHECK_ARG(x && wpacked && bias && y && B > 0 && H > 0 && W > 0);
+    ECM_CHECK_ARG(x && wpacked && bias && y && B > 0 && Ci > 0 && Co > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0);
     if (Ci % 4 != 0 || Co < 1 || Co > 64) return ECM_EUNSUP;
     if (Ho > 2 * H || Ho < 2 * H - 1 || Wo > 2 * W || Wo < 2 * W - 1) return ECM_EUNSUP;
     hipStream_t st = ecm_stream(stream);

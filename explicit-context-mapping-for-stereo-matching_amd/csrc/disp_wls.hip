@@ -222,6 +222,7 @@ inline bool positive(float v) { return v > 0.f && v < __builtin_inff(); }
 
 extern "C" long long ecm_disp_wls_scratch_bytes(int B, int H, int W) {
     if (B < 1 || H < 1 || W < 1) return ECM_EINVAL;
+    if ((long long)B * H * W > INT_MAX) return 0;                                  // what ecm_disp_wls_fwd answers ECM_EUNSUP
     return (long long)B * H * W * (long long)sizeof(float);                     // the c' plane
 }
 

@@ -149,7 +149,10 @@ inline int lds_floats(int s) {
 
 }  // namespace
 
-extern "C" long long ecm_weights9_scratch_bytes(int B, int h, int w) { return (long long)B * h * w * CF * 4; }
+extern "C" long long ecm_weights9_scratch_bytes(int B, int h, int w) {
+    if (B <= 0 || h <= 0 || w <= 0) return 0;
+    return (long long)B * h * w * CF * 4;
+}
 
 extern "C" int ecm_context_weights_fwd(const float* lr, const float* hr, const float* W0, const float* W1, const float* W2,
                                        const float* W3, float* out, void* scratch, long long scratch_bytes, int B, int h,

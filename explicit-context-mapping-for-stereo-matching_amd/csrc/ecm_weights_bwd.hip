@@ -712,7 +712,8 @@ extern "C" int ecm_context_weights_bwd(const float* lr, const float* hr, const f
                                        const float* W3, const float* out_saved, const float* gout, float* glr, float* ghr,
                                        float* gW, void* scratch, long long scratch_bytes, int B, int h, int w, int s,
                                        int variant, void* stream) {
-    ECM_CHECK_ARG(lr && hr && W0 && W1 && W2 && W3 && out_saved && gout && glr && ghr && gW && scratch && B > 0 && h > 0 && w > 0);
+    ECM_CHECK_ARG(lr && hr && W0 && W1 && W2 && W3 && out_saved && gout && glr && ghr && gW && scratch && B > 0 && h > 0 && w > 0 &&
+                  s > 0);
     if ((s != 4 && s != 8 && s != 16) || variant < 0 || variant > 2) return ECM_EUNSUP;    // the registered architectures' scales
     if (variant == 0 && s != 4) return ECM_EUNSUP;                                         // see ecm_context_weights_fwd
     const BwdPlan p = plan(B, h, w, s, planes_of(variant));

@@ -265,7 +265,7 @@ extern "C" int ecm_disp_to_u16(const float* pred, unsigned short* out, int B, in
 }
 
 extern "C" long long ecm_eval_kitti_scratch_bytes(int B, int H, int W) {
-    if (B < 1 || H < 1 || W < 1) return 0;
+    if (B < 1 || H < 1 || W < 1 || B > 65535 || (long long)H * W > 0x7fffffffLL) return 0;   // what ecm_eval_kitti refuses
     return kitti_part_bytes(B, (long long)H * W) + (long long)B * KP * (long long)sizeof(unsigned long long);
 }
 

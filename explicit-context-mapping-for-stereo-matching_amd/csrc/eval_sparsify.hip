@@ -337,6 +337,7 @@ extern "C" int ecm_eval_sparsify_max_steps(void) { return MAX_STEPS; }
 
 extern "C" long long ecm_eval_sparsify_scratch_bytes(int B, int H, int W, int K, int steps) {
     if (B < 1 || H < 1 || W < 1 || K < 1 || K > MAX_K || steps < 1 || steps > MAX_STEPS) return 0;
+    if (B > 65535 || (long long)H * W > 0x7fffffffLL) return 0;
     return (hist_words(B, K, steps) + (long long)B * (K + 1) * ST_WORDS) * (long long)sizeof(u64);
 }
 

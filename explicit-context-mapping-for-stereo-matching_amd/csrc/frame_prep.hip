@@ -95,7 +95,7 @@ int frame_prep_launch(Src src, float* left, float* right, float* disp, float* im
     } else if (mode == 1) {
         if (!(th >= H && tw >= W && th - H <= H && tw - W <= W)) return ECM_EINVAL;      // the pad repeats existing rows / columns
     } else {
-        return ECM_EINVAL;
+        return ECM_EUNSUP;
     }
     for (int b0 = 0; b0 < B; b0 += FP_MAXB) {
         const int nb = B - b0 < FP_MAXB ? B - b0 : FP_MAXB;

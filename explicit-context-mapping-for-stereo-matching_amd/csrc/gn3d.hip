@@ -869,6 +869,7 @@ int launch_apply(const TI* x, const float* mean_rstd, const float* gamma, const 
 }  // namespace
 
 extern "C" long long ecm_gn3d_scratch_bytes(int B, int C, long long S) {
+    if (B <= 0 || C <= 0 || C % GROUPS != 0 || S <= 0) return 0;              // what every GroupNorm entry refuses
     // max over: stats partials [B*32][chunks(cpg*S)][2], bwd partials [B*C][chunks(S)][2] + chan [B*C][2]
     const long long cpg = C / 32 > 0 ? C / 32 : 1;
     const long long a = (long long)B * 32 * chunks_of(cpg * S) * 2;

@@ -178,7 +178,8 @@ __global__ __launch_bounds__(256) void aggregate9_mode_fwd(const float* __restri
 extern "C" int ecm_aggregate9_mode_fwd(const float* c0, long long head_stride, const float* lse, const float* w9, float* modal,
                                        int nheads, int B, int D, int h, int w, int s, int radius, void* stream) {
     ECM_CHECK_ARG(c0 && lse && w9 && modal && B > 0 && D > 0 && h > 0 && w > 0 && s > 0 && radius >= 0 && radius % s == 0);
-    if (nheads < 1 || nheads > 3 || B > 65535) return ECM_EUNSUP;     // nheads sizes the LDS below
+    ECM_CHECK_HEADS(head_stride, nheads);                            // nheads sizes the LDS below
+    if (B > 65535) return ECM_EUNSUP;
     const int ncol = span_cells(TX, s) * span_cells(TY, s);
     // the levels that fit beside S, L and Kc; at s = 4: 54 columns, 48 levels x 3 heads = 31,104 B + 1,944 B
     const int dc = min(min(D, DC_MAX), (LDS_BUDGET / (int)sizeof(float) - 3 * nheads * ncol) / (nheads * ncol));

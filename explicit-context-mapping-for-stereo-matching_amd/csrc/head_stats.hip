@@ -102,6 +102,7 @@ __global__ __launch_bounds__(256) void aggregate9_stats_fwd(const float* __restr
 extern "C" int ecm_aggregate9_stats_fwd(const float* c0, long long head_stride, const float* lse, const float* w9,
                                         float* stats, int nheads, int B, int D, int h, int w, int s, void* stream) {
     ECM_CHECK_ARG(c0 && lse && w9 && stats && B > 0 && D > 0 && h > 0 && w > 0 && s > 0);
+    ECM_CHECK_HEADS(head_stride, nheads);
     const long long n = (long long)B * h * s * w * s;
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
     return ecm_dispatch_heads(nheads, [&](auto nh) {

@@ -210,18 +210,21 @@ static int launch_softargmin_fwd(const float* c0, long long head_stride, float* 
 extern "C" int ecm_softargmin_heads_fwd(const float* c0, long long head_stride, float* disp, int nheads, int B, int D,
                                         int hw, void* stream) {
     ECM_CHECK_ARG(c0 && disp && B > 0 && D > 0 && hw > 0);
+    ECM_CHECK_HEADS(head_stride, nheads);
     return launch_softargmin_fwd(c0, head_stride, disp, nullptr, nheads, B, D, hw, stream);
 }
 
 extern "C" int ecm_softargmin_heads_lse_fwd(const float* c0, long long head_stride, float* disp, float* lse, int nheads,
                                             int B, int D, int hw, void* stream) {
     ECM_CHECK_ARG(c0 && disp && lse && B > 0 && D > 0 && hw > 0);
+    ECM_CHECK_HEADS(head_stride, nheads);
     return launch_softargmin_fwd(c0, head_stride, disp, lse, nheads, B, D, hw, stream);
 }
 
 extern "C" int ecm_softargmin_heads_bwd(const float* c0, long long head_stride, const float* gdisp, float* gc0,
                                         int nheads, int B, int D, int hw, void* stream) {
     ECM_CHECK_ARG(c0 && gdisp && gc0 && B > 0 && D > 0 && hw > 0);
+    ECM_CHECK_HEADS(head_stride, nheads);
     const long long n = (long long)B * hw;
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
     return ecm_dispatch_heads(nheads, [&](auto nh) {
@@ -242,6 +245,7 @@ extern "C" int ecm_disparity_regression_fwd(const float* x, float* out, int B, i
 extern "C" int ecm_aggregate9_fwd(const float* d, const float* w9, float* out, int nheads, int B, int h, int w, int s,
                                   void* stream) {
     ECM_CHECK_ARG(d && w9 && out && B > 0 && h > 0 && w > 0 && s > 0);
+    if (nheads < 1 || nheads > 3) return ECM_EUNSUP;
     const long long n = (long long)B * h * s * w * s;
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
     return ecm_dispatch_heads(nheads, [&](auto nh) {
@@ -253,6 +257,7 @@ extern "C" int ecm_aggregate9_fwd(const float* d, const float* w9, float* out, i
 extern "C" int ecm_aggregate9_bwd(const float* d, const float* w9, const float* gout, float* gd, float* gw9,
                                   int nheads, int B, int h, int w, int s, void* stream) {
     ECM_CHECK_ARG(d && w9 && gout && gd && gw9 && B > 0 && h > 0 && w > 0 && s > 0);
+    if (nheads < 1 || nheads > 3) return ECM_EUNSUP;
     const long long n = (long long)B * h * s * w * s;
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
     const long long cells = (long long)B * h * w;

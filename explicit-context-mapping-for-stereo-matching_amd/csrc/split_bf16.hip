@@ -104,7 +104,7 @@ extern "C" int ecm_conv3d_k3s2_split_fwd(const float* x, const unsigned short* w
 
 extern "C" int ecm_deconv3d_k3s2_split_fwd(const float* x, const unsigned short* wpacked, float* y, int B, int Ci, int Co, int D,
                                            int H, int W, int Do, int Ho, int Wo, void* stream) {
-    ECM_CHECK_ARG(x && wpacked && y && B > 0 && Ci > 0 && Co > 0 && D > 0 && H > 0 && W > 0);
+    ECM_CHECK_ARG(x && wpacked && y && B > 0 && Ci > 0 && Co > 0 && D > 0 && H > 0 && W > 0 && Do > 0 && Ho > 0 && Wo > 0);
     // output extent per dim is 2n (output_padding 1) or 2n-1 (dgrad of a stride-2 conv on an odd extent)
     if (Do > 2 * D || Do < 2 * D - 1 || Ho > 2 * H || Ho < 2 * H - 1 || Wo > 2 * W || Wo < 2 * W - 1) return ECM_EUNSUP;
     if (!split_shape_ok(Ci, Co, (long long)D * H * W, (long long)Do * Ho * Wo)) return ECM_EUNSUP;

@@ -669,6 +669,7 @@ static int launch_trilinear_fwd(const float* c0, long long head_stride, float* d
 extern "C" int ecm_volume_mapping_fwd(const float* c0, long long head_stride, const float* m5, const float* mt3,
                                       float* disp, int nheads, int B, int Dl, int h, int w, int s, void* stream) {
     ECM_CHECK_ARG(c0 && m5 && mt3 && disp && B > 0 && Dl > 0 && h > 0 && w > 0 && s > 0);
+    ECM_CHECK_HEADS(head_stride, nheads);
     return launch_volume_mapping_fwd(c0, head_stride, m5, mt3, disp, nullptr, nheads, B, Dl, h, w, s, -1, stream);
 }
 
@@ -676,6 +677,7 @@ extern "C" int ecm_volume_mapping_stats_fwd(const float* c0, long long head_stri
                                             float* disp, float* stats, int nheads, int B, int Dl, int h, int w, int s,
                                             void* stream) {
     ECM_CHECK_ARG(c0 && m5 && mt3 && disp && stats && B > 0 && Dl > 0 && h > 0 && w > 0 && s > 0);
+    ECM_CHECK_HEADS(head_stride, nheads);
     return launch_volume_mapping_fwd(c0, head_stride, m5, mt3, disp, stats, nheads, B, Dl, h, w, s, -1, stream);
 }
 
@@ -685,18 +687,21 @@ extern "C" int ecm_volume_mapping_mode_fwd(const float* c0, long long head_strid
                                            float* modal, int nheads, int B, int Dl, int h, int w, int s, int radius,
                                            void* stream) {
     ECM_CHECK_ARG(c0 && m5 && mt3 && modal && B > 0 && Dl > 0 && h > 0 && w > 0 && s > 0 && radius >= 0);
+    ECM_CHECK_HEADS(head_stride, nheads);
     return launch_volume_mapping_fwd(c0, head_stride, m5, mt3, nullptr, modal, nheads, B, Dl, h, w, s, radius, stream);
 }
 
 extern "C" int ecm_trilinear_softargmin_mode_fwd(const float* c0, long long head_stride, float* modal, int nheads, int B,
                                                  int Dl, int h, int w, int Do, int H, int W, int radius, void* stream) {
     ECM_CHECK_ARG(c0 && modal && B > 0 && Dl > 0 && h > 0 && w > 0 && Do > 0 && H > 0 && W > 0 && radius >= 0);
+    ECM_CHECK_HEADS(head_stride, nheads);
     return launch_trilinear_fwd(c0, head_stride, nullptr, modal, nheads, B, Dl, h, w, Do, H, W, radius, stream);
 }
 
 extern "C" int ecm_trilinear_softargmin_fwd(const float* c0, long long head_stride, float* disp, int nheads, int B, int Dl,
                                             int h, int w, int Do, int H, int W, void* stream) {
     ECM_CHECK_ARG(c0 && disp && B > 0 && Dl > 0 && h > 0 && w > 0 && Do > 0 && H > 0 && W > 0);
+    ECM_CHECK_HEADS(head_stride, nheads);
     return launch_trilinear_fwd(c0, head_stride, disp, nullptr, nheads, B, Dl, h, w, Do, H, W, -1, stream);
 }
 
@@ -704,11 +709,13 @@ extern "C" int ecm_trilinear_softargmin_stats_fwd(const float* c0, long long hea
                                                   int nheads, int B, int Dl, int h, int w, int Do, int H, int W,
                                                   void* stream) {
     ECM_CHECK_ARG(c0 && disp && stats && B > 0 && Dl > 0 && h > 0 && w > 0 && Do > 0 && H > 0 && W > 0);
+    ECM_CHECK_HEADS(head_stride, nheads);
     return launch_trilinear_fwd(c0, head_stride, disp, stats, nheads, B, Dl, h, w, Do, H, W, -1, stream);
 }
 
 extern "C" long long ecm_volume_mapping_bwd_scratch_bytes(int nheads, int B, int Dl, int h, int w, int s) {
-    if (nheads <= 0 || B <= 0 || Dl <= 0 || h <= 0 || w <= 0 || s <= 0) return 0;
+    if (nheads <= 0 || nheads > 3 || B <= 0 || Dl <= 0 || h <= 0 || w <= 0 || s <= 0) return 0;
+    if ((s & (s - 1)) != 0 || s > 64) return 0;                   // what ecm_volume_mapping_bwd refuses
     return (long long)nheads * B * Dl * h * s * 5 * w * (long long)sizeof(float);
 }
 
@@ -716,6 +723,7 @@ extern "C" int ecm_volume_mapping_bwd(const float* c0, long long head_stride, co
                                       const float* gdisp, float* gc0, float* gm5, float* gmt3, void* scratch,
                                       long long scratch_bytes, int nheads, int B, int Dl, int h, int w, int s, void* stream) {
     ECM_CHECK_ARG(c0 && m5 && mt3 && gdisp && gc0 && gm5 && gmt3 && scratch && B > 0 && Dl > 0 && h > 0 && w > 0 && s > 0);
+    ECM_CHECK_HEADS(head_stride, nheads);
     if ((s & (s - 1)) != 0 || s > 64) return ECM_EUNSUP;          // cell lanes are reduced with xor-shuffles inside a wave
     if (scratch_bytes < ecm_volume_mapping_bwd_scratch_bytes(nheads, B, Dl, h, w, s)) return ECM_ESCRATCH;
     hipStream_t st = ecm_stream(stream);
@@ -737,7 +745,7 @@ extern "C" int ecm_volume_mapping_bwd(const float* c0, long long head_stride, co
 }
 
 extern "C" long long ecm_trilinear_softargmin_bwd_scratch_bytes(int nheads, int B, int Dl, int h, int w, int H, int W) {
-    if (nheads <= 0 || B <= 0 || Dl <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return 0;
+    if (nheads <= 0 || nheads > 3 || B <= 0 || Dl <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return 0;
     return (long long)nheads * B * Dl * H * ((long long)W + w) * (long long)sizeof(float);
 }
 
@@ -745,6 +753,7 @@ extern "C" int ecm_trilinear_softargmin_bwd(const float* c0, long long head_stri
                                             void* scratch, long long scratch_bytes, int nheads, int B, int Dl, int h, int w,
                                             int Do, int H, int W, void* stream) {
     ECM_CHECK_ARG(c0 && gdisp && gc0 && scratch && B > 0 && Dl > 0 && h > 0 && w > 0 && Do > 0 && H > 0 && W > 0);
+    ECM_CHECK_HEADS(head_stride, nheads);
     if (scratch_bytes < ecm_trilinear_softargmin_bwd_scratch_bytes(nheads, B, Dl, h, w, H, W)) return ECM_ESCRATCH;
     hipStream_t st = ecm_stream(stream);
     float* S = static_cast<float*>(scratch);

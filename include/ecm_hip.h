@@ -10,6 +10,13 @@
  *     enqueued asynchronously on it;
  *   - return 0 on success, a negative ECM_E* code on a bad argument, or the positive
  *     hipError_t of a failed launch; no exceptions cross the ABI;
+ *   - which negative code: ECM_EINVAL for a null pointer (unless the entry says it may be NULL) and for a size, count or extent
+ *     that is zero or negative, and for arguments that contradict each other (a window outside its frame); ECM_EUNSUP for a
+ *     positive value that the kernels are not built for, and for ANY value of a stride, dilation, kernel size (kd, k; kh, kw of
+ *     the convolutions), head count, variant or mode outside the set its entry names, zero and negative ones included: these
+ *     select a kernel, they do not size one; ECM_ESCRATCH for a scratch buffer below the entry's size query.  Every refusal
+ *     is answered on the host, before any device work, and a size query answers 0 for the sizes its entry refuses
+ *     (tests/test_abi_refusals.py holds all of this for every entry, without a device);
  *   - re-entrant; the only process-wide state is the sticky asynchronous-error word (ecm_async_status) and the
  *     GroupNorm cluster mode (ecm_gn3d_cluster_mode), both documented below.
  *
@@ -45,7 +52,7 @@ int ecm_costvol_concat_bwd(const float* gcost, float* gL, float* gR,
 /* ---- a8: soft-argmin over D (cmfsm.py:703-706 + disparityregression 111-123) -----------------
  * Fused three-head form: logits_k = sum_{j<=k} c_j (cmfsm.py:725,748), disp[k] = sum_d softmax_d(logits_k)*d.
  * c: nheads pointers' worth of [B,D,h*w] raw classifier outputs packed as c[head] = c0 + head*head_stride.
- * disp: [nheads,B,h*w].  nheads in 1..3. */
+ * disp: [nheads,B,h*w].  nheads in 1..3, else ECM_EUNSUP; head_stride >= 0, else ECM_EINVAL: so for every entry that takes them. */
 int ecm_softargmin_heads_fwd(const float* c0, long long head_stride, float* disp,
                              int nheads, int B, int D, int hw, void* stream);
 /* gc[head] (same packing as c) from gdisp [nheads,B,hw]; recomputes the softmax. */
@@ -101,13 +108,15 @@ int ecm_weights9_bwd(const float* lr, const float* hr, const float* W0, const fl
 /* ---- a4: six-related context mapping (cmfsm_sub_8.py:440-572; same text in cmfsm_sub_16.py, cm_sub_4/8/16.py) and the
  * general form of a3.  variant 0: eight_related (9 planes, softmax; == ecm_weights9_fwd); variant 1: six_related on the
  * reference image (5 planes c,r,l,t,b; zero padding; extra LeakyReLU; output softmax*logit); variant 2: six_related on
- * the target image (3 planes c,r,l).  out: [B,N,H,W], N = 9/5/3.  Any even scale s. */
+ * the target image (3 planes c,r,l).  out: [B,N,H,W], N = 9/5/3.  Any even scale s for variants 1 and 2; variant 0 is built for
+ * s = 4 (ECM_EUNSUP otherwise, as for an odd s or a variant outside 0..2).  scratch: ecm_weights9_scratch_bytes(B,h,w) bytes. */
 int ecm_context_weights_fwd(const float* lr, const float* hr, const float* W0, const float* W1, const float* W2,
                             const float* W3, float* out, void* scratch, long long scratch_bytes,
                             int B, int h, int w, int s, int variant, void* stream);
 
 /* Backward of ecm_context_weights_fwd for any variant and any scale with s % 4 == 0.  out_saved = the forward output
- * (used by variant 0; variants 1/2 recompute their logits).  gW = [gW0(2112) | gW1(512) | gW2(128) | gW3(8)] floats. */
+ * (used by variant 0; variants 1/2 recompute their logits).  gW = [gW0(2112) | gW1(512) | gW2(128) | gW3(8)] floats.
+ * s <= 0: ECM_EINVAL; any other s outside {4, 8, 16}: ECM_EUNSUP, and the size query answers 0. */
 long long ecm_context_weights_bwd_scratch_bytes(int B, int h, int w, int s, int variant);
 int ecm_context_weights_bwd(const float* lr, const float* hr, const float* W0, const float* W1, const float* W2,
                             const float* W3, const float* out_saved, const float* gout,
@@ -165,7 +174,7 @@ long long ecm_conv3d_packed_floats(int Ci, int Co);
 int ecm_conv3d_pack_weight(const float* w, float* packed, int Co, int Ci, int flip_transpose, void* stream);
 
 /* y[b,co,od,oh,ow] = sum w[co,ci,kd,kh,kw] x[b,ci,od*st+kd-1,oh*st+kh-1,ow*st+kw-1]; k=3, pad=1, st in {1,2}.
- * x: [B,Ci,D,H,W]; y: [B,Co,Do,Ho,Wo] with Do=(D-1)/st+1 etc.  Ci % 4 == 0; 1 <= Co <= 64. */
+ * x: [B,Ci,D,H,W]; y: [B,Co,Do,Ho,Wo] with Do=(D-1)/st+1 etc.  Ci % 4 == 0; 1 <= Co <= 64 (ECM_EUNSUP; Ci, Co <= 0: ECM_EINVAL). */
 int ecm_conv3d_k3_fwd(const float* x, const float* wpacked, float* y,
                       int B, int Ci, int Co, int D, int H, int W, int stride, void* stream);
 
@@ -185,7 +194,8 @@ int ecm_conv_wino_fwd(const float* x, const float* upacked, float* y, int B, int
                       void* stream);
 /* out = ((a + b) + c) + d elementwise over n floats, c and d optional (NULL): the gradient accumulation of a tensor with
  * several consumers in one pass (cmfsm.py:686-693: cost0 feeds the first hourglass and three residual adds) instead of
- * autograd's chain of binary adds.  16-byte aligned pointers; out may alias an input. */
+ * autograd's chain of binary adds.  d only together with c (d without c: ECM_EINVAL).  16-byte aligned pointers (ECM_EUNSUP
+ * otherwise); out may alias an input. */
 int ecm_sum_n(const float* a, const float* b, const float* c, const float* d, float* out, long long n, void* stream);
 /* out [planes,H,W] = small [planes,Hs,Ws] on the even positions, 0 elsewhere: the data gradient of a 1x1 / stride-2 projection
  * (the encoder's downsample layers) once W^T gy exists on the coarse grid. */
@@ -214,7 +224,8 @@ int ecm_conv3d_c1_wgrad(const float* x, const float* gy, float* gw, void* scratc
                         int B, int Ci, int D, int H, int W, void* stream);
 /* ABI 4: the whole tail of a classifier, GroupNorm(32) + ReLU + Conv3d(32 -> 1) (cmfsm.py:621-634: classifN[0][1], [1], [2]),
  * with the normalisation applied while x is staged: x is the RAW output of classifN[0][0] and mean_rstd [B,32,2] its group
- * statistics from ecm_gn3d_stats; h = relu(gn(x)) is never written.  Ci must be 32 (one channel per group).  fwd: y [B,1,D,H,W];
+ * statistics from ecm_gn3d_stats; h = relu(gn(x)) is never written.  Ci must be 32 (one channel per group; any other positive Ci:
+ * ECM_EUNSUP).  fwd: y [B,1,D,H,W];
  * wgrad: gw [1,32,27] = sum gy (x) h.  The data gradient w.r.t. h is ecm_conv3d_c1_dgrad, the GroupNorm backward
  * ecm_gn3d_bwd with y == NULL (ReLU mask recomputed from x). */
 int ecm_conv3d_c1_gn_fwd(const float* x, const float* mean_rstd, const float* gamma, const float* beta, const float* w,
@@ -225,7 +236,8 @@ int ecm_conv3d_c1_gn_wgrad(const float* x, const float* mean_rstd, const float* 
 /* ConvTranspose3d k=3, stride 2, pad 1, output_padding 1 (cmfsm.py:262-281): x [B,Ci,D,H,W] -> y [B,Co,Do,Ho,Wo],
  * Do = 2D (or 2D-1 when used as the data gradient of a stride-2 conv over an odd extent).
  * Weight in the reference layout [Ci,Co,3,3,3]; a Conv3d weight [Co_f,Ci_f,27] is the same memory layout
- * for its own data gradient (Ci := Co_f, Co := Ci_f).  packed: 27*Ci*CoP floats. */
+ * for its own data gradient (Ci := Co_f, Co := Ci_f).  packed: 27*Ci*CoP floats.  Ci % 4 == 0 and Co <= 64, and every output
+ * extent 2n or 2n-1, else ECM_EUNSUP; a zero or negative Ci, Co or extent: ECM_EINVAL.  So for the 2-D deconvolutions below. */
 int ecm_deconv3d_pack_weight(const float* w, float* packed, int Ci, int Co, void* stream);
 int ecm_deconv3d_k3s2_fwd(const float* x, const float* wpacked, float* y,
                           int B, int Ci, int Co, int D, int H, int W, int Do, int Ho, int Wo, void* stream);
@@ -250,7 +262,9 @@ int ecm_conv2d_pack_weight_ex(const float* w, float* packed, int Co, int Ci, int
 int ecm_conv2d_fwd_ex(const float* x, const float* wpacked, float* y, int B, int Ci, int Co, int H, int W, int kh, int kw,
                       int stride, int dil, int pad_top, int pad_left, int Ho, int Wo, void* stream);
 /* gw[co,ci,kh,kw] = sum_{b,oh,ow} gy[b,co,oh,ow] x[b,ci,oh*stride - pad_top + i*dil, ow*stride - pad_left + j*dil] for the
- * same family; gy: [B,Co,Ho,Wo].  Deterministic (per-workgroup partials, fixed-order sum). */
+ * same family; gy: [B,Co,Ho,Wo].  Deterministic (per-workgroup partials, fixed-order sum).  The size
+ * query also answers outside the family (with the caller's kh * kw taps): there a short scratch is ECM_ESCRATCH and, with room,
+ * the call ECM_EUNSUP. */
 long long ecm_conv2d_wgrad_ex_scratch_bytes(int B, int Ci, int Co, int Ho, int Wo, int kh, int kw, int stride);
 int ecm_conv2d_wgrad_ex(const float* x, const float* gy, float* gw, void* scratch, long long scratch_bytes, int B, int Ci,
                         int Co, int H, int W, int kh, int kw, int stride, int dil, int pad_top, int pad_left, int Ho, int Wo,
@@ -283,7 +297,7 @@ int ecm_conv2d_c1_wgrad(const float* x, const float* gy, const float* y, float* 
                         long long scratch_bytes, int B, int Ci, int H, int W, void* stream);
 
 /* GroupNorm(32 groups, eps) over [B,C,S] (S = D*H*W), cmfsm.py:58; deterministic fixed-order reductions.
- * scratch for every call: >= ecm_gn3d_scratch_bytes(B,C,S).
+ * scratch for every call: >= ecm_gn3d_scratch_bytes(B,C,S) (0 for sizes the entries refuse: C % 32 != 0 is ECM_EUNSUP).
  * fwd: y = relu?( (x-mean)*rstd*gamma[c]+beta[c] (+ skip) ) (skip may be NULL) and mean_rstd [B,32,2] in ONE pass over x
  *      (a cluster of co-resident workgroups keeps the span in registers across the reduction); shapes that do not fit
  *      that kernel run the two-stage forward below. */
@@ -373,7 +387,8 @@ int ecm_gn3d_bwd_p(const float* x, const float* mean_rstd, const float* gamma, c
  *   Qp[b, classQ, co, y, u+2]  classQ(d,x) = edge(d)*2 + (x == w-1), u = x-d         6 classes, target-image half (3x5)
  *   edge(d) = 0 / 1 / 2 for d == 0 / interior / d == D-1
  * fwd: y[B,Co,D,h,w] = P[classP(d,x)][x] + Qp[classQ(d,x)][x-d+2] where d-x < 3, else 0.
- * bwd: gP [B,15,Co,h,w], gQp [B,6,Co,h,w+2] = sums of gy over the d of each class (adjoint of fwd).  D >= 2. */
+ * bwd: gP [B,15,Co,h,w], gQp [B,6,Co,h,w+2] = sums of gy over the d of each class (adjoint of fwd).  D >= 2 (D = 1: ECM_EUNSUP;
+ * D <= 0: ECM_EINVAL). */
 int ecm_costvol_conv_assemble_fwd(const float* P, const float* Qp, float* y, int B, int Co, int D, int h, int w, void* stream);
 int ecm_costvol_conv_assemble_bwd(const float* gy, float* gP, float* gQp, int B, int Co, int D, int h, int w, void* stream);
 

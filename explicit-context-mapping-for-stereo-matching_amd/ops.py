@@ -297,6 +297,7 @@ def costvol_conv3d(left, right, weight, ndisp):
     2-D convolutions of the two feature maps (3x3 on `left`, sheared 3x5 on `right`) -- see csrc/costvol_conv.hip.
     weight: [Co, 2C, 3, 3, 3] (the reference's dres0[0][0].weight)."""
     _AGG.guard("costvol_conv3d")
+    _chk(left, right, weight)                  # before ClassWeights launches anything
     _need(left.dim() == 4 and right.shape == left.shape and weight.dim() == 5,
           lambda: f"costvol_conv3d: left {tuple(left.shape)}, right {tuple(right.shape)}, weight {tuple(weight.shape)}")
     Cc = left.shape[1]
@@ -1082,6 +1083,7 @@ class Fork(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, n):
+        _chk(x)                                # backward hands the gradients' addresses to ecm_sum_n as fp32
         ctx.set_materialize_grads(False)
         return tuple(x.view_as(x) for _ in range(n))
 
@@ -1115,6 +1117,7 @@ class ForkHead(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, n):
+        _chk(x)
         ctx.n = n
         ctx.set_materialize_grads(False)
         return x.view_as(x), x[:n]

@@ -39,8 +39,8 @@ def ecm():
     return ecm_amd
 
 
-def check_arguments(name, args, argtypes, tensors, problems):
-    """Append to `problems` what is wrong with `args` as the arguments of entry point `name`."""
+def check_arguments(name, args, argtypes, tensors, problems, census=True):
+    """Append to `problems` what is wrong with `args` as the arguments of entry point `name`.  census: feed INT_MAX."""
     if len(args) != len(argtypes):
         problems.append(f"{name}: {len(args)} arguments for {len(argtypes)} parameters")
         return
@@ -51,7 +51,7 @@ def check_arguments(name, args, argtypes, tensors, problems):
                 problems.append(f"{at}: c_int takes a plain int, got {type(v).__name__} {v!r}")
             elif not -2 ** 31 <= v < 2 ** 31:
                 problems.append(f"{at}: {v} does not fit a c_int")
-            elif v > INT_MAX.get(name, (-1, 0))[0]:
+            elif census and v > INT_MAX.get(name, (-1, 0))[0]:
                 INT_MAX[name] = (v, i)
         elif t is C.c_longlong:
             w = v.value if type(v) is C.c_longlong else v
@@ -80,25 +80,33 @@ def check_arguments(name, args, argtypes, tensors, problems):
 
 
 @contextlib.contextmanager
-def recording(ecm, case, table=None):
+def recording(ecm, case, table=None, census=True, strict=False):
     """Wrap _lib.call and _lib.query (and ops._p / ops._c, to know which addresses are tensors and which were promised
     aligned) for the block; on exit every recorded call has been checked and the device has reported no asynchronous error.
     table: the table of _lib.TABLES whose calls are recorded and checked (default PROTOTYPES); a name of another table passes
-    through, a name of none is a problem.  Only PROTOTYPES feeds this module's closing test (RECORDED, CASES, INT_MAX)."""
+    through, a name of none is a problem.  Only PROTOTYPES feeds this module's closing test (RECORDED, CASES, INT_MAX).
+    census=False: the block is another module's (tests/test_hip_autograd_contract.py): RECORDED, CASES and INT_MAX are left alone,
+    strict=True: a call whose arguments have a problem
+    raises AssertionError, with the argument named, BEFORE it is forwarded -- nothing is launched on a bad pointer."""
     lib, ops = ecm._lib, ecm.ops
     table = lib.PROTOTYPES if table is None else table
-    own = table is lib.PROTOTYPES
+    own = census and table is lib.PROTOTYPES
     real_call, real_query, real_p, real_c = lib.call, lib.query, ops._p, ops._c
     calls, problems, tensors, aligned = [], [], {}, set()
 
     def record(name, args):
         if name in table:
             calls.append(name)
-            check_arguments(name, args, table[name][1], tensors, problems)
-            if not own:
+            seen = len(problems)
+            check_arguments(name, args, table[name][1], tensors, problems, census)
+            if census and not own:
                 INT_MAX.pop(name, None)                            # the table of largest ints is about this module's cases
+            if strict and len(problems) > seen:
+                raise AssertionError(f"{case}: refused before the call:\n" + "\n".join(problems[seen:]))
         elif not any(name in t for t, _ in lib.TABLES.values()):
             problems.append(f"{name}: in no table")
+            if strict:
+                raise AssertionError(f"{case}: {problems[-1]}")
 
     def call(name, *args):
         record(name, args)

@@ -1247,3 +1247,63 @@ class StereoRig:
         else:
             left, right = self(left_raw, right_raw)
         return model.point_cloud(left, right, self.Q, colors=colors, source=source, **stage_args)
+
+
+# What DisparityTracker returns, each field [B,1,H,W]: this frame's own disparity and std, bit for bit; the
+# previous state warped into this frame (zeros where it starts over); and the new state: the fused disparity, its variance and
+# the number of frames it has been measured over (int32).
+Tracked = collections.namedtuple("Tracked", "disparity std warped fused variance age")
+
+
+class DisparityTracker:
+    """Disparity carried from frame to frame by the camera's known motion: per call one model.predict for
+    the disparity and std of `head` (for the architectures whose predict raises NotImplementedError, one plain forward and the
+    constant std sigma0), ops.disparity_warp of the state by ops.warp_matrix(Q, motion) with the planes (variance, disparity, age)
+    as attributes -- age travels as a float plane, exact below 2^24 -- and ops.disparity_fuse(disparity, std^2, warped state,
+    gate, process_noise, coast) with the pre-warp disparity as prev_source; (fused, variance, age) is the next call's state.
+    motion (float64 CPU [4,4] or [B,4,4]) takes points of the previous left-camera frame to this one, in the unit of Q's baseline;
+    motion=None, a first call, a changed shape and reset() start over: warped is zeros and the state is this frame's own.  A plain
+    object without parameters, not a module; it changes nothing in the model.  A static-scene model: a moving object is caught by
+    the gate alone; "cover" thickens foreground edges by up to a pixel; the defaults of gate, process_noise and sigma0 are
+    untested for quality, and nobody has measured the effect on EPE, D1 or temporal stability."""
+
+    def __init__(self, model, Q, head=2, gate=3.0, process_noise=0.01, sigma0=1.0, footprint="cover", coast=True):
+        if not isinstance(model, _ECMNet):
+            raise ValueError(f"DisparityTracker: model {type(model).__name__}: one of the registered architectures")
+        if isinstance(head, bool) or not isinstance(head, numbers.Integral) or not 0 <= head <= 2:
+            raise ValueError(f"DisparityTracker: head {head!r}: one of 0, 1, 2")
+        ops.warp_matrix(Q, torch.eye(4, dtype=torch.float64))              # Q's own refusals, a singular Q among them
+        self.gate, self.process_noise, _ = ops.check_fuse_parameters(gate, process_noise, coast, "DisparityTracker")
+        self.sigma0 = ops._real("DisparityTracker", "sigma0", sigma0, "> 0", fp32=True)
+        if footprint not in ops.WARP_FOOTPRINTS:
+            raise ValueError(f"DisparityTracker: footprint {footprint!r}: one of {ops.WARP_FOOTPRINTS}")
+        self.model, self.Q, self.head, self.footprint, self.coast = model, Q.detach().clone(), int(head), footprint, coast
+        self._state = None
+
+    def reset(self):
+        """Forget the state: the next call starts over."""
+        self._state = None
+
+    def __call__(self, left, right, motion=None):
+        M = None if motion is None else ops.warp_matrix(self.Q, motion)    # ValueError before any device work
+        with torch.no_grad():
+            if self.model.HEAD in _NO_DISTRIBUTION:
+                disparity = self.model(left, right)[self.head]
+                if disparity.dim() == 3:
+                    disparity = disparity.unsqueeze(1)
+                std = torch.full_like(disparity, self.sigma0)
+            else:
+                p = self.model.predict(left, right, (self.head,))
+                disparity, std = p.disparity[0], p.std[0]
+            state = self._state
+            if M is None or state is None or state[0].shape != disparity.shape or state[0].device != disparity.device:
+                warped, prev_var, prev_source = (torch.zeros_like(disparity) for _ in range(3))
+                prev_age = torch.zeros_like(disparity, dtype=torch.int32)
+            else:
+                fused, variance, age = state
+                warped, carried = ops.disparity_warp(fused, M, attributes=torch.cat([variance, fused, age.to(torch.float32)], 1),
+                                                     footprint=self.footprint)
+                prev_var, prev_source, prev_age = carried[:, 0:1], carried[:, 1:2], carried[:, 2:3].to(torch.int32)
+            self._state = ops.disparity_fuse(disparity, std * std, warped, prev_var, prev_age, prev_source, self.gate,
+                                             self.process_noise, self.coast)
+        return Tracked(disparity, std, warped, *self._state)

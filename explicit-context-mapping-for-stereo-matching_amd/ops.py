@@ -886,17 +886,18 @@ def q_matrix(focal, baseline, cx, cy, cx_right=None, x0=0, y0=0):
                          [0.0, 0.0, 1.0 / b, (float(vals["cx_right"]) - float(cx)) / b]], dtype=torch.float64)
 
 
-def check_reproject_parameters(Q, min_disp=0.0, max_disp=None, n_attributes=0, who="disparity_reproject"):
+def check_reproject_parameters(Q, min_disp=0.0, max_disp=None, n_attributes=0, who="disparity_reproject", name="Q"):
     """(min_disp, max_disp) as the two floats the library takes, after refusing -- before any device work -- a Q that is not a
     floating-point [4,4] or [B,4,4] tensor or, where it lies on the CPU, has a non-finite entry (a Q already on the device is not
     read back: its entries are the caller's), a min_disp that is not a finite fp32 value, a max_disp below it, and more than four
-    attribute planes.  max_disp None or beyond the largest float is that float: a usable disparity is finite."""
+    attribute planes.  max_disp None or beyond the largest float is that float: a usable disparity is finite.  name: what the
+    messages call the matrix (disparity_warp's is M)."""
     if not isinstance(Q, torch.Tensor) or not Q.is_floating_point() or Q.dim() not in (2, 3) or tuple(Q.shape[-2:]) != (4, 4) \
             or Q.shape[0] < 1:
         what = f"{tuple(Q.shape)} {Q.dtype}" if isinstance(Q, torch.Tensor) else type(Q).__name__
-        raise ValueError(f"{who}: Q {what}: a floating-point [4,4] or [B,4,4] tensor")
+        raise ValueError(f"{who}: {name} {what}: a floating-point [4,4] or [B,4,4] tensor")
     if not Q.is_cuda and not bool(torch.isfinite(Q).all()):
-        raise ValueError(f"{who}: Q has a non-finite entry")
+        raise ValueError(f"{who}: {name} has a non-finite entry")
     _real(who, "min_disp", min_disp, fp32=True)
     if max_disp is None:
         max_disp = _FLT_MAX
@@ -907,16 +908,17 @@ def check_reproject_parameters(Q, min_disp=0.0, max_disp=None, n_attributes=0, w
     return float(min_disp), min(float(max_disp), _FLT_MAX)
 
 
-def _reproject_operands(who, disp, Q, attributes, valid, min_disp, max_disp):
-    """Every refusal of the two ops, then the operands: (d, v, q, per_image, a, lo, hi); q the float64 device copy of Q."""
+def _reproject_operands(who, disp, Q, attributes, valid, min_disp, max_disp, name="Q"):
+    """Every refusal of the two ops (and of disparity_warp, whose matrix is called M: `name`), then the operands:
+    (d, v, q, per_image, a, lo, hi); q the float64 device copy of Q."""
     if attributes is not None:
         _need(isinstance(attributes, torch.Tensor) and attributes.dim() == 4,
               lambda: f"{who}: attributes {tuple(getattr(attributes, 'shape', ()))}: want [B,C,H,W]")
-    lo, hi = check_reproject_parameters(Q, min_disp, max_disp, 0 if attributes is None else attributes.shape[1], who)
+    lo, hi = check_reproject_parameters(Q, min_disp, max_disp, 0 if attributes is None else attributes.shape[1], who, name)
     d, v = _filter_planes(who, disp, valid)
     B, H, W = d.shape
     if Q.dim() == 3 and Q.shape[0] != B:
-        raise ValueError(f"{who}: Q {tuple(Q.shape)} against disp {tuple(d.shape)}: one matrix, or one per image")
+        raise ValueError(f"{who}: {name} {tuple(Q.shape)} against disp {tuple(d.shape)}: one matrix, or one per image")
     a = None
     if attributes is not None and attributes.shape[1] > 0:
         _chk(attributes)
@@ -975,6 +977,131 @@ def point_cloud(disp, Q, attributes=None, valid=None, min_disp=0.0, max_disp=Non
     n = int(offsets[B].item())                                         # the one host synchronisation
     points = points[:n]
     return (points, offsets, xyz, mask.view(torch.bool)) if with_dense else (points, offsets)
+
+
+# ------------------------------------------------------------------------------------ temporal carry: pose warp and fusion
+# DESIGN.md section 30; include/ecm_temporal.h.  Forward only: a disparity map carried to the next frame by a known camera motion
+# -- one fp64 matrix per image, a z-buffered 2-D scatter -- and a per-pixel Kalman update behind it.
+WARP_FOOTPRINTS = ("cover", "nearest")                                 # the `footprint` of ecmt_disparity_warp_fwd: 0, 1
+
+
+def disparity_warp_max_attributes():
+    """The most attribute planes disparity_warp carries (a size query of the library: no GPU needed)."""
+    return int(_lib.query("ecmt_disparity_warp_max_attributes"))
+
+
+def _pose(who, name, t):
+    """t, a float64 CPU [4,4] or [B,4,4] tensor with finite entries, or ValueError."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.is_cuda or t.dim() not in (2, 3) \
+            or tuple(t.shape[-2:]) != (4, 4) or t.shape[0] < 1:
+        what = f"{tuple(t.shape)} {t.dtype} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{who}: {name} {what}: a float64 CPU [4,4] or [B,4,4] tensor")
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError(f"{who}: {name} has a non-finite entry")
+    return t.detach()
+
+
+def warp_matrix(Q, T, Q_out=None):
+    """M = inv(Q_out) @ T @ Q in float64 on the CPU, [4,4] or (where any operand is batched) [B,4,4]: the matrix that
+    disparity_warp applies to (x, y, d, 1).  Q and Q_out (None: Q) are the disparity-to-depth matrices of the previous and the
+    current frame, as q_matrix / stereo_rectify return them; T takes points of the previous left-camera frame to the current
+    one, in the unit of Q's baseline.  Q is projective, so T Q (x, y, d, 1) is the moved point in homogeneous coordinates and
+    inv(Q_out) takes it back to a pixel and a disparity: the whole motion is one matrix.  T need not be rigid -- any finite 4x4 is
+    applied as it is.  Rigid means T = [[R, t], [0, 1]] with R a rotation (R^T R = I, det R = +1): that is the caller's to
+    supply, for a static scene seen from a moving camera the inverse of the camera's own motion.  ValueError, before any device
+    work, for an operand that is not a float64 CPU [4,4] or [B,4,4] tensor, disagreeing batch sizes, a non-finite entry or a
+    singular Q_out."""
+    Q, T = _pose("warp_matrix", "Q", Q), _pose("warp_matrix", "T", T)
+    Q_out = Q if Q_out is None else _pose("warp_matrix", "Q_out", Q_out)
+    batches = {t.shape[0] for t in (Q, T, Q_out) if t.dim() == 3}
+    if len(batches) > 1:
+        raise ValueError(f"warp_matrix: Q {tuple(Q.shape)}, T {tuple(T.shape)}, Q_out {tuple(Q_out.shape)}: one batch size")
+    inv, info = torch.linalg.inv_ex(Q_out)
+    if bool((info != 0).any()) or not bool(torch.isfinite(inv).all()):
+        raise ValueError("warp_matrix: Q_out is singular")
+    return inv @ T @ Q
+
+
+def check_warp_parameters(M, min_disp=0.0, max_disp=None, n_attributes=0, footprint="cover", who="disparity_warp"):
+    """(min_disp, max_disp, footprint) as the two floats and the int the library takes, after refusing -- before any device work
+    -- an M that is not a float64 [4,4] or [B,4,4] tensor or, where it lies on the CPU, has a non-finite entry, a min_disp that
+    is not a finite fp32 value, a max_disp below it, more than disparity_warp's four attribute planes and a footprint other than
+    "cover" or "nearest"."""
+    if footprint not in WARP_FOOTPRINTS:
+        raise ValueError(f"{who}: footprint {footprint!r}: one of {WARP_FOOTPRINTS}")
+    if isinstance(M, torch.Tensor) and M.dtype != torch.float64:
+        raise ValueError(f"{who}: M is {M.dtype}: want float64 (ops.warp_matrix builds one)")
+    lo, hi = check_reproject_parameters(M, min_disp, max_disp, n_attributes, who, "M")
+    return lo, hi, WARP_FOOTPRINTS.index(footprint)
+
+
+@torch.no_grad()
+def disparity_warp(disp, M, valid=None, attributes=None, min_disp=0.0, max_disp=None, footprint="cover", with_source=False):
+    """disp ([B,H,W] or [B,1,H,W], pixels) carried into another frame by M (float64 [4,4] or [B,4,4], on the CPU or the device;
+    ops.warp_matrix builds one), with a z-buffer, as out [B,1,H,W].  A pixel is usable by disparity_reproject's rule (d finite,
+    valid != 0, min_disp < d <= max_disp, the fourth row's w finite and non-zero).  [a b c w]^T = M [x y d 1]^T in fp64 in
+    disparity_reproject's order; the pixel is a candidate where u = a/w, v = b/w and dn = (float)(c/w) are finite, dn > 0,
+    0 <= u <= W-1 and 0 <= v <= H-1.  footprint "cover": it lands on (floor u, floor v), on the next column too iff u is not
+    integral, on the next row too iff v is not -- up to four sites, so that a surface that the motion magnifies (by less than
+    two) leaves no holes, at the price of foreground edges up to one pixel thicker (as disparity_splat's); "nearest": on the
+    one site (floor(u + 0.5), floor(v + 0.5)).  Per site the largest dn wins (the nearest surface), among equals the larger
+    source index y * W + x.  out is the winner's dn bit for bit and +0.0 for a hole.  attributes ([B,C,H,W] fp32, C <= 4): also
+    returns attrs_out [B,C,H,W], the planes at the winner's source pixel bit for bit, +0.0 for a hole.  with_source=True: also
+    src [B,1,H,W] int32, the winner's index, -1 for a hole.  Returns out, (out, src), (out, attrs_out) or (out, attrs_out, src).
+    Integer maxima only: bit-reproducible, and an image does not depend on the rest of the batch.  A static-scene model: what
+    moved on its own is warped as if it had not."""
+    if attributes is not None:
+        _need(isinstance(attributes, torch.Tensor) and attributes.dim() == 4,
+              lambda: f"disparity_warp: attributes {tuple(getattr(attributes, 'shape', ()))}: want [B,C,H,W]")
+    _, _, fp = check_warp_parameters(M, min_disp, max_disp, 0 if attributes is None else attributes.shape[1], footprint)
+    d, v, m, per_image, a, lo, hi = _reproject_operands("disparity_warp", disp, M, attributes, valid, min_disp, max_disp, "M")
+    B, H, W = d.shape
+    C_ = 0 if a is None else a.shape[1]
+    nb = _lib.query("ecmt_disparity_warp_scratch_bytes", B, H, W)
+    _need(nb > 0, lambda: f"disparity_warp: disp {tuple(d.shape)}: more pixels than the kernels are built for (H*W < 2^31)")
+    out = torch.empty(B, 1, H, W, device=d.device, dtype=d.dtype)
+    src = torch.empty(B, 1, H, W, device=d.device, dtype=torch.int32) if with_source else None
+    attrs_out = torch.empty(B, C_, H, W, device=d.device, dtype=d.dtype) if attributes is not None else None
+    scratch = _scratch(nb, d.device)
+    _lib.call("ecmt_disparity_warp_fwd", _p(d), _p(v), _p(m), per_image, _p(a), C_, _p(out), _p(src),
+              _p(attrs_out if C_ else None), _p(scratch), C.c_longlong(nb), B, H, W, lo, hi, fp, _stream())
+    res = (out,) + ((attrs_out,) if attributes is not None else ()) + ((src,) if with_source else ())
+    return res if len(res) > 1 else out
+
+
+def check_fuse_parameters(gate=3.0, process_noise=0.0, coast=True, who="disparity_fuse"):
+    """(gate, process_noise, coast) as two floats and an int: both numbers finite fp32 values >= 0, coast a bool."""
+    if not isinstance(coast, bool):
+        raise ValueError(f"{who}: coast {coast!r}: True or False")
+    return _real(who, "gate", gate, ">= 0", fp32=True), _real(who, "process_noise", process_noise, ">= 0", fp32=True), int(coast)
+
+
+@torch.no_grad()
+def disparity_fuse(disp, var, prev, prev_var, prev_age=None, prev_source=None, gate=3.0, process_noise=0.0, coast=True):
+    """(fused, fused_var, age), each [B,1,H,W] (age int32): the per-pixel scalar Kalman update of a state carried into this frame
+    (prev, prev_var, prev_age: disparity_warp's outputs) with the frame's own estimate (disp and its variance var, e.g.
+    predict's std squared).  A measurement exists where disp and var are finite and > 0, a prediction where prev > 0 and prev_var
+    is finite and > 0.  The predicted variance s = prev_var + process_noise; with prev_source (the disparity the winner had
+    before the warp, carried as an attribute) s = prev_var * r^4 + process_noise, r = prev / prev_source -- the first-order
+    propagation of a disparity's variance for a motion along the optical axis, and only that: a rotation or a sideways motion
+    changes the disparity by an amount that does not scale it.  Both exist and (disp - prev)^2 <= gate^2 (s + var):
+    K = s / (s + var), fused = prev + K (disp - prev), fused_var = (1 - K) s, age = prev_age + 1.  Both exist and the gate fails
+    (a moving object, a disocclusion), or only a measurement: (disp, var, 1).  Only a prediction: (prev, s, prev_age) with
+    coast, else zeros.  Neither: zeros.  prev_age: int32, None for all zeros.  One launch, fp32 in a fixed order:
+    bit-reproducible.  Every plane [B,H,W] or [B,1,H,W] of disp's shape."""
+    who = "disparity_fuse"
+    gate, process_noise, coast = check_fuse_parameters(gate, process_noise, coast)          # before any device work
+    d = _disp_plane(who, disp)
+    f32 = ((torch.float32,), "fp32")
+    planes = [_c(d.detach())] + [_c(_plane_like(who, n, t, d, *f32)) for n, t in (("var", var), ("prev", prev), ("prev_var", prev_var))]
+    age_in = None if prev_age is None else _c(_plane_like(who, "prev_age", prev_age, d, (torch.int32,), "int32"))
+    source = None if prev_source is None else _c(_plane_like(who, "prev_source", prev_source, d, *f32))
+    B, H, W = d.shape
+    fused, fused_var = (torch.empty(B, 1, H, W, device=d.device, dtype=d.dtype) for _ in range(2))
+    age = torch.empty(B, 1, H, W, device=d.device, dtype=torch.int32)
+    _lib.call("ecmt_disparity_fuse_fwd", *(_p(t) for t in planes), _p(age_in), _p(source), _p(fused), _p(fused_var), _p(age),
+              C.c_longlong(B * H * W), gate, process_noise, coast, _stream())
+    return fused, fused_var, age
 
 
 # ------------------------------------------------------------------------------------ a5-a7 conv / deconv / GN

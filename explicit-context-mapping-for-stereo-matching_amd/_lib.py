@@ -1,5 +1,5 @@
-"""ctypes binding of libecm_hip.so (the C ABI declared in include/ecm_hip.h and, for the geometry, rectification and temporal
-entries, include/ecm_geometry.h, include/ecm_rectify.h and include/ecm_temporal.h).
+"""ctypes binding of libecm_hip.so (the C ABI declared in include/ecm_hip.h and, for the geometry, rectification, temporal and
+motion entries, include/ecm_geometry.h, include/ecm_rectify.h, include/ecm_temporal.h and include/ecm_motion.h).
 
 The product path has NO fallback: if the library is missing or a call fails, a RuntimeError is
 raised.  Each table below mirrors its header one to one: tests/test_abi_types.py parses every header of TABLES and compares
@@ -192,8 +192,26 @@ EXTENSION_TABLES = {
 }
 
 
+# The motion entries (include/ecm_motion.h, prefix ecmm_): the normal equations of the dense disparity alignment.
+MOTION_PROTOTYPES = {
+    "ecmm_align_sums": (_I, []),
+    "ecmm_align_scratch_bytes": (_LL, [_I, _I, _I, _I]),
+    "ecmm_align_normal_fwd": (_I, [_P] * 8 + [_I, _P, _P, _P, _LL, _I, _I, _I, _I, _F, _F, _F, _F, _F, _P]),
+}
+
+# A third registry of the same form: tests/test_disp_warp_cpu.py pins the keys of TABLES (three rows) and of EXTENSION_TABLES
+# (ecm_temporal.h alone), so a fifth header can be a row of neither without an edit of that file.  Its own test file holds it to
+# the same census.  Folding the three registries into one is a later change that may touch the census files.
+MOTION_TABLES = {
+    "ecm_motion.h": (MOTION_PROTOTYPES, "ecmm_"),
+}
+
+# every registry that load(), missing_symbols(), call() and query() serve
+REGISTRIES = (TABLES, EXTENSION_TABLES, MOTION_TABLES)
+
+
 def _tables():
-    return [row for registry in (TABLES, EXTENSION_TABLES) for table, _ in registry.values() for row in table.items()]
+    return [row for registry in REGISTRIES for table, _ in registry.values() for row in table.items()]
 
 
 _lib = None

@@ -1284,8 +1284,8 @@ class DisparityTracker:
         """Forget the state: the next call starts over."""
         self._state = None
 
-    def __call__(self, left, right, motion=None):
-        M = None if motion is None else ops.warp_matrix(self.Q, motion)    # ValueError before any device work
+    def measure(self, left, right):
+        """The measuring half of a call: this frame's own (disparity, std), each [B,1,H,W]; the state is not touched."""
         with torch.no_grad():
             if self.model.HEAD in _NO_DISTRIBUTION:
                 disparity = self.model(left, right)[self.head]
@@ -1295,15 +1295,84 @@ class DisparityTracker:
             else:
                 p = self.model.predict(left, right, (self.head,))
                 disparity, std = p.disparity[0], p.std[0]
-            state = self._state
-            if M is None or state is None or state[0].shape != disparity.shape or state[0].device != disparity.device:
+        return disparity, std
+
+    def carries(self, disparity):
+        """Whether the state can be carried into a frame whose disparity is `disparity`: it exists, with that shape and device."""
+        state = self._state
+        return state is not None and state[0].shape == disparity.shape and state[0].device == disparity.device
+
+    def advance(self, disparity, std, M):
+        """The advancing half of a call: the state warped by M (None: start over) and fused with the measurement; the Tracked."""
+        with torch.no_grad():
+            if M is None or not self.carries(disparity):
                 warped, prev_var, prev_source = (torch.zeros_like(disparity) for _ in range(3))
                 prev_age = torch.zeros_like(disparity, dtype=torch.int32)
             else:
-                fused, variance, age = state
+                fused, variance, age = self._state
                 warped, carried = ops.disparity_warp(fused, M, attributes=torch.cat([variance, fused, age.to(torch.float32)], 1),
                                                      footprint=self.footprint)
                 prev_var, prev_source, prev_age = carried[:, 0:1], carried[:, 1:2], carried[:, 2:3].to(torch.int32)
             self._state = ops.disparity_fuse(disparity, std * std, warped, prev_var, prev_age, prev_source, self.gate,
                                              self.process_noise, self.coast)
         return Tracked(disparity, std, warped, *self._state)
+
+    def __call__(self, left, right, motion=None):
+        M = None if motion is None else ops.warp_matrix(self.Q, motion)    # ValueError before any device work
+        return self.advance(*self.measure(left, right), M)
+
+
+# What StereoOdometry returns: Tracked's six fields as DisparityTracker returns them for `motion`; motion [B,4,4] float64 CPU, the
+# estimated motion from the previous frame to this one (the identity where the frame starts over); pose [B,4,4], the product of
+# the motions since the last start, so that it takes points of the starting frame to this one; estimate, the ops.MotionEstimate
+# (None where there was no state to align to); restarted: the frame started over (a first call, a reset, a changed shape, or an
+# estimate that did not converge for some image of the batch).
+Odometry = collections.namedtuple("Odometry", Tracked._fields + ("motion", "pose", "estimate", "restarted"))
+
+
+class StereoOdometry:
+    """DisparityTracker for a rig whose motion is NOT known: per call the frame's predict
+    (DisparityTracker.measure), ops.motion_estimate from the carried state to this frame's disparity -- disp0 the fused state
+    with valid0 = fused > 0 and weight = 1 / variance, init the previous frame's motion (constant velocity), on the lattice of
+    `step` -- and the tracker's warp and fuse (DisparityTracker.advance) with the estimate.  Where the estimate does not
+    converge for every image of the batch the frame starts over as motion=None does, and `restarted` says so.  A plain object
+    like the tracker; reset() forgets the state, the velocity and the pose.  A static-scene estimator without a pyramid; every
+    default is untested for quality, and nobody has measured it on real sequences."""
+
+    def __init__(self, model, Q, head=2, step=2, iterations=10, damping=1e-6, tolerance=1e-7, min_pixels=64, tap_range=1.0,
+                 max_residual=3.0, cauchy=1.0, gate=3.0, process_noise=0.01, sigma0=1.0, footprint="cover", coast=True):
+        self.tracker = DisparityTracker(model, Q, head, gate, process_noise, sigma0, footprint, coast)
+        eye = torch.eye(4, dtype=torch.float64)
+        ops._align_matrices("StereoOdometry", Q, eye, None)               # the estimator's own refusals, before any frame is seen
+        ops.check_align_parameters(step, 0.0, None, tap_range, max_residual, cauchy, "StereoOdometry")
+        ops.check_estimate_parameters(iterations, damping, tolerance, min_pixels, "StereoOdometry")
+        self.estimator = dict(step=step, iterations=iterations, damping=damping, tolerance=tolerance, min_pixels=min_pixels,
+                              tap_range=tap_range, max_residual=max_residual, cauchy=cauchy)
+        self.Q = self.tracker.Q
+        self._velocity, self._pose, self._eye = None, None, eye
+
+    def reset(self):
+        """Forget the state, the velocity and the pose: the next call starts over."""
+        self.tracker.reset()
+        self._velocity = self._pose = None
+
+    def __call__(self, left, right):
+        disparity, std = self.tracker.measure(left, right)
+        B = disparity.shape[0]
+        estimate, motion = None, None
+        if self.tracker.carries(disparity):
+            fused, variance, _ = self.tracker._state
+            init = self._velocity if self._velocity is not None and self._velocity.shape[0] == B else None
+            with torch.no_grad():
+                estimate = ops.motion_estimate(fused, disparity, self.Q, init, valid0=fused > 0, weight=1.0 / variance,
+                                               **self.estimator)
+            if bool(estimate.converged.all()):
+                motion = estimate.T
+        restarted = motion is None
+        tracked = self.tracker.advance(disparity, std, None if restarted else ops.warp_matrix(self.Q, motion))
+        if restarted:
+            motion = self._eye.expand(B, 4, 4).clone()
+            self._velocity, self._pose = None, motion.clone()
+        else:
+            self._velocity, self._pose = motion, motion @ self._pose
+        return Odometry(*tracked, motion, self._pose.clone(), estimate, restarted)

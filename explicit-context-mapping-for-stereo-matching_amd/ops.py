@@ -1104,6 +1104,222 @@ def disparity_fuse(disp, var, prev, prev_var, prev_age=None, prev_source=None, g
     return fused, fused_var, age
 
 
+# ------------------------------------------------------------------------------------ camera motion: dense disparity alignment
+# DESIGN.md section 31; include/ecm_motion.h.  Forward only: the rigid motion that maps one disparity map onto the next, by
+# Gauss-Newton on the residual in disparity space.  The device forms the 27 sums of the normal equations in one call; the 6x6
+# solve and the pose update are fp64 on the host.
+_SE3_SERIES = 0.1            # below this angle the coefficients are their Taylor series (truncated below 1e-17 relative)
+
+
+def _twists(who, name, t, last):
+    """t, a float64 CPU tensor [last...] or [B, last...] with finite entries, as ([B, last...], was it batched), or ValueError."""
+    n = len(last)
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.is_cuda or t.dim() not in (n, n + 1) \
+            or tuple(t.shape[-n:]) != last or t.shape[0] < 1:
+        what = f"{tuple(t.shape)} {t.dtype} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{who}: {name} {what}: a float64 CPU tensor {list(last)} or [B, {', '.join(map(str, last))}]")
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError(f"{who}: {name} has a non-finite entry")
+    t = t.detach()
+    return (t, True) if t.dim() == n + 1 else (t.unsqueeze(0), False)
+
+
+def _hat(w):
+    """[B,3] -> the skew matrices [B,3,3]: hat(w) x = w cross x."""
+    K = torch.zeros(w.shape[0], 3, 3, dtype=torch.float64)
+    K[:, 0, 1], K[:, 0, 2], K[:, 1, 0], K[:, 1, 2], K[:, 2, 0], K[:, 2, 1] = -w[:, 2], w[:, 1], w[:, 2], -w[:, 0], -w[:, 1], w[:, 0]
+    return K
+
+
+def se3_exp(xi):
+    """The rigid motion exp(xi^) of a twist xi = (nu, omega), float64 on the CPU, [6] -> [4,4] or [B,6] -> [B,4,4]:
+    R = I + a K + b K^2 and t = (I + b K + c K^2) nu with K = hat(omega), th = |omega|, a = sin th / th, b = (1 - cos th) / th^2,
+    c = (th - sin th) / th^3.  Below th = 0.1 the three are their Taylor series, so exp(0) is the identity exactly."""
+    xi, batched = _twists("se3_exp", "xi", xi, (6,))
+    nu, om = xi[:, :3], xi[:, 3:]
+    t2 = (om * om).sum(1)
+    th = torch.sqrt(t2)
+    small = th < _SE3_SERIES
+    ts = torch.where(small, torch.ones_like(th), th)
+    half = torch.sin(ts / 2.0) / (ts / 2.0)
+    a = torch.where(small, 1 - t2 / 6 * (1 - t2 / 20 * (1 - t2 / 42 * (1 - t2 / 72 * (1 - t2 / 110)))), torch.sin(ts) / ts)
+    b = torch.where(small, 0.5 * (1 - t2 / 12 * (1 - t2 / 30 * (1 - t2 / 56 * (1 - t2 / 90 * (1 - t2 / 132))))), 0.5 * half * half)
+    c = torch.where(small, (1 - t2 / 20 * (1 - t2 / 42 * (1 - t2 / 72 * (1 - t2 / 110 * (1 - t2 / 156))))) / 6,
+                    (ts - torch.sin(ts)) / (ts * ts * ts))
+    K = _hat(om)
+    K2 = K @ K
+    eye = torch.eye(3, dtype=torch.float64)
+    T = torch.zeros(xi.shape[0], 4, 4, dtype=torch.float64)
+    T[:, :3, :3] = eye + a[:, None, None] * K + b[:, None, None] * K2
+    T[:, :3, 3] = ((eye + b[:, None, None] * K + c[:, None, None] * K2) @ nu[:, :, None])[:, :, 0]
+    T[:, 3, 3] = 1.0
+    return T if batched else T[0]
+
+
+def se3_log(T):
+    """The twist xi = (nu, omega) with exp(xi^) = T, float64 on the CPU, [4,4] -> [6] or [B,4,4] -> [B,6]; |omega| in [0, pi].  T's
+    rotation block is taken as orthonormal and its bottom row is not read.  nu = (I - K / 2 + d K^2) t with K = hat(omega),
+    d = (1 - a / (2 b)) / th^2 in se3_exp's a and b, its Taylor series below th = 0.1.  se3_log(se3_exp(xi)) is xi to rounding
+    for |omega| < pi."""
+    T, batched = _twists("se3_log", "T", T, (4, 4))
+    om = torch.stack([_rotation_vector(R) for R in T[:, :3, :3]])
+    t2 = (om * om).sum(1)
+    th = torch.sqrt(t2)
+    small = th < _SE3_SERIES
+    ts = torch.where(small, torch.ones_like(th), th)
+    half = torch.sin(ts / 2.0) / (ts / 2.0)
+    a, b = torch.sin(ts) / ts, 0.5 * half * half
+    d = torch.where(small, 1.0 / 12 + t2 / 720 + t2 * t2 / 30240 + t2 * t2 * t2 / 1209600, (1 - a / (2 * b)) / (ts * ts))
+    K = _hat(om)
+    Vinv = torch.eye(3, dtype=torch.float64) - 0.5 * K + d[:, None, None] * (K @ K)
+    xi = torch.cat([(Vinv @ T[:, :3, 3:4])[:, :, 0], om], 1)
+    return xi if batched else xi[0]
+
+
+ALIGN_SUMS = 32                                                        # doubles per image of motion_normal
+
+
+def align_sums():
+    """The doubles per image that motion_normal returns (a size query of the library: no GPU needed); ALIGN_SUMS restates it."""
+    return int(_lib.query("ecmm_align_sums"))
+
+
+def check_align_parameters(step=1, min_disp=0.0, max_disp=None, tap_range=1.0, max_residual=3.0, cauchy=1.0, who="motion_normal"):
+    """(step, min_disp, max_disp, tap_range, max_residual, cauchy) as the int and the five floats the library takes: step an
+    integer >= 1, min_disp a finite fp32 value, max_disp None (no upper bound) or a number >= min_disp, the other three finite
+    fp32 values > 0.  ValueError otherwise, before any device work."""
+    step = _integer(who, "step", step, 1, 2 ** 31 - 1)
+    lo, hi = check_reproject_parameters(torch.eye(4, dtype=torch.float64), min_disp, max_disp, 0, who)
+    return (step, lo, hi) + tuple(_real(who, n, v, "> 0", fp32=True)
+                                  for n, v in (("tap_range", tap_range), ("max_residual", max_residual), ("cauchy", cauchy)))
+
+
+def _align_matrices(who, Q, T, Q_out):
+    """(Q, inv(Q_out), T) after their refusals: Q and Q_out float64 CPU [4,4], T float64 CPU [4,4] or [B,4,4], Q_out regular."""
+    Q, T = _pose(who, "Q", Q), _pose(who, "T", T)
+    Q_out = Q if Q_out is None else _pose(who, "Q_out", Q_out)
+    if Q.dim() != 2 or Q_out.dim() != 2:
+        raise ValueError(f"{who}: Q {tuple(Q.shape)}, Q_out {tuple(Q_out.shape)}: one [4,4] matrix each for the batch")
+    inv, info = torch.linalg.inv_ex(Q_out)
+    if bool((info != 0).any()) or not bool(torch.isfinite(inv).all()):
+        raise ValueError(f"{who}: Q_out is singular")
+    return Q, inv, T
+
+
+@torch.no_grad()
+def motion_normal(disp0, disp1, Q, T, valid0=None, valid1=None, weight=None, Q_out=None, step=1, min_disp=0.0, max_disp=None,
+                  tap_range=1.0, max_residual=3.0, cauchy=1.0, with_residual=False):
+    """The normal equations of one Gauss-Newton step of the alignment of disp0 (the source: the previous frame or a carried
+    state) to disp1 (the target: this frame), both [B,H,W] or [B,1,H,W] fp32 with H, W >= 2, under the motion estimate T (float64
+    CPU [4,4] or [B,4,4]; it takes points of the source frame to the target frame): sums [B,32] float64 on the device, one kernel
+    call.  Per source pixel of the lattice x % step == 0, y % step == 0 that is usable by disparity_reproject's rule (valid0,
+    min_disp, max_disp, Q) and whose weight ([B,H,W] fp32, the inverse variance of the residual; None: 1) is finite and > 0: the
+    point is moved by T, projected by inv(Q_out) (Q_out None: Q; both float64 CPU [4,4]) to (u, v, dn); disp1 is sampled
+    bilinearly at (u, v) where its four taps are usable (valid1) and within tap_range of one another; the residual is
+    r = sample - dn, dropped beyond max_residual; J is its derivative for a left-multiplied twist; the Cauchy weight is
+    1 / (1 + weight r^2 / cauchy^2).  sums[b]: [0..20] the upper triangle of sum a J^T J, [21..26] sum a J^T r, [27] sum a r^2,
+    [28] sum a, [29] the pixels used, [30] the candidates (projected into view), [31] 0 -- include/ecm_motion.h states every
+    operation.  with_residual=True returns (sums, residual), residual [B,1,H,W] fp32: r at the used source pixels, NaN elsewhere.
+    No atomics, a fixed order of additions: bit-reproducible, and an image's sums do not depend on the rest of the batch."""
+    who = "motion_normal"
+    step, lo, hi, tap_range, max_residual, cauchy = check_align_parameters(step, min_disp, max_disp, tap_range, max_residual, cauchy)
+    Q, Qinv, T = _align_matrices(who, Q, T, Q_out)
+    d0, v0 = _filter_planes(who, disp0, valid0)
+    B, H, W = d0.shape
+    _need(H >= 2 and W >= 2, lambda: f"{who}: disp0 {tuple(d0.shape)}: H and W at least 2 (the target is sampled bilinearly)")
+    if T.dim() == 3 and T.shape[0] != B:
+        raise ValueError(f"{who}: T {tuple(T.shape)} against disp0 {tuple(d0.shape)}: one matrix, or one per image")
+    f32 = ((torch.float32,), "fp32")
+    d1 = _c(_plane_like(who, "disp1", disp1, d0, *f32))
+    v1 = None if valid1 is None else _mask_plane(who, valid1, d0)
+    w0 = None if weight is None else _c(_plane_like(who, "weight", weight, d0, *f32))
+    nb = _lib.query("ecmm_align_scratch_bytes", B, H, W, step)
+    _need(nb > 0, lambda: f"{who}: disp0 {tuple(d0.shape)}: more pixels than the kernels are built for (H*W < 2^31)")
+    mats = torch.cat([Q.reshape(-1), Qinv.reshape(-1), T.reshape(-1)]).to(d0.device)          # one host-to-device copy
+    sums = torch.empty(B, ALIGN_SUMS, device=d0.device, dtype=torch.float64)
+    residual = torch.empty(B, 1, H, W, device=d0.device, dtype=d0.dtype) if with_residual else None
+    scratch = _scratch(nb, d0.device)
+    at = mats.data_ptr()
+    _lib.call("ecmm_align_normal_fwd", _p(d0), _p(v0), _p(w0), _p(d1), _p(v1), C.c_void_p(at), C.c_void_p(at + 128),
+              C.c_void_p(at + 256), int(T.dim() == 3), _p(sums), _p(residual), _p(scratch), C.c_longlong(nb), B, H, W, step, lo, hi,
+              tap_range, max_residual, cauchy, _stream())
+    return (sums, residual) if with_residual else sums
+
+
+# What motion_estimate returns.  T [B,4,4] float64 on the CPU, in the form DisparityTracker takes as `motion`; per image:
+# converged (bool), iterations (int64: the steps taken), used and candidates (int64: the pixels of the last sums), rms
+# (sqrt(sums[27] / sums[28]) of the last sums; NaN where nothing was used) and information [B,6,6], the last J^T J (undamped).
+MotionEstimate = collections.namedtuple("MotionEstimate", "T converged iterations used candidates rms information")
+
+
+def unpack_align_sums(sums):
+    """(H [B,6,6], g [B,6]) of sums [B,32]: the symmetric J^T J from its upper triangle, and J^T r."""
+    iu = torch.triu_indices(6, 6)
+    H = torch.zeros(sums.shape[0], 6, 6, dtype=sums.dtype)
+    H[:, iu[0], iu[1]] = sums[:, :21]
+    H[:, iu[1], iu[0]] = sums[:, :21]
+    return H, sums[:, 21:27]
+
+
+def check_estimate_parameters(iterations=10, damping=1e-6, tolerance=1e-7, min_pixels=64, who="motion_estimate"):
+    """(iterations, damping, tolerance, min_pixels): integers >= 1 and finite numbers >= 0, or ValueError."""
+    return (_integer(who, "iterations", iterations, 1), _real(who, "damping", damping, ">= 0"),
+            _real(who, "tolerance", tolerance, ">= 0"), _integer(who, "min_pixels", min_pixels, 1))
+
+
+def motion_estimate(disp0, disp1, Q, init=None, valid0=None, valid1=None, weight=None, Q_out=None, step=1, min_disp=0.0,
+                    max_disp=None, tap_range=1.0, max_residual=3.0, cauchy=1.0, iterations=10, damping=1e-6, tolerance=1e-7,
+                    min_pixels=64, normal=None):
+    """The rigid motion T that maps the disparity surface of disp0 onto disp1 (motion_normal's operands), by at most `iterations`
+    Gauss-Newton steps from init (float64 CPU [4,4] or [B,4,4]; None: the identity): per step one motion_normal call, one
+    device-to-host copy of its [B,32] sums, the solve of (H + damping diag(H)) xi = -g in fp64 on the host, and
+    T <- se3_exp(xi) T.  An image stops, converged, once |xi| < tolerance.  An image with fewer than min_pixels used pixels or a
+    system that cannot be solved stops with its init as T and converged False: never a NaN pose.  Returns a MotionEstimate.
+    normal: a callable T [B,4,4] -> sums [B,32] that replaces motion_normal (disp0 then only gives B, and nothing is launched):
+    the loop itself runs on the host.  A static-scene estimator without a pyramid: see DESIGN.md section 31 for what it cannot
+    do; every default is untested for quality."""
+    who = "motion_estimate"
+    iterations, damping, tolerance, min_pixels = check_estimate_parameters(iterations, damping, tolerance, min_pixels)
+    check_align_parameters(step, min_disp, max_disp, tap_range, max_residual, cauchy, who)
+    B = disp0.shape[0]
+    init = torch.eye(4, dtype=torch.float64) if init is None else _pose(who, "init", init)
+    if init.dim() == 3 and init.shape[0] != B:
+        raise ValueError(f"{who}: init {tuple(init.shape)} against disp0 {tuple(disp0.shape)}: one matrix, or one per image")
+    init = (init.expand(B, 4, 4) if init.dim() == 2 else init).clone()
+    if normal is None:
+        def normal(T):
+            return motion_normal(disp0, disp1, Q, T, valid0, valid1, weight, Q_out, step, min_disp, max_disp, tap_range,
+                                 max_residual, cauchy)
+    T = init.clone()
+    active = torch.ones(B, dtype=torch.bool)
+    converged = torch.zeros(B, dtype=torch.bool)
+    steps = torch.zeros(B, dtype=torch.int64)
+    last = torch.zeros(B, ALIGN_SUMS, dtype=torch.float64)
+    for _ in range(iterations):
+        sums = normal(T).detach().to(device="cpu", dtype=torch.float64)                      # the one device-to-host copy
+        last[active] = sums[active]
+        H, g = unpack_align_sums(sums)
+        A = H + damping * torch.diag_embed(torch.diagonal(H, dim1=1, dim2=2))
+        xi, info = torch.linalg.solve_ex(A, -g.unsqueeze(2))
+        xi = xi[:, :, 0]
+        solved = (info == 0) & torch.isfinite(xi).all(1) & torch.isfinite(sums).all(1) & (sums[:, 29] >= min_pixels)
+        failed = active & ~solved
+        T[failed] = init[failed]
+        active = active & solved
+        if not bool(active.any()):
+            break
+        T[active] = se3_exp(xi[active]) @ T[active]
+        steps[active] += 1
+        done = active & (torch.linalg.vector_norm(xi, dim=1) < tolerance)
+        converged |= done
+        active = active & ~done
+        if not bool(active.any()):
+            break
+    H, _ = unpack_align_sums(last)
+    rms = torch.sqrt(last[:, 27] / last[:, 28])
+    return MotionEstimate(T, converged, steps, last[:, 29].to(torch.int64), last[:, 30].to(torch.int64), rms, H)
+
+
 # ------------------------------------------------------------------------------------ a5-a7 conv / deconv / GN
 def _pack_conv(w, flip_transpose=False):
     Co, Ci = w.shape[0], w.shape[1]

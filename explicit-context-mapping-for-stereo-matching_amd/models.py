@@ -1376,3 +1376,84 @@ class StereoOdometry:
         else:
             self._velocity, self._pose = motion, motion @ self._pose
         return Odometry(*tracked, motion, self._pose.clone(), estimate, restarted)
+
+
+# What StereoMapper returns: Odometry's ten fields as the odometry (or, for a given motion, the tracker) returns them, bit for bit;
+# world [4,4] float64 CPU, the pose of this frame's left camera (it takes points of the first frame's left-camera frame, the
+# world frame, to this one); integrated: the frame went into the volume; frames: the frames integrated since the last reset.
+Mapped = collections.namedtuple("Mapped", Odometry._fields + ("world", "integrated", "frames"))
+
+
+class StereoMapper:
+    """A TSDF volume filled by a moving stereo rig: per call one StereoOdometry frame -- or, where the
+    motion from the previous frame is known (`motion`, as DisparityTracker takes it), one frame of the odometry's tracker -- the
+    update world = motion @ world of the mapper's own pose, and ops.volume_integrate of the frame's OWN disparity at that pose
+    with weight = 1 / std^2 and valid = disparity > 0 (not the fused state, whose history the volume would count twice).  The
+    world frame is the first frame's left camera; the volume has dims = (nz, ny, nx) voxels of `voxel` (the unit of Q's baseline)
+    from `origin`, and is allocated on the first frame's device.  A frame after the first whose estimate did not converge
+    (Odometry.restarted) is not integrated and the pose is held: what follows is placed as if the rig had not moved over it.
+    render() raycasts the volume at the current pose or a given one; reset() empties the volume and forgets the poses.  A plain
+    object, not a module; batch size 1.  A static-scene model with a dense volume; the distance is along the optical axis, the
+    weight ignores that depth noise grows with Z^2 (min_disp is the guard against far, noisy pixels); every default is untested
+    for quality, and nobody has measured it on real sequences."""
+
+    def __init__(self, model, Q, origin, voxel, dims, trunc, head=2, max_weight=64.0, min_disp=1.0, **odometry_kwargs):
+        self.odometry = StereoOdometry(model, Q, head, **odometry_kwargs)
+        self.Q = self.odometry.Q
+        eye = torch.eye(4, dtype=torch.float64)
+        ops.volume_matrices(self.Q, eye, origin, voxel)                   # origin, voxel and a singular Q, before any frame is seen
+        self.dims = ops._volume_dims("StereoMapper", dims)
+        ops.check_volume_parameters(trunc, max_weight, min_disp, None, "StereoMapper")
+        self.origin, self.voxel, self.trunc, self.max_weight, self.min_disp = origin, voxel, trunc, max_weight, min_disp
+        self.volume, self.world, self.frames, self._size, self._eye = None, eye.clone(), 0, None, eye
+
+    def reset(self):
+        """Empty the volume and forget the poses and the tracker's state: the next frame defines the world frame."""
+        self.odometry.reset()
+        if self.volume is not None:
+            self.volume[0].fill_(1.0)
+            self.volume[1].zero_()
+        self.world, self.frames = self._eye.clone(), 0
+
+    def __call__(self, left, right, motion=None):
+        if not isinstance(left, torch.Tensor) or left.dim() != 4 or left.shape[0] != 1:
+            raise ValueError(f"StereoMapper: frames {tuple(getattr(left, 'shape', ()))}: one pair at a time, [1,3,H,W]")
+        first = self.frames == 0
+        if motion is None:
+            o = self.odometry(left, right)
+            moved, held = o.motion[0], o.restarted and not first
+        else:
+            M = ops.warp_matrix(self.Q, motion)                           # ValueError before any device work
+            motion = motion if motion.dim() == 3 else motion.unsqueeze(0)
+            if motion.shape[0] != 1:
+                raise ValueError(f"StereoMapper: motion {tuple(motion.shape)}: one pair at a time")
+            tracker = self.odometry.tracker
+            disparity, std = tracker.measure(left, right)
+            carried = tracker.carries(disparity)
+            tracked = tracker.advance(disparity, std, M)
+            moved, held = motion[0], False
+            o = Odometry(*tracked, motion.clone(), (self._eye if first else moved @ self.world)[None].clone(), None, not carried)
+        if not (first or held):
+            self.world = moved @ self.world
+        if self.volume is None or self.volume[0].device != o.disparity.device:
+            self.volume = ops.volume_new(self.dims, o.disparity.device)
+        self._size = tuple(o.disparity.shape[-2:])
+        if not held:
+            with torch.no_grad():
+                ops.volume_integrate(*self.volume, o.disparity, self.Q, self.world, self.origin, self.voxel, self.trunc,
+                                     valid=o.disparity > 0, weight=1.0 / (o.std * o.std), max_weight=self.max_weight,
+                                     min_disp=self.min_disp)
+            self.frames += 1
+        return Mapped(*o, self.world.clone(), not held, self.frames)
+
+    def render(self, T=None, size=None, near_disp=None, far_disp=None, step=0.5, max_steps=None, with_weight=False, Q_out=None):
+        """ops.volume_raycast of the volume at the current pose (T None) or at T (world to camera), for the view Q_out (None: Q)
+        of size (H, W) (None: the last frame's): near_disp None is W, the largest disparity a map of that width can hold, and
+        far_disp None is min_disp."""
+        if self.volume is None:
+            raise ValueError("StereoMapper.render: no frame has been integrated")
+        size = self._size if size is None else size
+        near_disp = float(size[1]) if near_disp is None and isinstance(size, (tuple, list)) and len(size) == 2 else near_disp
+        return ops.volume_raycast(*self.volume, self.Q if Q_out is None else Q_out, self.world if T is None else T, self.origin,
+                                  self.voxel, size, near_disp, self.min_disp if far_disp is None else far_disp, step, max_steps,
+                                  with_weight)

@@ -1320,6 +1320,180 @@ def motion_estimate(disp0, disp1, Q, init=None, valid0=None, valid1=None, weight
     return MotionEstimate(T, converged, steps, last[:, 29].to(torch.int64), last[:, 30].to(torch.int64), rms, H)
 
 
+# ------------------------------------------------------------------------------------ TSDF volume: integrate and raycast
+# DESIGN.md section 32; include/ecm_volume.h.  Forward only: disparity maps with their poses are averaged into a dense grid of
+# truncated signed distances, and the grid is raycast back into a disparity map from any pose -- the form motion_estimate takes
+# as disp0.
+
+# What volume_matrices returns, float64 on the CPU, [4,4] each or (for a batched T) [V,4,4]: G grid -> (u, v, d) of the view, C
+# grid -> camera, R (x, y, d) of the output view -> grid, Rinv its inverse.
+VolumeMatrices = collections.namedtuple("VolumeMatrices", "G C R Rinv")
+
+
+def _origin(who, origin):
+    """origin as three floats, or ValueError."""
+    if isinstance(origin, torch.Tensor) and origin.dim() == 1 and not origin.is_cuda:
+        origin = origin.tolist()
+    if not isinstance(origin, (tuple, list)) or len(origin) != 3 or not all(_is_real(v) for v in origin):
+        raise ValueError(f"{who}: origin {origin!r}: three finite numbers")
+    return [float(v) for v in origin]
+
+
+def volume_matrices(Q, T, origin, voxel, Q_out=None):
+    """The per-view matrices of the volume ops, float64 on the CPU: VolumeMatrices(G, C, R, Rinv).  With S = [[voxel I, origin],
+    [0, 1]] (grid point (i, j, k) -> the world point origin + voxel (i, j, k)):  C = T S, grid to camera;  G = inv(Q) C, grid to
+    (u, v, d) of the view that is integrated;  R = inv(S) inv(T) Q_out, (x, y, d) of the view that is raycast to grid;
+    Rinv = inv(Q_out) C, its inverse.  Q and Q_out (None: Q) are disparity-to-depth matrices as q_matrix / stereo_rectify return
+    them, one [4,4] each; T is WORLD TO CAMERA, one [4,4] or [V,4,4], and rigid (the world frame is the left-camera frame of the
+    first frame: what StereoOdometry's pose maps from).  ValueError, before any device work: what motion_normal refuses of its
+    matrices, a voxel that is not a finite number > 0, an origin that is not three finite numbers, a singular Q, and a T whose
+    rotation is not orthonormal (R R^T = I to 1e-6, det +1, as stereo_rectify checks it) or whose bottom row is not (0, 0, 0, 1)."""
+    who = "volume_matrices"
+    Q, Qinv_out, T = _align_matrices(who, Q, T, Q_out)
+    voxel = _real(who, "voxel", voxel, "> 0")
+    origin = _origin(who, origin)
+    Qinv, info = torch.linalg.inv_ex(Q)
+    if bool((info != 0).any()) or not bool(torch.isfinite(Qinv).all()):
+        raise ValueError(f"{who}: Q is singular")
+    Q_out = Q if Q_out is None else Q_out.detach()
+    Tb = T if T.dim() == 3 else T.unsqueeze(0)
+    rot, eye = Tb[:, :3, :3], torch.eye(3, dtype=torch.float64)
+    if float((rot @ rot.transpose(1, 2) - eye).abs().max()) > 1e-6 or float(torch.linalg.det(rot).min()) < 0 \
+            or not torch.equal(Tb[:, 3], torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=torch.float64).expand(Tb.shape[0], 4)):
+        raise ValueError(f"{who}: T is not rigid (R R^T = I to 1e-6, det +1, bottom row 0 0 0 1)")
+    S = torch.eye(4, dtype=torch.float64)
+    S[0, 0] = S[1, 1] = S[2, 2] = voxel
+    S[:3, 3] = torch.tensor(origin, dtype=torch.float64)
+    Sinv = torch.eye(4, dtype=torch.float64)
+    Sinv[0, 0] = Sinv[1, 1] = Sinv[2, 2] = 1.0 / voxel
+    Sinv[:3, 3] = -torch.tensor(origin, dtype=torch.float64) / voxel
+    Tinv = torch.zeros_like(Tb)                                           # a rigid inverse: [[R^T, -R^T t], [0, 1]]
+    Tinv[:, :3, :3] = rot.transpose(1, 2)
+    Tinv[:, :3, 3:] = -(rot.transpose(1, 2) @ Tb[:, :3, 3:])
+    Tinv[:, 3, 3] = 1.0
+    C_ = Tb @ S
+    out = VolumeMatrices(Qinv @ C_, C_, Sinv @ Tinv @ Q_out, Qinv_out @ C_)
+    return out if T.dim() == 3 else VolumeMatrices(*(m[0] for m in out))
+
+
+def check_volume_parameters(trunc, max_weight=64.0, min_disp=0.0, max_disp=None, who="volume_integrate"):
+    """(trunc, max_weight, min_disp, max_disp) as the four floats the library takes: trunc and max_weight finite fp32 values > 0,
+    min_disp a finite fp32 value, max_disp None (no upper bound) or a number >= min_disp.  ValueError otherwise."""
+    trunc, max_weight = _real(who, "trunc", trunc, "> 0", fp32=True), _real(who, "max_weight", max_weight, "> 0", fp32=True)
+    lo, hi = check_reproject_parameters(torch.eye(4, dtype=torch.float64), min_disp, max_disp, 0, who)
+    return trunc, max_weight, lo, hi
+
+
+def raycast_max_steps():
+    """The largest max_steps volume_raycast takes (a query of the library: no GPU needed)."""
+    return int(_lib.query("ecmv_raycast_max_steps"))
+
+
+def check_raycast_parameters(size, near_disp, far_disp, step=0.5, max_steps=None, who="volume_raycast"):
+    """((H, W), near_disp, far_disp, step, max_steps) as the library takes them: size two integers >= 1, near_disp > far_disp > 0
+    and step > 0 finite fp32 values, max_steps None (the library's limit) or an integer in 1..raycast_max_steps()."""
+    H, W = _hw(who, "size", size)
+    near_disp, far_disp = _real(who, "near_disp", near_disp, "> 0", fp32=True), _real(who, "far_disp", far_disp, "> 0", fp32=True)
+    if not near_disp > far_disp:
+        raise ValueError(f"{who}: near_disp {near_disp!r} and far_disp {far_disp!r}: near_disp > far_disp > 0")
+    step = _real(who, "step", step, "> 0", fp32=True)
+    limit = raycast_max_steps()
+    return (H, W), near_disp, far_disp, step, limit if max_steps is None else _integer(who, "max_steps", max_steps, 1, limit)
+
+
+def _volume_dims(who, dims, least=1):
+    if not isinstance(dims, (tuple, list, torch.Size)) or len(dims) != 3 or not all(_is_int(n) and n >= least for n in dims):
+        raise ValueError(f"{who}: dims {dims!r}: (nz, ny, nx), three integers >= {least}")
+    return tuple(int(n) for n in dims)
+
+
+def volume_new(dims, device):
+    """An empty volume of dims = (nz, ny, nx) on `device`: (tsdf, wsum), fp32 [nz,ny,nx] each, tsdf = 1 and wsum = 0."""
+    dims = _volume_dims("volume_new", dims)
+    if torch.device(device).type != "cuda":
+        raise RuntimeError(_CPU_TENSOR)
+    tsdf = torch.empty(dims, dtype=torch.float32, device=device)
+    tsdf.fill_(1.0)
+    return tsdf, torch.zeros(dims, dtype=torch.float32, device=device)
+
+
+def _volume_planes(who, tsdf, wsum, least=1):
+    """The two planes of a volume after their refusals: fp32 on the device, [nz,ny,nx], contiguous (they are used in place), of
+    one shape, neither requiring grad."""
+    for name, t in (("tsdf", tsdf), ("wsum", wsum)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{who}: {name} {type(t).__name__}: a tensor")
+        if t.requires_grad:
+            raise ValueError(f"{who}: {name} requires grad: the volume ops are forward only")
+    _chk(tsdf, wsum)
+    _need(tsdf.dim() == 3 and tsdf.shape == wsum.shape and all(n >= least for n in tsdf.shape),
+          lambda: f"{who}: tsdf {tuple(tsdf.shape)}, wsum {tuple(wsum.shape)}: one shape [nz,ny,nx], every dim >= {least}")
+    _need(tsdf.is_contiguous() and wsum.is_contiguous(), lambda: f"{who}: tsdf and wsum must be contiguous")
+    _need(tsdf.data_ptr() != wsum.data_ptr(), lambda: f"{who}: tsdf and wsum are one tensor")
+    return tuple(int(n) for n in tsdf.shape)
+
+
+def _no_grad_operands(who, **ts):
+    for name, t in ts.items():
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            raise ValueError(f"{who}: {name} requires grad: the volume ops are forward only")
+
+
+@torch.no_grad()
+def volume_integrate(tsdf, wsum, disp, Q, T, origin, voxel, trunc, valid=None, weight=None, max_weight=64.0, min_disp=0.0,
+                     max_disp=None):
+    """Integrate the V views disp ([V,H,W] or [V,1,H,W] fp32, pixels) into the volume (tsdf, wsum) of volume_new, IN PLACE, and
+    return the pair.  Q (float64 CPU [4,4]) is the views' disparity-to-depth matrix, T (float64 CPU [4,4] or [V,4,4]) their
+    world-to-camera poses, origin and voxel place the grid (volume_matrices).  Per voxel, the views in order: the voxel is
+    projected into the view and rounded to the nearest pixel; the pixel must be usable by disparity_reproject's rule (valid:
+    bool or uint8 of disp's shape; min_disp, max_disp) and its weight ([V,H,W] fp32, e.g. 1 / std^2; None: 1) finite and > 0;
+    s = (the pixel's depth) - (the voxel's depth), along the optical axis; a voxel more than trunc behind the surface is left
+    alone, and otherwise tsdf <- (tsdf wsum + min(1, s / trunc) w) / (wsum + w), wsum <- min(wsum + w, max_weight).  One launch,
+    one thread per voxel, no atomics: bit-reproducible; a voxel no view sees keeps its bits.  include/ecm_volume.h states every
+    operation.  A static-scene model; every default is untested for quality."""
+    who = "volume_integrate"
+    trunc, max_weight, lo, hi = check_volume_parameters(trunc, max_weight, min_disp, max_disp)
+    m = volume_matrices(Q, T, origin, voxel)
+    _no_grad_operands(who, disp=disp, valid=valid, weight=weight)
+    nz, ny, nx = _volume_planes(who, tsdf, wsum)
+    d, v = _filter_planes(who, disp, valid)
+    V, H, W = d.shape
+    if m.G.dim() == 3 and m.G.shape[0] != V:
+        raise ValueError(f"{who}: T {tuple(T.shape)} against disp {tuple(d.shape)}: one matrix, or one per view")
+    w = None if weight is None else _c(_plane_like(who, "weight", weight, d, ((torch.float32,)), "fp32"))
+    n = m.G.numel()
+    mats = torch.cat([Q.detach().reshape(-1), m.G.reshape(-1), m.C.reshape(-1)]).to(d.device)        # one host-to-device copy
+    at = mats.data_ptr()
+    _lib.call("ecmv_integrate_fwd", _p(tsdf), _p(wsum), _p(d), _p(v), _p(w), C.c_void_p(at), C.c_void_p(at + 128),
+              C.c_void_p(at + 128 + 8 * n), int(m.G.dim() == 3), nx, ny, nz, V, H, W, trunc, max_weight, lo, hi, _stream())
+    return tsdf, wsum
+
+
+@torch.no_grad()
+def volume_raycast(tsdf, wsum, Q_out, T, origin, voxel, size, near_disp, far_disp, step=0.5, max_steps=None, with_weight=False):
+    """The disparity map out [B,1,H,W] fp32 that the volume (tsdf, wsum; every dim >= 2) shows to the B views T (float64 CPU
+    [4,4]: B = 1, or [B,4,4]; world to camera) with the disparity-to-depth matrix Q_out and size = (H, W).  Per pixel the ray
+    from disparity near_disp to far_disp (near_disp > far_disp > 0) is a straight segment of the grid; it is sampled at
+    n = ceil(length / step) equal intervals (step in voxels; a pixel with n > max_steps is a hole; None: the library's limit), a
+    sample counts where all eight corners of its cell have wsum > 0, and the first front-face zero crossing of the trilinear
+    tsdf between two consecutive samples that count, found by linear interpolation, is mapped back to a disparity; a back-face
+    crossing met first ends the ray.  Holes are +0.0.  with_weight=True returns (out, hit_weight), the trilinear wsum at the
+    crossing.  One launch, one thread per pixel: bit-reproducible.  include/ecm_volume.h states every operation."""
+    who = "volume_raycast"
+    (H, W), near_disp, far_disp, step, max_steps = check_raycast_parameters(size, near_disp, far_disp, step, max_steps)
+    m = volume_matrices(Q_out, T, origin, voxel)
+    nz, ny, nx = _volume_planes(who, tsdf, wsum, least=2)
+    B = m.R.shape[0] if m.R.dim() == 3 else 1
+    n = m.R.numel()
+    mats = torch.cat([m.R.reshape(-1), m.Rinv.reshape(-1)]).to(tsdf.device)
+    at = mats.data_ptr()
+    out = torch.empty(B, 1, H, W, device=tsdf.device, dtype=torch.float32)
+    hit = torch.empty(B, 1, H, W, device=tsdf.device, dtype=torch.float32) if with_weight else None
+    _lib.call("ecmv_raycast_fwd", _p(tsdf), _p(wsum), C.c_void_p(at), C.c_void_p(at + 8 * n), int(m.R.dim() == 3), _p(out), _p(hit),
+              nx, ny, nz, B, H, W, near_disp, far_disp, step, max_steps, _stream())
+    return (out, hit) if with_weight else out
+
+
 # ------------------------------------------------------------------------------------ a5-a7 conv / deconv / GN
 def _pack_conv(w, flip_transpose=False):
     Co, Ci = w.shape[0], w.shape[1]

@@ -55,8 +55,11 @@ __device__ __forceinline__ int ecm_xcd_tile(int id, int n) {
     return x * q + (x < r ? x : r) + (id >> 3);
 }
 
-// 64-lane wave reductions (CDNA wave = 64).
-__device__ __forceinline__ float wave_sum(float v) {
+// 64-lane wave reductions (CDNA wave = 64): a fixed xor butterfly, every lane ends with the same bits.  wave_sum is for any
+// arithmetic type; a reduction that interleaves several values per step, or spans fewer lanes, is not this loop and stays where it is.
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+    static_assert(std::is_arithmetic<T>::value, "wave_sum adds numbers");
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;

@@ -9,9 +9,7 @@
 //            centre's guide values in registers and the spatial exponents of one window row in LDS;
 //   store    two planes, predicated on x < W.
 // No atomics, no inline assembly, no private segment: every register array is indexed by compile-time constants only.
-#include "common.h"
-#include <climits>
-#include <cmath>
+#include "disp_geom.h"
 #include <utility>
 
 namespace {
@@ -23,20 +21,7 @@ constexpr int MEDIAN_R_MAX = 3;               // 7 x 7: 49 values in registers
 constexpr int R_MAX = 8;                      // bilateral: 17 x 17; LDS (1 + C)(TH + 2r)(TW + 2r) + 2r + 1 floats = 38,468 B at C = 4
 constexpr int C_MAX = 4;
 
-// ---- the tile walk ------------------------------------------------------------------------------------------------------------
-struct Tiles {
-    int tx, ty;                               // tiles along x and y
-    long long n;                              // B * tx * ty
-};
-
-__host__ __device__ inline Tiles tiles_of(int B, int H, int W) {
-    Tiles t;
-    t.tx = (W + TW - 1) / TW;
-    t.ty = (H + TH - 1) / TH;
-    t.n = (long long)B * t.tx * t.ty;
-    return t;
-}
-
+// ---- staging: the tile walk is disp_geom.h's --------------------------------------------------------------------------------------
 // Stage rows y0-r .. y0+TH-1+r, columns x0-r .. x0+TW-1+r of the plane `src` (of image b) into dst [TH+2r][TW+2r].  MASKED: the
 // disparity plane, NaN where the sample is not usable; else a guide plane, 0 outside the image (never looked at: d is NaN there).
 template <bool MASKED>
@@ -44,17 +29,15 @@ __device__ __forceinline__ void stage_plane(float* dst, const float* __restrict_
                                             int H, int W, int y0, int x0, int r) {
     const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
     const int sw = TW + 2 * r, sh = TH + 2 * r;
-    const float inf = __builtin_inff(), nan = __builtin_nanf("");
     for (int ly = wave; ly < sh; ly += NWAVE) {
         const int y = y0 - r + ly;
         const bool yin = y >= 0 && y < H;                                  // wave-uniform
         for (int lx = lane; lx < sw; lx += WAVE) {
             const int x = x0 - r + lx;
-            float v = MASKED ? nan : 0.f;
+            float v = MASKED ? __builtin_nanf("") : 0.f;
             if (yin && x >= 0 && x < W) {
                 const size_t at = (size_t)y * W + x;
-                v = src[at];
-                if (MASKED && (!(fabsf(v) < inf) || (valid && valid[at] == 0))) v = nan;
+                v = MASKED ? ecm_disp_or_nan(src, valid, at) : src[at];
             }
             dst[ly * sw + lx] = v;
         }
@@ -107,7 +90,7 @@ __global__ __launch_bounds__(THREADS) void disp_median_fwd(const float* __restri
     constexpr int K = 2 * R + 1, N = K * K, SW = TW + 2 * R, SH = TH + 2 * R;
     __shared__ float D[SH * SW];
     const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-    const Tiles t = tiles_of(B, H, W);
+    const Tiles2D t = ecm_tiles_of<TW, TH>(B, H, W);
     const size_t image = (size_t)H * W, plane = (size_t)B * image;
     const float inf = __builtin_inff();
 
@@ -162,7 +145,7 @@ __global__ __launch_bounds__(THREADS) void disp_bilateral_fwd(const float* __res
     float* G = lds + SH * SW;
     float* S = lds + (1 + C) * SH * SW;
     const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-    const Tiles t = tiles_of(B, H, W);
+    const Tiles2D t = ecm_tiles_of<TW, TH>(B, H, W);
     const size_t image = (size_t)H * W, plane = (size_t)B * image;
 
     if ((int)threadIdx.x < K) S[threadIdx.x] = ks * (float)(((int)threadIdx.x - r) * ((int)threadIdx.x - r));
@@ -213,7 +196,7 @@ __global__ __launch_bounds__(THREADS) void disp_bilateral_fwd(const float* __res
 inline bool sizes_ok(int B, int H, int W) { return B > 0 && H > 0 && W > 0; }
 inline bool too_large(int B, int H, int W) { return (long long)B * H * W > INT_MAX; }
 inline int grid_of(int B, int H, int W) {
-    const long long n = tiles_of(B, H, W).n;
+    const long long n = ecm_tiles_of<TW, TH>(B, H, W).n;
     return (int)(n < GRID ? n : GRID);
 }
 

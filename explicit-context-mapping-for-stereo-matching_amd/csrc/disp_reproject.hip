@@ -1,9 +1,8 @@
 // Disparity reprojection (include/ecm_geometry.h has the definitions): [X Y Z W]^T = Q_b [x y d 1]^T in
 // fp64, the point (X/W, Y/W, Z/W) rounded once to fp32, as a dense map [B,3,H,W] and as a packed cloud of the usable pixels in
 // row-major order.  HBM-bound (4-5 B read, 12-28 B written per pixel), so the fp64 arithmetic is free.
-// A tile is TILE = THREADS x ITEMS consecutive pixels of ONE image, a workgroup owns one tile: Q is uniform per workgroup.  Item k
-// of thread t is pixel k * THREADS + t of the tile, so a wave reads 64 consecutive pixels at a time, and the pixel order of a tile
-// is (item, wave, lane).
+// A workgroup owns one linear pixel tile (disp_geom.h): Q is uniform per workgroup, and the pixel order of a tile is (item, wave,
+// lane).
 //   dense   one launch: every pixel's point or +0.0, and the mask.
 //   cloud   three launches, a stable stream compaction:
 //     count   the usable pixels of each tile: one ballot per (item, wave), popcounts summed per wave, one int per tile;
@@ -13,39 +12,25 @@
 //             offset + the counts of the (item, wave) pairs before its own + mbcnt of its ballot below its lane.
 // No workgroup waits for another (the rule disp_speckle.hip states), no atomics of any kind, no scratch memory: the order is the
 // pixel order whatever the scheduling.
-#include "common.h"
+#include "disp_geom.h"
 #include "../../include/ecm_geometry.h"
-#include <climits>
-#include <cmath>
 
 namespace {
 
-constexpr int THREADS = 256, WAVE = 64, NWAVE = THREADS / WAVE;
-constexpr int ITEMS = 8;                      // pixels of a tile per thread: eight independent loads in flight
-constexpr int TILE = THREADS * ITEMS;
-constexpr int MAX_TILES = 16777215;           // B * T: the launch's global size (tiles x THREADS) stays below 2^32
+using namespace ecm_pix;
 constexpr int MAX_ATTRS = 4;
 
 typedef unsigned long long u64;
 
-struct Range {
-    float lo, hi;                             // usable: lo < d <= hi
-};
-
-__device__ __forceinline__ double row_of(const double* __restrict__ q, double x, double y, double d) {
-#pragma clang fp contract(off)
-    return ((q[0] * x + q[1] * y) + q[2] * d) + q[3];
-}
-
 // W of the pixel and whether it is usable; every comparison is on input bits or on the one fp64 value W
-__device__ __forceinline__ bool usable(const double* __restrict__ q, float d, bool v, int x, int y, Range r, double& w) {
-    w = row_of(q + 12, (double)x, (double)y, (double)d);
-    return v && fabsf(d) < __builtin_inff() && d > r.lo && d <= r.hi && fabs(w) < __builtin_inf() && w != 0.0;
+__device__ __forceinline__ bool usable(const double* __restrict__ q, float d, bool v, int x, int y, DispRange r, double& w) {
+    w = ecm_row4(q + 12, (double)x, (double)y, (double)d);
+    return ecm_disp_usable(d, v, r) && ecm_nonzero_finite(w);
 }
 
 __device__ __forceinline__ float3 point(const double* __restrict__ q, float d, int x, int y, double w) {
     const double fx = (double)x, fy = (double)y, fd = (double)d;
-    const double X = row_of(q, fx, fy, fd), Y = row_of(q + 4, fx, fy, fd), Z = row_of(q + 8, fx, fy, fd);
+    const double X = ecm_row4(q, fx, fy, fd), Y = ecm_row4(q + 4, fx, fy, fd), Z = ecm_row4(q + 8, fx, fy, fd);
     return make_float3((float)(X / w), (float)(Y / w), (float)(Z / w));
 }
 
@@ -54,23 +39,11 @@ __device__ __forceinline__ int rank_in_wave(u64 ballot) {
     return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ballot, 0u));
 }
 
-struct Tile {
-    int b;                                    // image
-    unsigned first;                           // first pixel of the tile within the image
-};
-
-__device__ __forceinline__ Tile tile_of(int T) {
-    Tile t;
-    t.b = (int)(blockIdx.x / (unsigned)T);
-    t.first = (blockIdx.x % (unsigned)T) * (unsigned)TILE;
-    return t;
-}
-
 // ---- dense -------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(THREADS) void reproject_dense(const float* __restrict__ disp, const unsigned char* __restrict__ valid,
                                                            const double* __restrict__ Q, int q_stride, float* __restrict__ xyz,
-                                                           unsigned char* __restrict__ mask, int HW, int W, int T, Range r) {
-    const Tile t = tile_of(T);
+                                                           unsigned char* __restrict__ mask, int HW, int W, int T, DispRange r) {
+    const PixTile t = ecm_pix_tile(T);
     const double* q = Q + (size_t)t.b * q_stride;
     const size_t img = (size_t)t.b * HW;
     float* out = xyz + 3 * img;
@@ -80,7 +53,8 @@ __global__ __launch_bounds__(THREADS) void reproject_dense(const float* __restri
         if (pix >= (unsigned)HW) continue;
         const float d = disp[img + pix];
         const bool v = !valid || valid[img + pix] != 0;
-        const int y = (int)(pix / (unsigned)W), x = (int)(pix - (unsigned)y * (unsigned)W);
+        int x, y;
+        ecm_pix_xy(pix, W, x, y);
         double w;
         const bool ok = usable(q, d, v, x, y, r, w);
         const float3 p = ok ? point(q, d, x, y, w) : make_float3(0.f, 0.f, 0.f);
@@ -94,9 +68,9 @@ __global__ __launch_bounds__(THREADS) void reproject_dense(const float* __restri
 // ---- cloud (a): per-tile counts ----------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(THREADS) void cloud_count(const float* __restrict__ disp, const unsigned char* __restrict__ valid,
                                                        const double* __restrict__ Q, int q_stride, int* __restrict__ counts,
-                                                       int HW, int W, int T, Range r) {
+                                                       int HW, int W, int T, DispRange r) {
     __shared__ int per_wave[NWAVE];
-    const Tile t = tile_of(T);
+    const PixTile t = ecm_pix_tile(T);
     const double* q = Q + (size_t)t.b * q_stride;
     const size_t img = (size_t)t.b * HW;
     int n = 0;                                                        // wave-uniform: the wave's usable pixels
@@ -107,7 +81,8 @@ __global__ __launch_bounds__(THREADS) void cloud_count(const float* __restrict__
         if (pix < (unsigned)HW) {
             const float d = disp[img + pix];
             const bool v = !valid || valid[img + pix] != 0;
-            const int y = (int)(pix / (unsigned)W), x = (int)(pix - (unsigned)y * (unsigned)W);
+            int x, y;
+            ecm_pix_xy(pix, W, x, y);
             double w;
             ok = usable(q, d, v, x, y, r, w);
         }
@@ -163,10 +138,10 @@ __global__ __launch_bounds__(THREADS) void cloud_emit(const float* __restrict__ 
                                                       const double* __restrict__ Q, int q_stride, const float* __restrict__ attrs,
                                                       const int* __restrict__ tile_offset, float* __restrict__ points,
                                                       float* __restrict__ xyz, unsigned char* __restrict__ mask, int HW, int W, int T,
-                                                      Range r) {
+                                                      DispRange r) {
     __shared__ __align__(16) int count[ITEMS * NWAVE];                // [item][wave]
     static_assert(NWAVE == 4, "an item's counts are read as one int4");
-    const Tile t = tile_of(T);
+    const PixTile t = ecm_pix_tile(T);
     const double* q = Q + (size_t)t.b * q_stride;
     const size_t img = (size_t)t.b * HW;
     const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
@@ -182,7 +157,8 @@ __global__ __launch_bounds__(THREADS) void cloud_emit(const float* __restrict__ 
         if (pix < (unsigned)HW) {
             d[k] = disp[img + pix];
             const bool v = !valid || valid[img + pix] != 0;
-            const int y = (int)(pix / (unsigned)W), x = (int)(pix - (unsigned)y * (unsigned)W);
+            int x, y;
+            ecm_pix_xy(pix, W, x, y);
             double w;
             ok = usable(q, d[k], v, x, y, r, w);
         }
@@ -205,8 +181,9 @@ __global__ __launch_bounds__(THREADS) void cloud_emit(const float* __restrict__ 
         const bool ok = (ok_bits >> k) & 1u;
         float3 p = make_float3(0.f, 0.f, 0.f);
         if (ok) {
-            const int y = (int)(pix / (unsigned)W), x = (int)(pix - (unsigned)y * (unsigned)W);
-            const double w = row_of(q + 12, (double)x, (double)y, (double)d[k]);
+            int x, y;
+            ecm_pix_xy(pix, W, x, y);
+            const double w = ecm_row4(q + 12, (double)x, (double)y, (double)d[k]);
             p = point(q, d[k], x, y, w);
             float* row = points + (size_t)(before + below[k]) * (3 + C);
             row[0] = p.x;
@@ -231,15 +208,8 @@ int tiles_per_image(int B, int H, int W, int& code) {
     if (B < 1 || H < 1 || W < 1) return 0;
     code = ECM_EUNSUP;
     const long long hw = (long long)H * W;
-    if (hw * B > INT_MAX) return 0;
-    const long long T = (hw + TILE - 1) / TILE;
-    if (T * B > MAX_TILES) return 0;
-    code = 0;
-    return (int)T;
-}
-
-bool range_ok(float min_disp, float max_disp) {
-    return std::isfinite(min_disp) && !std::isnan(max_disp) && max_disp >= min_disp;
+    if (hw * B > INT_MAX) return 0;           // the batch: the cloud's rows and the scan's carry are ints
+    return ecm_pix_tiles(hw, B, code);
 }
 
 }  // namespace
@@ -254,14 +224,13 @@ extern "C" long long ecmg_point_cloud_scratch_bytes(int B, int H, int W) {
 
 extern "C" int ecmg_reproject_fwd(const float* disp, const unsigned char* valid, const double* Q, int q_per_image, float* xyz,
                                   unsigned char* mask, int B, int H, int W, float min_disp, float max_disp, void* stream) {
-    ECM_CHECK_ARG(disp && Q && xyz && range_ok(min_disp, max_disp));
-    ECM_CHECK_ARG((const void*)xyz != (const void*)disp && (const void*)xyz != (const void*)valid &&
-                  (!mask || ((const void*)mask != (const void*)disp && mask != valid)));
+    ECM_CHECK_ARG(disp && Q && xyz && ecm_disp_range_ok(min_disp, max_disp));
+    ECM_CHECK_ARG(ecm_no_alias({xyz, mask}, {disp, valid}));
     int code;
     const int T = tiles_per_image(B, H, W, code);
     if (!T) return code;
-    const Range r = {min_disp, max_disp};
-    hipLaunchKernelGGL(reproject_dense, dim3(B * T), dim3(THREADS), 0, ecm_stream(stream), disp, valid, Q, q_per_image ? 16 : 0, xyz,
+    const DispRange r = {min_disp, max_disp};
+    hipLaunchKernelGGL(reproject_dense, dim3(B * T), dim3(THREADS), 0, ecm_stream(stream), disp, valid, Q, ecm_mat_stride(q_per_image), xyz,
                        mask, H * W, W, T, r);
     return ECM_LAUNCH_RESULT();
 }
@@ -269,31 +238,22 @@ extern "C" int ecmg_reproject_fwd(const float* disp, const unsigned char* valid,
 extern "C" int ecmg_point_cloud_fwd(const float* disp, const unsigned char* valid, const double* Q, int q_per_image, const float* attrs,
                                     int C, float* points, long long* offsets, float* xyz, unsigned char* mask, void* scratch,
                                     long long scratch_bytes, int B, int H, int W, float min_disp, float max_disp, void* stream) {
-    ECM_CHECK_ARG(disp && Q && points && offsets && scratch && range_ok(min_disp, max_disp));
+    ECM_CHECK_ARG(disp && Q && points && offsets && scratch && ecm_disp_range_ok(min_disp, max_disp));
     ECM_CHECK_ARG(C >= 0 && C <= MAX_ATTRS && (C == 0 || attrs));
-    const void* const outs[] = {points, offsets, xyz, mask, scratch};
-    for (const void* o : outs)
-        ECM_CHECK_ARG(!o || (o != (const void*)disp && o != (const void*)valid && o != (const void*)Q && o != (const void*)attrs));
+    ECM_CHECK_ARG(ecm_no_alias({points, offsets, xyz, mask, scratch}, {disp, valid, Q, attrs}));
     int code;
     const int T = tiles_per_image(B, H, W, code);
     if (!T) return code;
     if (scratch_bytes < ecmg_point_cloud_scratch_bytes(B, H, W)) return ECM_ESCRATCH;
-    const Range r = {min_disp, max_disp};
-    const int HW = H * W, q_stride = q_per_image ? 16 : 0, n = B * T;
+    const DispRange r = {min_disp, max_disp};
+    const int HW = H * W, q_stride = ecm_mat_stride(q_per_image), n = B * T;
     int* tiles = static_cast<int*>(scratch);
     hipStream_t s = ecm_stream(stream);
     hipLaunchKernelGGL(cloud_count, dim3(n), dim3(THREADS), 0, s, disp, valid, Q, q_stride, tiles, HW, W, T, r);
     hipLaunchKernelGGL(cloud_scan, dim3(1), dim3(THREADS), 0, s, tiles, offsets, n, T, B);
-#define ECMG_EMIT(c)                                                                                                            \
-    hipLaunchKernelGGL(cloud_emit<c>, dim3(n), dim3(THREADS), 0, s, disp, valid, Q, q_stride, attrs, (const int*)tiles, points, \
-                       xyz, mask, HW, W, T, r)
-    switch (C) {
-        case 0: ECMG_EMIT(0); break;
-        case 1: ECMG_EMIT(1); break;
-        case 2: ECMG_EMIT(2); break;
-        case 3: ECMG_EMIT(3); break;
-        default: ECMG_EMIT(4); break;
-    }
-#undef ECMG_EMIT
-    return ECM_LAUNCH_RESULT();
+    return ecm_dispatch<0, 1, 2, 3, 4>(C, [&](auto c) {
+        hipLaunchKernelGGL(cloud_emit<decltype(c)::value>, dim3(n), dim3(THREADS), 0, s, disp, valid, Q, q_stride, attrs,
+                           (const int*)tiles, points, xyz, mask, HW, W, T, r);
+        return ECM_LAUNCH_RESULT();
+    });
 }

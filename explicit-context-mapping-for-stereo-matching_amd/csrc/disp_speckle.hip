@@ -14,8 +14,7 @@
 // Termination does not depend on scheduling: a parent is never larger than its child, so every step of a `find` and every retry
 // of a `unite` strictly decreases a non-negative integer; no workgroup waits for another, there is no loop on a flag.  Integer
 // atomics only (min on parents, add on counts), no inline assembly, no private segment, no scratch buffer.
-#include "common.h"
-#include <climits>
+#include "disp_geom.h"
 
 namespace {
 
@@ -56,26 +55,7 @@ __device__ __forceinline__ void unite(int* parent, int a, int b) {
     }                                                                       // max(a, b) has decreased: the loop ends
 }
 
-// ---- the tile walk and the samples -----------------------------------------------------------------------------------------------
-struct Tiles {
-    int tx, ty;                               // tiles along x and y
-    long long n;                              // B * tx * ty
-};
-
-__host__ __device__ inline Tiles tiles_of(int B, int H, int W) {
-    Tiles t;
-    t.tx = (W + TW - 1) / TW;
-    t.ty = (H + TH - 1) / TH;
-    t.n = (long long)B * t.tx * t.ty;
-    return t;
-}
-
-// d at `at`, NaN where the sample is not usable: then every comparison with it is false
-__device__ __forceinline__ float sample(const float* __restrict__ d, const unsigned char* __restrict__ valid, size_t at) {
-    const float v = d[at];
-    return fabsf(v) < __builtin_inff() && (!valid || valid[at] != 0) ? v : __builtin_nanf("");
-}
-
+// the tile walk and the samples (NaN where not usable: then every comparison is false) are disp_geom.h's
 __device__ __forceinline__ bool joined(float a, float b, float max_diff) { return fabsf(a - b) <= max_diff; }
 
 // ---- local: the segments of each tile ----------------------------------------------------------------------------------------------
@@ -86,7 +66,7 @@ __global__ __launch_bounds__(THREADS) void speckle_local(const float* __restrict
     __shared__ int P[TH * TW];                // parents, as indices into the tile
     __shared__ int N[TH * TW];                // pixel counts, at the roots
     const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-    const Tiles t = tiles_of(B, H, W);
+    const Tiles2D t = ecm_tiles_of<TW, TH>(B, H, W);
     const size_t image = (size_t)H * W;
 
     for (long long tile = blockIdx.x; tile < t.n; tile += gridDim.x) {
@@ -103,7 +83,7 @@ __global__ __launch_bounds__(THREADS) void speckle_local(const float* __restrict
         for (int k = 0; k < ROWS; ++k) {
             const int ty = wave + k * NWAVE, y = y0 + ty, i = ty * TW + lane;
             v[k] = __builtin_nanf("");
-            if (y < H && x < W) v[k] = sample(d, valid, b * image + (size_t)y * W + x);
+            if (y < H && x < W) v[k] = ecm_disp_or_nan(d, valid, b * image + (size_t)y * W + x);
             const float vl = __shfl_up(v[k], 1, WAVE);
             left[k] = lane > 0 && joined(v[k], vl, max_diff);
             const bool usable = v[k] == v[k];
@@ -163,7 +143,7 @@ __global__ __launch_bounds__(THREADS) void speckle_local(const float* __restrict
 // another that is left out on the strength of it.  The parents are read and written here by agent-scope atomics only.
 __global__ __launch_bounds__(THREADS) void speckle_merge(const float* __restrict__ d, const unsigned char* __restrict__ valid,
                                                          int* label, int B, int H, int W, float max_diff) {
-    const Tiles t = tiles_of(B, H, W);
+    const Tiles2D t = ecm_tiles_of<TW, TH>(B, H, W);
     const size_t image = (size_t)H * W;
     const long long across = (long long)(t.ty - 1) * W, per = across + (long long)(t.tx - 1) * H, total = per * B;
     for (long long e = (long long)blockIdx.x * THREADS + threadIdx.x; e < total; e += (long long)gridDim.x * THREADS) {
@@ -182,11 +162,11 @@ __global__ __launch_bounds__(THREADS) void speckle_merge(const float* __restrict
         const float* di = d + b * image;
         const unsigned char* vi = valid ? valid + b * image : nullptr;
         const int p = y * W + x, q = p - back;
-        const float vp = sample(di, vi, p), vq = sample(di, vi, q);
+        const float vp = ecm_disp_or_nan(di, vi, p), vq = ecm_disp_or_nan(di, vi, q);
         if (!joined(vp, vq, max_diff)) continue;
         if (inner) {
             const int side = back == W ? 1 : W;                             // to the previous pair along the border
-            const float vps = sample(di, vi, p - side), vqs = sample(di, vi, q - side);
+            const float vps = ecm_disp_or_nan(di, vi, p - side), vqs = ecm_disp_or_nan(di, vi, q - side);
             if (joined(vp, vps, max_diff) && joined(vq, vqs, max_diff) && joined(vps, vqs, max_diff)) continue;
         }
         unite<__HIP_MEMORY_SCOPE_AGENT>(label + b * image, p, q);
@@ -242,7 +222,7 @@ extern "C" int ecm_disp_speckle_fwd(const float* d, const unsigned char* valid, 
     ECM_CHECK_ARG(d && out && segments && B > 0 && H > 0 && W > 0 && max_size >= 0 && max_diff >= 0.f &&
                   max_diff < __builtin_inff());
     if ((long long)B * H * W > INT_MAX) return ECM_EUNSUP;
-    const Tiles t = tiles_of(B, H, W);
+    const Tiles2D t = ecm_tiles_of<TW, TH>(B, H, W);
     const int image = H * W, n = B * image;
     int* label = segments;
     int* size = segments + n;

@@ -11,10 +11,8 @@
 //              that can lie inside the volume's box (a slab test with a margin of one sample on either side); every sample in
 //              between is visited.
 // The whole file is compiled with contraction off: every product and sum is one IEEE operation, as the header states them.
-#include "common.h"
+#include "disp_geom.h"
 #include "../../include/ecm_volume.h"
-#include <climits>
-#include <cmath>
 #include <cstdint>
 
 #pragma clang fp contract(off)
@@ -28,16 +26,10 @@ constexpr int MAX_GROUPS = 16777215;                      // workgroups of a lau
 constexpr int MAX_STEPS = 65536;
 
 struct Gates {
-    float lo, hi, max_weight;                 // usable: lo < d <= hi
+    DispRange range;
+    float max_weight;
     double trunc;
 };
-
-// ecm_geometry.h's row
-__device__ __forceinline__ double row_of(const double* __restrict__ m, double a, double b, double c) {
-    return ((m[0] * a + m[1] * b) + m[2] * c) + m[3];
-}
-
-__device__ __forceinline__ bool finite(double v) { return fabs(v) < __builtin_inf(); }
 
 // ---- integrate -----------------------------------------------------------------------------------------------------------------
 // one view's update of one voxel: X = tsdf, N = wsum
@@ -45,22 +37,22 @@ __device__ __forceinline__ void integrate_view(float& X, float& N, double di, do
                                                const double* __restrict__ Cm, const double* __restrict__ Q,
                                                const float* __restrict__ disp, const unsigned char* __restrict__ valid,
                                                const float* __restrict__ weight, int H, int W, const Gates& g) {
-    const double h3 = row_of(G + 12, di, dj, dk);
-    const double u = row_of(G, di, dj, dk) / h3, v = row_of(G + 4, di, dj, dk) / h3, dv = row_of(G + 8, di, dj, dk) / h3;
-    if (!(finite(u) && finite(v) && finite(dv) && dv > 0.0)) return;
+    const double h3 = ecm_row4(G + 12, di, dj, dk);
+    const double u = ecm_row4(G, di, dj, dk) / h3, v = ecm_row4(G + 4, di, dj, dk) / h3, dv = ecm_row4(G + 8, di, dj, dk) / h3;
+    if (!(ecm_finite(u) && ecm_finite(v) && ecm_finite(dv) && dv > 0.0)) return;
     const double fx = floor(u + 0.5), fy = floor(v + 0.5);
     if (!(fx >= 0.0 && fx <= (double)(W - 1) && fy >= 0.0 && fy <= (double)(H - 1))) return;
     const size_t pix = (size_t)(int)fy * W + (int)fx;                       // 0 <= pix < H * W
     const float d = disp[pix];
-    if (!((!valid || valid[pix] != 0) && fabsf(d) < __builtin_inff() && d > g.lo && d <= g.hi)) return;
+    if (!ecm_disp_usable(d, !valid || valid[pix] != 0, g.range)) return;
     const float w = weight ? weight[pix] : 1.f;
     if (!(w > 0.f && w < __builtin_inff())) return;
     const double fd = (double)d;
-    const double P3 = row_of(Q + 12, fx, fy, fd);
-    if (!(finite(P3) && P3 != 0.0)) return;
-    const double z_meas = row_of(Q + 8, fx, fy, fd) / P3;
-    const double z_vox = row_of(Cm + 8, di, dj, dk);
-    if (!(finite(z_meas) && z_meas > 0.0 && finite(z_vox) && z_vox > 0.0)) return;
+    const double P3 = ecm_row4(Q + 12, fx, fy, fd);
+    if (!ecm_nonzero_finite(P3)) return;
+    const double z_meas = ecm_row4(Q + 8, fx, fy, fd) / P3;
+    const double z_vox = ecm_row4(Cm + 8, di, dj, dk);
+    if (!(ecm_finite(z_meas) && z_meas > 0.0 && ecm_finite(z_vox) && z_vox > 0.0)) return;
     const double s = z_meas - z_vox;
     if (s < -g.trunc) return;
     const float t = (float)fmin(1.0, s / g.trunc);
@@ -165,13 +157,13 @@ __global__ __launch_bounds__(THREADS) void raycast_kernel(const float* __restric
     const double fx = (double)x, fy = (double)y;
 
     float result = 0.f, weight = 0.f;
-    const double hn = row_of(R + 12, fx, fy, near_disp), hf = row_of(R + 12, fx, fy, far_disp);
-    const double gx = row_of(R, fx, fy, near_disp) / hn, gy = row_of(R + 4, fx, fy, near_disp) / hn, gz = row_of(R + 8, fx, fy, near_disp) / hn;
-    const double ex = row_of(R, fx, fy, far_disp) / hf, ey = row_of(R + 4, fx, fy, far_disp) / hf, ez = row_of(R + 8, fx, fy, far_disp) / hf;
+    const double hn = ecm_row4(R + 12, fx, fy, near_disp), hf = ecm_row4(R + 12, fx, fy, far_disp);
+    const double gx = ecm_row4(R, fx, fy, near_disp) / hn, gy = ecm_row4(R + 4, fx, fy, near_disp) / hn, gz = ecm_row4(R + 8, fx, fy, near_disp) / hn;
+    const double ex = ecm_row4(R, fx, fy, far_disp) / hf, ey = ecm_row4(R + 4, fx, fy, far_disp) / hf, ez = ecm_row4(R + 8, fx, fy, far_disp) / hf;
     const double dx = ex - gx, dy = ey - gy, dz = ez - gz;
     const double len = sqrt((dx * dx + dy * dy) + dz * dz);
     const double nd = ceil(len / step);
-    const bool ends = finite(gx) && finite(gy) && finite(gz) && finite(ex) && finite(ey) && finite(ez);
+    const bool ends = ecm_finite(gx) && ecm_finite(gy) && ecm_finite(gz) && ecm_finite(ex) && ecm_finite(ey) && ecm_finite(ez);
     if (ends && nd >= 1.0 && nd <= (double)max_steps) {                     // a NaN fails both comparisons
         const int n = (int)nd;
         double s_lo = 0.0, s_hi = 1.0;
@@ -201,7 +193,7 @@ __global__ __launch_bounds__(THREADS) void raycast_kernel(const float* __restric
                 if (f0 > 0.0 && f <= 0.0) {
                     const double a = f0 / (f0 - f);
                     const double qx = px0 + (px - px0) * a, qy = py0 + (py - py0) * a, qz = pz0 + (pz - pz0) * a;
-                    result = (float)(row_of(Ri + 8, qx, qy, qz) / row_of(Ri + 12, qx, qy, qz));
+                    result = (float)(ecm_row4(Ri + 8, qx, qy, qz) / ecm_row4(Ri + 12, qx, qy, qz));
                     if (hit_weight) {
                         const double wx = fmin(fmax(floor(qx), 0.0), (double)(nx - 2)), wy = fmin(fmax(floor(qy), 0.0), (double)(ny - 2));
                         const double wz = fmin(fmax(floor(qz), 0.0), (double)(nz - 2));
@@ -221,8 +213,6 @@ __global__ __launch_bounds__(THREADS) void raycast_kernel(const float* __restric
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
-bool positive(float v) { return std::isfinite(v) && v > 0.f; }
-
 bool voxels_fit(int nx, int ny, int nz) { return (long long)nx * ny * nz <= INT_MAX; }   // after nx, ny, nz >= 1: nx * ny <= 2^62
 
 }  // namespace
@@ -232,27 +222,21 @@ extern "C" int ecmv_integrate_fwd(float* tsdf, float* wsum, const float* disp, c
                                   int H, int W, float trunc, float max_weight, float min_disp, float max_disp, void* stream) {
     ECM_CHECK_ARG(tsdf && wsum && disp && Q && G && C);
     ECM_CHECK_ARG(nx >= 1 && ny >= 1 && nz >= 1 && V >= 1 && H >= 1 && W >= 1);
-    ECM_CHECK_ARG(positive(trunc) && positive(max_weight));
-    ECM_CHECK_ARG(std::isfinite(min_disp) && !std::isnan(max_disp) && max_disp >= min_disp);
-    const void* const ins[] = {disp, valid, weight, Q, G, C};
-    for (const void* i : ins) ECM_CHECK_ARG((const void*)tsdf != i && (const void*)wsum != i);
-    ECM_CHECK_ARG(tsdf != wsum);
+    ECM_CHECK_ARG(ecm_positive(trunc) && ecm_positive(max_weight));
+    ECM_CHECK_ARG(ecm_disp_range_ok(min_disp, max_disp));
+    ECM_CHECK_ARG(ecm_no_alias({tsdf, wsum}, {disp, valid, weight, Q, G, C}) && tsdf != wsum);
     if ((long long)nx * ny > INT_MAX || !voxels_fit(nx, ny, nz) || (long long)H * W > INT_MAX) return ECM_EUNSUP;
     const bool wide = nx % 4 == 0 && ((uintptr_t)tsdf | (uintptr_t)wsum) % 16 == 0;
     const long long per = (long long)BRICK_X * (wide ? 4 : 1);
     const long long bx = (nx + per - 1) / per, by = (ny + BRICK_Y - 1) / BRICK_Y, bz = (nz + BRICK_Z - 1) / BRICK_Z;
     if (bx * by * bz > MAX_GROUPS) return ECM_EUNSUP;
-    const Gates g = {min_disp, max_disp, max_weight, (double)trunc};
-    const int m_stride = m_per_view ? 16 : 0;
-    hipStream_t s = ecm_stream(stream);
+    const Gates g = {{min_disp, max_disp}, max_weight, (double)trunc};
     const dim3 grid((unsigned)(bx * by * bz));
-    if (wide)
-        hipLaunchKernelGGL(integrate_kernel<4>, grid, dim3(THREADS), 0, s, tsdf, wsum, disp, valid, weight, Q, G, C, m_stride, nx, ny,
-                           nz, (int)bx, (int)by, V, H, W, g);
-    else
-        hipLaunchKernelGGL(integrate_kernel<1>, grid, dim3(THREADS), 0, s, tsdf, wsum, disp, valid, weight, Q, G, C, m_stride, nx, ny,
-                           nz, (int)bx, (int)by, V, H, W, g);
-    return ECM_LAUNCH_RESULT();
+    return ecm_dispatch<1, 4>(wide ? 4 : 1, [&](auto vec) {
+        hipLaunchKernelGGL(integrate_kernel<decltype(vec)::value>, grid, dim3(THREADS), 0, ecm_stream(stream), tsdf, wsum, disp, valid,
+                           weight, Q, G, C, ecm_mat_stride(m_per_view), nx, ny, nz, (int)bx, (int)by, V, H, W, g);
+        return ECM_LAUNCH_RESULT();
+    });
 }
 
 extern "C" int ecmv_raycast_max_steps(void) { return MAX_STEPS; }
@@ -262,16 +246,14 @@ extern "C" int ecmv_raycast_fwd(const float* tsdf, const float* wsum, const doub
                                 float step, int max_steps, void* stream) {
     ECM_CHECK_ARG(tsdf && wsum && R && Rinv && out);
     ECM_CHECK_ARG(nx >= 2 && ny >= 2 && nz >= 2 && B >= 1 && H >= 1 && W >= 1 && max_steps >= 1);
-    ECM_CHECK_ARG(positive(step) && positive(far_disp) && std::isfinite(near_disp) && near_disp > far_disp);
-    const void* const ins[] = {tsdf, wsum, R, Rinv};
-    for (const void* i : ins) ECM_CHECK_ARG((const void*)out != i && (!hit_weight || (const void*)hit_weight != i));
-    ECM_CHECK_ARG(out != hit_weight);
+    ECM_CHECK_ARG(ecm_positive(step) && ecm_positive(far_disp) && std::isfinite(near_disp) && near_disp > far_disp);
+    ECM_CHECK_ARG(ecm_no_alias({out, hit_weight}, {tsdf, wsum, R, Rinv}) && out != hit_weight);
     if ((long long)nx * ny > INT_MAX || !voxels_fit(nx, ny, nz) || (long long)H * W > INT_MAX) return ECM_EUNSUP;
     if (max_steps > MAX_STEPS) return ECM_EUNSUP;
     const long long tiles_x = ((long long)W + TILE - 1) / TILE, tiles_y = ((long long)H + TILE - 1) / TILE;
     if (tiles_x * tiles_y * B > MAX_GROUPS) return ECM_EUNSUP;
     hipLaunchKernelGGL(raycast_kernel, dim3((unsigned)(tiles_x * tiles_y * B)), dim3(THREADS), 0, ecm_stream(stream), tsdf, wsum, R, Rinv,
-                       m_per_view ? 16 : 0, out, hit_weight, nx, ny, nz, H, W, (int)tiles_x, (int)(tiles_x * tiles_y), (double)near_disp,
+                       ecm_mat_stride(m_per_view), out, hit_weight, nx, ny, nz, H, W, (int)tiles_x, (int)(tiles_x * tiles_y), (double)near_disp,
                        (double)far_disp, (double)step, max_steps);
     return ECM_LAUNCH_RESULT();
 }

@@ -1,9 +1,7 @@
 // Temporal carry of a disparity map (include/ecm_temporal.h has the definitions): the z-buffered forward warp
 // of a disparity map by a 4x4 fp64 matrix M = Q_out^-1 T Q -- a 2-D scatter, where disp_splat.hip stays inside a row and inside
 // LDS -- and the per-pixel fusion of the warped state with the next frame's own estimate.
-// A tile is TILE = THREADS x ITEMS consecutive pixels of ONE image, a workgroup owns one tile (the tile shape of
-// disp_reproject.hip): M is uniform per workgroup.  Item k of thread t is pixel k * THREADS + t of the tile, so a wave reads 64
-// consecutive pixels at a time.
+// A workgroup owns one linear pixel tile (disp_geom.h): M is uniform per workgroup.
 //   clear    hipMemsetAsync of the keys, one 8-byte word per pixel of the batch;
 //   scatter  every pixel: the usable rule, [a b c w] = M [x y d 1] in fp64, the candidate rule, the 64-bit key (the bits of the new
 //            disparity above the source's linear index), and an integer atomic max of it on each of its one to four landing
@@ -13,67 +11,40 @@
 //   fuse     one elementwise launch: the scalar Kalman update of include/ecm_temporal.h, fp32 in the stated order.
 // The only atomics are integer maxima and no workgroup waits for another (the rule disp_speckle.hip states): the result does not
 // depend on the order of arrival and is bit-reproducible.  No LDS, no scratch memory.
-#include "common.h"
+#include "disp_geom.h"
 #include "../../include/ecm_temporal.h"
-#include <climits>
-#include <cmath>
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int ITEMS = 8;                      // pixels of a tile per thread: eight independent loads in flight
-constexpr int TILE = THREADS * ITEMS;
-constexpr int MAX_TILES = 16777215;           // B * T: the launch's global size (tiles x THREADS) stays below 2^32
+using namespace ecm_pix;
 constexpr int MAX_ATTRS = 4;
 constexpr int FUSE_GRID = 4096;               // workgroups of the fusion launch at most; each walks elements a grid apart
 
 typedef unsigned long long u64;
 
-struct Range {
-    float lo, hi;                             // usable: lo < d <= hi
-};
-
-// disp_reproject.hip's row: fp64, the stated order, contraction off
-__device__ __forceinline__ double row_of(const double* __restrict__ m, double x, double y, double d) {
-#pragma clang fp contract(off)
-    return ((m[0] * x + m[1] * y) + m[2] * d) + m[3];
-}
-
-struct Tile {
-    int b;                                    // image
-    unsigned first;                           // first pixel of the tile within the image
-};
-
-__device__ __forceinline__ Tile tile_of(int T) {
-    Tile t;
-    t.b = (int)(blockIdx.x / (unsigned)T);
-    t.first = (blockIdx.x % (unsigned)T) * (unsigned)TILE;
-    return t;
-}
-
 // ---- scatter -----------------------------------------------------------------------------------------------------------------
 template <int NEAREST>
 __global__ __launch_bounds__(THREADS) void warp_scatter(const float* __restrict__ disp, const unsigned char* __restrict__ valid,
                                                         const double* __restrict__ M, int m_stride, u64* __restrict__ keys, int HW,
-                                                        int W, int H, int T, Range r) {
-    const Tile t = tile_of(T);
+                                                        int W, int H, int T, DispRange r) {
+    const PixTile t = ecm_pix_tile(T);
     const double* m = M + (size_t)t.b * m_stride;
     const size_t img = (size_t)t.b * HW;
     u64* best = keys + img;
-    const double inf = __builtin_inf(), last_x = (double)(W - 1), last_y = (double)(H - 1);
+    const double last_x = (double)(W - 1), last_y = (double)(H - 1);
 #pragma unroll
     for (int k = 0; k < ITEMS; ++k) {
         const unsigned pix = t.first + k * THREADS + threadIdx.x;
         if (pix >= (unsigned)HW) continue;
         const float d = disp[img + pix];
-        const bool v = !valid || valid[img + pix] != 0;
-        if (!(v && fabsf(d) < __builtin_inff() && d > r.lo && d <= r.hi)) continue;
-        const int y = (int)(pix / (unsigned)W), x = (int)(pix - (unsigned)y * (unsigned)W);
+        if (!ecm_disp_usable(d, !valid || valid[img + pix] != 0, r)) continue;
+        int x, y;
+        ecm_pix_xy(pix, W, x, y);
         const double fx = (double)x, fy = (double)y, fd = (double)d;
-        const double w = row_of(m + 12, fx, fy, fd);
-        if (!(fabs(w) < inf && w != 0.0)) continue;
-        const double u = row_of(m, fx, fy, fd) / w, vv = row_of(m + 4, fx, fy, fd) / w;
-        const float dn = (float)(row_of(m + 8, fx, fy, fd) / w);
+        const double w = ecm_row4(m + 12, fx, fy, fd);
+        if (!ecm_nonzero_finite(w)) continue;
+        const double u = ecm_row4(m, fx, fy, fd) / w, vv = ecm_row4(m + 4, fx, fy, fd) / w;
+        const float dn = (float)(ecm_row4(m + 8, fx, fy, fd) / w);
         // every comparison fails on a NaN; u and vv inside the image are finite
         if (!(fabsf(dn) < __builtin_inff() && dn > 0.f && u >= 0.0 && u <= last_x && vv >= 0.0 && vv <= last_y)) continue;
         const u64 key = ((u64)__float_as_uint(dn) << 32) | (u64)pix;
@@ -97,7 +68,7 @@ __global__ __launch_bounds__(THREADS) void warp_scatter(const float* __restrict_
 __global__ __launch_bounds__(THREADS) void warp_resolve(const u64* __restrict__ keys, const float* __restrict__ attrs, int C,
                                                         float* __restrict__ out, int* __restrict__ src,
                                                         float* __restrict__ attrs_out, int HW, int T) {
-    const Tile t = tile_of(T);
+    const PixTile t = ecm_pix_tile(T);
     const size_t img = (size_t)t.b * HW;
 #pragma unroll
     for (int k = 0; k < ITEMS; ++k) {
@@ -164,15 +135,8 @@ int tiles_per_image(int B, int H, int W, int& code) {
     if (B < 1 || H < 1 || W < 1) return 0;
     code = ECM_EUNSUP;
     const long long hw = (long long)H * W;
-    if (hw > INT_MAX) return 0;
-    const long long T = (hw + TILE - 1) / TILE;
-    if (T * B > MAX_TILES) return 0;
-    code = 0;
-    return (int)T;
-}
-
-bool range_ok(float min_disp, float max_disp) {
-    return std::isfinite(min_disp) && !std::isnan(max_disp) && max_disp >= min_disp;
+    if (hw > INT_MAX) return 0;               // the image, not the batch: a key holds an index into the image
+    return ecm_pix_tiles(hw, B, code);
 }
 
 }  // namespace
@@ -189,20 +153,17 @@ extern "C" int ecmt_disparity_warp_fwd(const float* disp, const unsigned char* v
                                        const float* attrs, int C, float* out, int* src, float* attrs_out, void* scratch,
                                        long long scratch_bytes, int B, int H, int W, float min_disp, float max_disp, int footprint,
                                        void* stream) {
-    ECM_CHECK_ARG(disp && M && out && scratch && range_ok(min_disp, max_disp));
+    ECM_CHECK_ARG(disp && M && out && scratch && ecm_disp_range_ok(min_disp, max_disp));
     ECM_CHECK_ARG(C >= 0 && C <= MAX_ATTRS && (C == 0 || (attrs && attrs_out)));
-    const void* const outs[] = {out, src, C ? attrs_out : nullptr, scratch};
-    for (const void* o : outs)
-        ECM_CHECK_ARG(!o || (o != (const void*)disp && o != (const void*)valid && o != (const void*)M &&
-                             (C == 0 || o != (const void*)attrs)));
+    ECM_CHECK_ARG(ecm_no_alias({out, src, C ? attrs_out : nullptr, scratch}, {disp, valid, M, C ? attrs : nullptr}));
     int code;
     const int T = tiles_per_image(B, H, W, code);
     if (!T) return code;
     if (footprint != 0 && footprint != 1) return ECM_EUNSUP;
     const long long need = ecmt_disparity_warp_scratch_bytes(B, H, W);
     if (scratch_bytes < need) return ECM_ESCRATCH;
-    const Range r = {min_disp, max_disp};
-    const int HW = H * W, m_stride = m_per_image ? 16 : 0, n = B * T;
+    const DispRange r = {min_disp, max_disp};
+    const int HW = H * W, m_stride = ecm_mat_stride(m_per_image), n = B * T;
     u64* keys = static_cast<u64*>(scratch);
     hipStream_t s = ecm_stream(stream);
     const hipError_t cleared = hipMemsetAsync(keys, 0, (size_t)need, s);

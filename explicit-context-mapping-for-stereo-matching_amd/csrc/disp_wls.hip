@@ -17,9 +17,7 @@
 // N and D go through the same instructions with the same coefficients, so a constant power-of-two plane comes back bit for bit
 // and a region that cut links separate from every confident pixel has D == 0 exactly.  Written with explicit fmaf so that no
 // contraction can treat the two planes differently.  No atomics, no workgroup waits for another, no private segment.
-#include "common.h"
-#include <climits>
-#include <cmath>
+#include "disp_geom.h"
 
 namespace {
 
@@ -43,8 +41,6 @@ struct Raw {                                  // what a thread has in flight for
     float n, d;                               // d and conf in the first pass, N and D after it
     float g[C_MAX], gq[C_MAX];                // the guide here and at the next position of the line
 };
-
-__device__ __forceinline__ bool finite(float v) { return fabsf(v) < __builtin_inff(); }
 
 // One pass over the lines of one direction.  in_n / in_d: d and conf (conf may be null) where `first`, else the N and D planes of
 // `out`; out_n / out_d the planes of `out`; cp the c' plane.  No __restrict__ on the planes that are both written and read.
@@ -104,7 +100,7 @@ __global__ __launch_bounds__(THREADS) void wls_pass(const float* in_n, const flo
             const int pos = chunk * G::NC + tp[k];
             float fn = raw[k].n, fd = raw[k].d;
             if (first) {                                                        // usable: both finite, conf >= 0; else both 0
-                const bool ok = finite(fn) && finite(fd) && fd >= 0.f;
+                const bool ok = ecm_finite(fn) && ecm_finite(fd) && fd >= 0.f;
                 fd = ok ? fd : 0.f;
                 fn = ok ? fd * fn : 0.f;
             }

@@ -93,12 +93,6 @@ __global__ __launch_bounds__(256) void disp_to_u16(const float* __restrict__ pre
 // (mask, mask_non, good).  mask_true is mask_non in the reference, so its column is a copy and costs no accumulator.
 constexpr int KT = 256, KSPAN = KT * 8, KITTI_MAX_BLOCKS = 256, KP = 5;
 
-__device__ __forceinline__ unsigned wave_sum_u(unsigned v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 __device__ __forceinline__ void kitti_pixel(float p, float d, unsigned x, float maxdisp, float& s, float& s_non, unsigned& n,
                                             unsigned& n_non, unsigned& n_good) {
     const float e = fabsf(p - d);
@@ -142,7 +136,7 @@ __global__ __launch_bounds__(KT) void eval_kitti_partial(const float* __restrict
     }
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     s = wave_sum(s); s_non = wave_sum(s_non);
-    n = wave_sum_u(n); n_non = wave_sum_u(n_non); n_good = wave_sum_u(n_good);
+    n = wave_sum(n); n_non = wave_sum(n_non); n_good = wave_sum(n_good);
     if (lane == 0) { sf[0][wave] = s; sf[1][wave] = s_non; sc[0][wave] = n; sc[1][wave] = n_non; sc[2][wave] = n_good; }
     __syncthreads();
     if (threadIdx.x < KP) {

@@ -36,12 +36,6 @@ constexpr int LDS_SLOTS = 15;
 
 struct Planes { const float* m[MAX_K]; };
 
-__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // The order-preserving image of a measure: -0.0 is +0.0, any NaN is the largest key.
 __device__ __forceinline__ unsigned measure_key(float u) {
     unsigned bits = __float_as_uint(u);
@@ -66,7 +60,7 @@ __device__ __forceinline__ void bin_add(u64* __restrict__ hist, bool on, unsigne
         const bool mine = on && idx == lidx;
         const u64 m = __ballot(mine);
         if (__popcll(m) < PEEL_MIN) break;
-        const u64 a0 = wave_sum_u64(mine ? w0 : 0ull), a1 = wave_sum_u64(mine ? w1 : 0ull);
+        const u64 a0 = wave_sum(mine ? w0 : 0ull), a1 = wave_sum(mine ? w1 : 0ull);
         if (lane == leader) {
             atomicAdd(hist + 2 * (size_t)lidx, a0);
             atomicAdd(hist + 2 * (size_t)lidx + 1, a1);

@@ -436,12 +436,6 @@ __device__ __forceinline__ void slice_st(__amdgpu_buffer_rsrc_t r, unsigned off,
     __builtin_amdgcn_raw_buffer_store_b128(v, r, off, 0, ECM_GN_ST_AUX);
 }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // Cluster exchange without fences: a workgroup's partial (two floats) is published as ONE 64-bit agent-scope atomic
 // store into a slot preset to EMPTY, and read back with agent-scope atomic loads, so data and "ready" flag travel
 // together and no release/acquire (= whole-L2 write-back / invalidate on a multi-XCD part) is needed.
@@ -655,7 +649,7 @@ __global__ __launch_bounds__(THREADS, ECM_GN_FWD_OCC) void gn_fused_fwd(const fl
             tnext = tk.next(t);
             last_s = cluster_done(ctl, tk, span, cl, tnext) ? 1u : 0u;
         }
-        ds = wave_sum_d(ds); dq = wave_sum_d(dq);
+        ds = wave_sum(ds); dq = wave_sum(dq);
         if (lane == 0) { smd[wave * 2] = ds; smd[wave * 2 + 1] = dq; }
         __syncthreads();
         if (last_s) cluster_restore(ctl, sp, span, cl, tid);
@@ -786,7 +780,7 @@ __global__ __launch_bounds__(THREADS, ECM_GN_BWD_OCC) void gn_fused_bwd(const fl
                 if (!slot_collect(sp + cc * wpc + i, ps, pq, ctl.poll_ticks)) got = 0;
                 ds += (double)ps; dq += (double)pq;
             }
-            ds = wave_sum_d(ds); dq = wave_sum_d(dq);
+            ds = wave_sum(ds); dq = wave_sum(dq);
             if (lane == 0) { chs[cc * 2] = ds; chs[cc * 2 + 1] = dq; }
         }
         const bool arrived = __syncthreads_and(got) != 0;

@@ -1,8 +1,7 @@
 // Dense disparity alignment (include/ecm_motion.h has the definitions): the normal equations of one
 // Gauss-Newton step for the rigid motion that maps one disparity map onto the next -- per lattice pixel an fp64 projection
 // through Q, T and Q_out^-1, a four-tap gather of the target map, a 1x6 Jacobian and 31 sums.
-// A tile is TILE = THREADS x ITEMS consecutive LATTICE pixels of ONE image and a workgroup owns one tile (disp_warp.hip's tiling
-// and its limits): the matrices are uniform per workgroup.  Item k of thread t is lattice pixel k * THREADS + t of the tile.
+// A workgroup owns one linear pixel tile (disp_geom.h) of LATTICE pixels: the matrices are uniform per workgroup.
 //   accumulate  every thread adds its items, in order, into 29 fp64 accumulators and two counters in registers; a wave adds its
 //               64 lanes in a fixed xor butterfly (a + b is commutative: every lane holds the same bits), the four waves are
 //               added in wave order through LDS, and the workgroup stores one partial of 32 doubles;
@@ -10,42 +9,21 @@
 //               partial into four accumulators, and the 8 group sums are added in order.
 // No atomics, no workgroup waits for another, no dependence on the batch: bit-reproducible.  The whole file is compiled with
 // contraction off: every product and sum is one fp64 operation, as the header states them.
-#include "common.h"
+#include "disp_geom.h"
 #include "../../include/ecm_motion.h"
-#include <climits>
-#include <cmath>
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int ITEMS = 8;                      // lattice pixels of a tile per thread
-constexpr int TILE = THREADS * ITEMS;
-constexpr int MAX_TILES = 16777215;           // B * tiles: the launch's global size (tiles x THREADS) stays below 2^32
+using namespace ecm_pix;
 constexpr int SUMS = 32;                      // doubles per partial and per image
 constexpr int ACCS = 29;                      // 21 of J^T J, 6 of J^T r, r^2 and the weight
-constexpr int WAVES = THREADS / 64;
 
 struct Gates {
-    float lo, hi;                             // usable: lo < d <= hi
+    DispRange range;
     double tap_range, max_residual, c2;       // c2 = cauchy^2
 };
-
-__device__ __forceinline__ bool usable(float d, bool v, const Gates& g) {
-    return v && fabsf(d) < __builtin_inff() && d > g.lo && d <= g.hi;
-}
-
-// ecm_geometry.h's row
-__device__ __forceinline__ double row_of(const double* __restrict__ m, double x, double y, double d) {
-    return ((m[0] * x + m[1] * y) + m[2] * d) + m[3];
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // ---- accumulate ----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(THREADS) void align_accumulate(const float* __restrict__ disp0, const unsigned char* __restrict__ valid0,
@@ -54,10 +32,9 @@ __global__ __launch_bounds__(THREADS) void align_accumulate(const float* __restr
                                                             const double* __restrict__ A, const double* __restrict__ Tm, int t_stride,
                                                             double* __restrict__ partial, float* __restrict__ residual, int W, int H,
                                                             int Ws, int L, int tiles, int step, Gates g) {
-    const int b = (int)(blockIdx.x / (unsigned)tiles);
-    const unsigned first = (blockIdx.x % (unsigned)tiles) * (unsigned)TILE;
-    const double* __restrict__ T = Tm + (size_t)b * t_stride;
-    const size_t img = (size_t)b * H * W;
+    const PixTile t = ecm_pix_tile(tiles);
+    const double* __restrict__ T = Tm + (size_t)t.b * t_stride;
+    const size_t img = (size_t)t.b * H * W;
     const double inf = __builtin_inf(), last_x = (double)(W - 1), last_y = (double)(H - 1);
 
     double acc[ACCS];
@@ -67,24 +44,25 @@ __global__ __launch_bounds__(THREADS) void align_accumulate(const float* __restr
 
 #pragma unroll 1
     for (int k = 0; k < ITEMS; ++k) {
-        const unsigned l = first + k * THREADS + threadIdx.x;
+        const unsigned l = t.first + k * THREADS + threadIdx.x;
         if (l >= (unsigned)L) continue;
-        const int ly = (int)(l / (unsigned)Ws), lx = (int)(l - (unsigned)ly * (unsigned)Ws);
+        int lx, ly;
+        ecm_pix_xy(l, Ws, lx, ly);
         const int x = lx * step, y = ly * step;                            // x <= W-1, y <= H-1: Ws = ceil(W / step), L = Hs * Ws
         const size_t pix = img + (size_t)y * W + x;
         const float d = disp0[pix];
-        if (!usable(d, !valid0 || valid0[pix] != 0, g)) continue;
+        if (!ecm_disp_usable(d, !valid0 || valid0[pix] != 0, g.range)) continue;
         const double w = weight0 ? (double)weight0[pix] : 1.0;
         if (!(w > 0.0 && w < inf)) continue;
         const double fxs = (double)x, fys = (double)y, fd = (double)d;
-        const double P3 = row_of(Q + 12, fxs, fys, fd);
-        if (!(fabs(P3) < inf && P3 != 0.0)) continue;
-        const double X0 = row_of(Q, fxs, fys, fd) / P3, X1 = row_of(Q + 4, fxs, fys, fd) / P3, X2 = row_of(Q + 8, fxs, fys, fd) / P3;
+        const double P3 = ecm_row4(Q + 12, fxs, fys, fd);
+        if (!ecm_nonzero_finite(P3)) continue;
+        const double X0 = ecm_row4(Q, fxs, fys, fd) / P3, X1 = ecm_row4(Q + 4, fxs, fys, fd) / P3, X2 = ecm_row4(Q + 8, fxs, fys, fd) / P3;
         const double Y0 = ((T[0] * X0 + T[1] * X1) + T[2] * X2) + T[3];
         const double Y1 = ((T[4] * X0 + T[5] * X1) + T[6] * X2) + T[7];
         const double Y2 = ((T[8] * X0 + T[9] * X1) + T[10] * X2) + T[11];
-        const double h3 = row_of(A + 12, Y0, Y1, Y2);
-        const double u = row_of(A, Y0, Y1, Y2) / h3, v = row_of(A + 4, Y0, Y1, Y2) / h3, dn = row_of(A + 8, Y0, Y1, Y2) / h3;
+        const double h3 = ecm_row4(A + 12, Y0, Y1, Y2);
+        const double u = ecm_row4(A, Y0, Y1, Y2) / h3, v = ecm_row4(A + 4, Y0, Y1, Y2) / h3, dn = ecm_row4(A + 8, Y0, Y1, Y2) / h3;
         // every comparison fails on a NaN; u and v inside the image are finite
         if (!(fabs(dn) < inf && dn > 0.0 && u >= 0.0 && u <= last_x && v >= 0.0 && v <= last_y)) continue;
         ++cand;
@@ -94,7 +72,9 @@ __global__ __launch_bounds__(THREADS) void align_accumulate(const float* __restr
         const float t00 = disp1[at], t01 = disp1[at + 1], t10 = disp1[at + W], t11 = disp1[at + W + 1];
         const bool v00 = !valid1 || valid1[at] != 0, v01 = !valid1 || valid1[at + 1] != 0;
         const bool v10 = !valid1 || valid1[at + W] != 0, v11 = !valid1 || valid1[at + W + 1] != 0;
-        if (!(usable(t00, v00, g) && usable(t01, v01, g) && usable(t10, v10, g) && usable(t11, v11, g))) continue;
+        if (!(ecm_disp_usable(t00, v00, g.range) && ecm_disp_usable(t01, v01, g.range) && ecm_disp_usable(t10, v10, g.range) &&
+              ecm_disp_usable(t11, v11, g.range)))
+            continue;
         const float hi = fmaxf(fmaxf(t00, t01), fmaxf(t10, t11)), lo = fminf(fminf(t00, t01), fminf(t10, t11));
         if ((double)hi - (double)lo > g.tap_range) continue;
         const double d00 = t00, d01 = t01, d10 = t10, d11 = t11;
@@ -133,14 +113,14 @@ __global__ __launch_bounds__(THREADS) void align_accumulate(const float* __restr
         acc[28] += a;
     }
 
-    __shared__ double sm[WAVES][SUMS];
+    __shared__ double sm[NWAVE][SUMS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int i = 0; i < ACCS; ++i) {
-        const double t = wave_sum_f64(acc[i]);
-        if (lane == 0) sm[wave][i] = t;
+        const double s = wave_sum(acc[i]);
+        if (lane == 0) sm[wave][i] = s;
     }
-    const double n_used = wave_sum_f64((double)used), n_cand = wave_sum_f64((double)cand);   // integers below 2^53: exact
+    const double n_used = wave_sum((double)used), n_cand = wave_sum((double)cand);   // integers below 2^53: exact
     if (lane == 0) {
         sm[wave][29] = n_used;
         sm[wave][30] = n_cand;
@@ -185,15 +165,10 @@ int tiles_per_image(int B, int H, int W, int step, int& code) {
     if (B < 1 || H < 2 || W < 2 || step < 1) return 0;
     code = ECM_EUNSUP;
     const long long hw = (long long)H * W;
-    if (hw > INT_MAX) return 0;
+    if (hw > INT_MAX) return 0;               // the image, not the batch: ecm_motion.h states H * W, and img is a size_t
     const long long hs = ((long long)H + step - 1) / step, ws = ((long long)W + step - 1) / step;
-    const long long T = (hs * ws + TILE - 1) / TILE;
-    if (T * B > MAX_TILES) return 0;
-    code = 0;
-    return (int)T;
+    return ecm_pix_tiles(hs * ws, B, code);
 }
-
-bool positive(float v) { return std::isfinite(v) && v > 0.f; }
 
 }  // namespace
 
@@ -211,19 +186,16 @@ extern "C" int ecmm_align_normal_fwd(const float* disp0, const unsigned char* va
                                      int H, int W, int step, float min_disp, float max_disp, float tap_range, float max_residual,
                                      float cauchy, void* stream) {
     ECM_CHECK_ARG(disp0 && disp1 && Q && Qinv_out && T && sums && scratch);
-    ECM_CHECK_ARG(std::isfinite(min_disp) && !std::isnan(max_disp) && max_disp >= min_disp);
-    ECM_CHECK_ARG(positive(tap_range) && positive(max_residual) && positive(cauchy));
-    const void* const ins[] = {disp0, valid0, weight0, disp1, valid1, Q, Qinv_out, T};
-    const void* const outs[] = {sums, residual, scratch};
-    for (const void* o : outs)
-        for (const void* i : ins) ECM_CHECK_ARG(!o || o != i);
+    ECM_CHECK_ARG(ecm_disp_range_ok(min_disp, max_disp));
+    ECM_CHECK_ARG(ecm_positive(tap_range) && ecm_positive(max_residual) && ecm_positive(cauchy));
+    ECM_CHECK_ARG(ecm_no_alias({sums, residual, scratch}, {disp0, valid0, weight0, disp1, valid1, Q, Qinv_out, T}));
     ECM_CHECK_ARG((const void*)sums != (const void*)residual && (const void*)sums != scratch && (const void*)residual != scratch);
     int code;
     const int tiles = tiles_per_image(B, H, W, step, code);
     if (!tiles) return code;
     if (scratch_bytes < ecmm_align_scratch_bytes(B, H, W, step)) return ECM_ESCRATCH;
     const int Hs = (int)(((long long)H + step - 1) / step), Ws = (int)(((long long)W + step - 1) / step);
-    const Gates g = {min_disp, max_disp, (double)tap_range, (double)max_residual, (double)cauchy * (double)cauchy};
+    const Gates g = {{min_disp, max_disp}, (double)tap_range, (double)max_residual, (double)cauchy * (double)cauchy};
     double* partial = static_cast<double*>(scratch);
     hipStream_t s = ecm_stream(stream);
     if (residual) {
@@ -231,7 +203,7 @@ extern "C" int ecmm_align_normal_fwd(const float* disp0, const unsigned char* va
         if (filled != hipSuccess) return (int)filled;
     }
     hipLaunchKernelGGL(align_accumulate, dim3(B * tiles), dim3(THREADS), 0, s, disp0, valid0, weight0, disp1, valid1, Q, Qinv_out, T,
-                       t_per_image ? 16 : 0, partial, residual, W, H, Ws, Hs * Ws, tiles, step, g);
+                       ecm_mat_stride(t_per_image), partial, residual, W, H, Ws, Hs * Ws, tiles, step, g);
     hipLaunchKernelGGL(align_finish, dim3(B), dim3(THREADS), 0, s, (const double*)partial, sums, tiles);
     return ECM_LAUNCH_RESULT();
 }

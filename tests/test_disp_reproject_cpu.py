@@ -61,8 +61,8 @@ def cloud_t(d, Q, attributes=None, valid=None, min_disp=0.0, max_disp=None):
 
 
 def kernel_constants():
-    """The constexpr ints of csrc/disp_reproject.hip by name."""
-    src = open(os.path.join(PACKAGE, "csrc", "disp_reproject.hip")).read()
+    """The constexpr ints of csrc/disp_geom.h by name."""
+    src = open(os.path.join(PACKAGE, "csrc", "disp_geom.h")).read()
     env = {}
     for stmt in re.findall(r"^constexpr int ([^;]+);", src, flags=re.M):
         for name, expr in re.findall(r"(\w+) = ([^,]+)", stmt):

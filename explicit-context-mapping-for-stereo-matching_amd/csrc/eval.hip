@@ -102,7 +102,9 @@ __device__ __forceinline__ void kitti_pixel(float p, float d, unsigned x, float 
     if (m && local - d >= 0.f) { s_non += e; n_non += 1u; }
 }
 
-// VEC: W % 4 == 0 and both bases 16-byte aligned, so a float4 never straddles a row or a sample.  hw = H * W < 2^31.
+// VEC: W % 4 == 0 and both bases 16-byte aligned, so a float4 never straddles a row or a sample.  hw = H * W < 2^31.  Both forms
+// give a thread the same four consecutive pixels in the same order, so the fp32 sums -- and with them the whole row -- do not depend
+// on the load width: the result is a function of the values, not of where they lie.
 template <bool VEC>
 __global__ __launch_bounds__(KT) void eval_kitti_partial(const float* __restrict__ pred, const float* __restrict__ gt,
                                                          unsigned* __restrict__ part, unsigned hw, unsigned W, float maxdisp) {
@@ -113,10 +115,10 @@ __global__ __launch_bounds__(KT) void eval_kitti_partial(const float* __restrict
     float s = 0.f, s_non = 0.f;
     unsigned n = 0, n_non = 0, n_good = 0;
     for (unsigned s0 = blockIdx.x * KSPAN; s0 < hw; s0 += gridDim.x * KSPAN) {
-        if (VEC) {
 #pragma unroll
-            for (int k = 0; k < KSPAN / (4 * KT); ++k) {
-                const unsigned i = s0 + (k * KT + threadIdx.x) * 4;
+        for (int k = 0; k < KSPAN / (4 * KT); ++k) {
+            const unsigned i = s0 + (k * KT + threadIdx.x) * 4;
+            if (VEC) {
                 if (i < hw) {
                     const float4 pv = *reinterpret_cast<const float4*>(p + i), dv = *reinterpret_cast<const float4*>(g + i);
                     const unsigned x = i % W;
@@ -125,12 +127,10 @@ __global__ __launch_bounds__(KT) void eval_kitti_partial(const float* __restrict
                     kitti_pixel(pv.z, dv.z, x + 2, maxdisp, s, s_non, n, n_non, n_good);
                     kitti_pixel(pv.w, dv.w, x + 3, maxdisp, s, s_non, n, n_non, n_good);
                 }
-            }
-        } else {
+            } else {
 #pragma unroll
-            for (int k = 0; k < KSPAN / KT; ++k) {
-                const unsigned i = s0 + k * KT + threadIdx.x;
-                if (i < hw) kitti_pixel(p[i], g[i], i % W, maxdisp, s, s_non, n, n_non, n_good);
+                for (unsigned j = 0; j < 4; ++j)
+                    if (i + j < hw) kitti_pixel(p[i + j], g[i + j], (i + j) % W, maxdisp, s, s_non, n, n_non, n_good);
             }
         }
     }

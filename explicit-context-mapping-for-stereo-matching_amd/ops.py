@@ -2755,7 +2755,7 @@ def eval_kitti(pred, gt, maxdisp=192, out=None, per_sample=False):
         pred = pred.squeeze(1)
     _need(pred.dim() == 3 and pred.shape == gt.shape and pred.numel() > 0,
           lambda: f"eval_kitti: pred {tuple(pred.shape)} / gt {tuple(gt.shape)}: want the same non-empty [B,H,W]")
-    pred, gt = pred.contiguous(), gt.contiguous()        # any 4-byte alignment: the kernel picks its load width
+    pred, gt = pred.contiguous(), gt.contiguous()        # any 4-byte alignment: the kernel picks its load width, the row is the same
     B, H, W = pred.shape
     out = _out_row(out, 8, pred.device)
     table = torch.empty(B, 8, device=pred.device, dtype=torch.float32) if per_sample else None

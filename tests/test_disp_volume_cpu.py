@@ -219,6 +219,87 @@ def test_closed_loop_of_the_restatement():
     assert bool((hw[loop["cast"]["hit"][0]] > 0).all()) and bool((hw[~loop["cast"]["hit"][0]] == 0).all())
 
 
+# ---- the mapper's closed loop ------------------------------------------------------------------------------------
+# models.StereoMapper composes three conventions that no other test composes: world = motion @ world, T is world to camera, and
+# the frame's OWN disparity (not the fused state) goes into the volume.  The reference loop below states them on the restatements:
+# five analytic views of the three-plane scene along a constant screw motion, each frame's motion estimated by
+# ops.motion_estimate's own host loop over align_t from the previous frame's map to this one (the device aligns the tracker's
+# fused state, which on an analytic scene is the previous map carried and averaged), the pose composed as the class documents it,
+# the frame's map integrated with the mapper's valid = d > 0 and weight = 1 / std^2, and the volume raycast at a pose that none
+# of the five views has.
+MAPPER_STEP = rigid(0.003, 0.007, -0.002, 0.025, -0.01, 0.03)              # step1 of test_stereo_odometry_is_the_tracker_fed_the_estimate
+MAPPER_STD = 0.05
+MAPPER_MIN_DISP = 1.0                                                       # StereoMapper's default
+MAPPER_HELD_OUT = rigid(0.005, -0.006, 0.004, -0.04, 0.03, 0.05)           # off the path: no view was taken here
+
+
+def mapper_poses(n=5):
+    """I, s, s^2, ...: the world-to-camera pose of frame k (the world frame is frame 0's left camera)."""
+    poses = [torch.eye(4, dtype=F64)]
+    for _ in range(n - 1):
+        poses.append(MAPPER_STEP @ poses[-1])
+    return poses
+
+
+def mapper_maps(poses=None):
+    """(maps [5,H0,W0] fp32, each rounded once from the analytic map, and Q)."""
+    return scene_views(mapper_poses() if poses is None else poses)
+
+
+# Both measured on the CPU with the restatements (the loop below prints them): the mean absolute disparity error over the pixels
+# that hit, in pixels, and the share of the pixels that hit.  The error is set by the discretisation (RAYCAST's, above) and by the
+# accumulated pose error of four estimates, not by rounding; the device's StereoMapper is held to ten times it.
+MEASURED_MAPPER_ERROR = 3.7e-3                                             # 3.687e-3 as printed
+MEASURED_MAPPER_HIT_SHARE = 0.88                                           # 0.8863 as printed
+MAPPER_BOUND = 10 * MEASURED_MAPPER_ERROR
+_MAPPER_LOOP = {}
+
+
+def mapper_loop():
+    """The reference loop, computed once: the world poses, the volume, the raycast at MAPPER_HELD_OUT and the analytic map there."""
+    if not _MAPPER_LOOP:
+        from test_motion_align_cpu import restated
+        ops = ecm().ops
+        maps, Q = mapper_maps()
+        world, worlds = torch.eye(4, dtype=F64), []
+        tsdf, wsum = empty(DIMS)
+        std = torch.full((1, H0, W0), MAPPER_STD, dtype=F32)
+        velocity = None
+        for k in range(maps.shape[0]):
+            if k:
+                est = ops.motion_estimate(maps[k - 1:k], maps[k:k + 1], Q, velocity, normal=restated(maps[k - 1:k], maps[k:k + 1], Q))
+                assert bool(est.converged.all()), k
+                velocity = est.T
+                world = est.T[0] @ world                                   # world = motion @ world
+            m = ops.volume_matrices(Q, world, ORIGIN, VOXEL)                # T is world to camera
+            tsdf, wsum, _ = integrate_t(tsdf, wsum, maps[k:k + 1], Q, m.G, m.C, TRUNC, maps[k:k + 1] > 0, 1.0 / (std * std),
+                                        min_disp=MAPPER_MIN_DISP)            # the frame's own map
+            worlds.append(world.clone())
+        r = ops.volume_matrices(Q, MAPPER_HELD_OUT, ORIGIN, VOXEL)
+        cast = raycast_t(tsdf, wsum, r.R, r.Rinv, (H0, W0), NEAR, FAR)
+        _MAPPER_LOOP.update(worlds=worlds, tsdf=tsdf, wsum=wsum, cast=cast, truth=render(MAPPER_HELD_OUT, H0, W0, PLANES, Q), Q=Q, maps=maps)
+    return _MAPPER_LOOP
+
+
+def test_mapper_loop_of_the_restatements():
+    from test_motion_align_cpu import POSE_BOUND, pose_error
+    loop = mapper_loop()
+    poses = mapper_poses()
+    errors = [pose_error(w, p) for w, p in zip(loop["worlds"], poses)]
+    share, err = loop_error(loop["cast"]["out"][0], loop["truth"])
+    print("mapper loop: pose errors", errors, "hit share", share, "mean |d - truth|", err)
+    assert all(pose_error(MAPPER_HELD_OUT, p) > 10 * POSE_BOUND for p in poses)      # the raycast pose is none of the five views
+    assert bool((loop["truth"] > FAR).all()) and bool((loop["truth"] < NEAR).all())
+    for p in poses:
+        t = render(p, H0, W0, PLANES, loop["Q"])
+        assert bool((t > FAR).all()) and bool((t < NEAR).all()) and bool((t > MAPPER_MIN_DISP).all())
+    assert all(e <= k * POSE_BOUND for k, e in enumerate(errors)), errors
+    assert share >= HIT_SHARE, share
+    # the loop's own numbers, as recorded: they come out of a Gauss-Newton loop, so another CPU or BLAS may move the last digits
+    assert share == pytest.approx(0.8863, abs=0.01) and err == pytest.approx(3.687e-3, rel=0.05), (share, err)
+    assert MEASURED_MAPPER_ERROR == pytest.approx(err, rel=0.05) and MEASURED_MAPPER_HIT_SHARE <= share + 0.01
+
+
 # ---- integration: every decision --------------------------------------------------------------------------------------------------------
 # A Q of powers of two and the identity pose: grid point (i, j, k) of a volume with voxel 1/64 and origin (-4/64, -2/64, 1) is the
 # camera point ((i - 4) / 64, (j - 2) / 64, 1 + k / 64), and at k = 0 (z = 1) it projects exactly onto pixel (i, j).

@@ -11,9 +11,10 @@ import torch
 
 from test_disp_warp_cpu import bits, rigid
 from test_hip_guard_bands import guarded
-from test_disp_volume_cpu import (DIMS, F32, F64, FAR, FIFTH, H0, HIT_SHARE, NEAR, ORIGIN, RAYCAST_BOUND, TRUNC, VIEWS, VOXEL, W0, closed_loop,
-                                  integrate_t, loop_error, raycast_t, scene_views)
-from test_motion_align_cpu import PLANES, render, scene_q
+from test_disp_volume_cpu import (DIMS, F32, F64, FAR, FIFTH, H0, HIT_SHARE, MAPPER_BOUND, MAPPER_HELD_OUT, MAPPER_MIN_DISP, MAPPER_STD, NEAR, ORIGIN,
+                                  RAYCAST_BOUND, TRUNC, VIEWS, VOXEL, W0, closed_loop, integrate_t, loop_error, mapper_loop, mapper_maps, mapper_poses,
+                                  raycast_t, scene_views)
+from test_motion_align_cpu import PLANES, POSE_BOUND, pose_error, render, scene_q
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -228,6 +229,51 @@ def test_stereo_mapper_smoke(ecm):
     assert out.shape == (1, 1) + hw and bool(torch.isfinite(out).all()) and bool((out >= 0).all()) and bool(torch.isfinite(hw_).all())
     other = mapper.render(T=eye, size=(64, 96), near_disp=200.0, far_disp=2.0, step=1.0)
     assert other.shape == (1, 1, 64, 96) and bool(torch.isfinite(other).all())
+    mapper.reset()
+    assert mapper.frames == 0 and bool((mapper.volume[0] == 1).all()) and bool((mapper.volume[1] == 0).all()) and torch.equal(mapper.world, eye)
+    ops.check_async_errors()
+
+
+def test_stereo_mapper_closes_the_loop(ecm):
+    """models.StereoMapper driven by known maps (the Stub of tests/test_hip_motion_align.py in the network's place, motion=None:
+    its own odometry), against the reference loop of tests/test_disp_volume_cpu.py: world = motion @ world, T world to camera,
+    the frame's own disparity integrated.  Then a frame that cannot converge, and reset()."""
+    from test_hip_motion_align import Stub
+    ops, models = ecm.ops, ecm.models
+    ref = mapper_loop()
+    maps, Q = mapper_maps()
+    poses = mapper_poses()
+    dev_maps = [m[None, None].to(DEV) for m in maps]
+    mapper = models.StereoMapper(ecm.get_model("cmfsm"), Q, ORIGIN, VOXEL, DIMS, TRUNC, min_disp=MAPPER_MIN_DISP, step=1)
+    mapper.odometry.tracker.model = Stub(dev_maps, MAPPER_STD)
+    x = torch.zeros(1, 3, H0, W0, device=DEV)
+    eye = torch.eye(4, dtype=F64)
+    errors = []
+    for k in range(len(poses)):
+        m = mapper(x, x)
+        assert isinstance(m, models.Mapped) and m.integrated and m.frames == k + 1 and m.restarted == (k == 0), k
+        assert (m.estimate is None) == (k == 0) and torch.equal(m.world, mapper.world) and m.world is not mapper.world
+        assert torch.equal(m.disparity.view(torch.int32), dev_maps[k].view(torch.int32))
+        errors.append(pose_error(m.world, poses[k]))
+        assert errors[-1] <= k * POSE_BOUND, (k, errors)
+    assert torch.equal(mapper.world, m.world) and mapper.frames == 5
+    assert bool((mapper.volume[1] >= 0).all()) and bool(torch.isfinite(mapper.volume[0]).all())
+    out, hw = mapper.render(T=MAPPER_HELD_OUT, near_disp=NEAR, far_disp=FAR, with_weight=True)
+    assert out.shape == (1, 1, H0, W0) and bool(torch.isfinite(out).all()) and bool((out >= 0).all()) and bool(torch.isfinite(hw).all())
+    share, err = loop_error(out.cpu()[0, 0], ref["truth"])
+    ref_share, ref_err = loop_error(ref["cast"]["out"][0], ref["truth"])
+    print("mapper on the device: pose errors", errors, "hit share", share, "mean |d - truth|", err, "(the reference loop:", ref_share, ref_err, ")")
+    assert share >= HIT_SHARE and err <= MAPPER_BOUND, (share, err)
+    here = mapper.render()                                                 # at the current pose, the last frame's size
+    assert here.shape == (1, 1, H0, W0) and float((here > 0).to(F64).mean()) >= HIT_SHARE
+    # a frame that cannot converge: not integrated, the pose and the count held, both planes bit-unchanged
+    before = [t.clone() for t in mapper.volume]
+    world = mapper.world.clone()
+    mapper.odometry.tracker.model = Stub([torch.zeros_like(dev_maps[0])], MAPPER_STD)
+    m = mapper(x, x)
+    assert not m.integrated and m.restarted and m.frames == 5 and mapper.frames == 5 and torch.equal(m.world, world) and torch.equal(mapper.world, world)
+    assert m.estimate is not None and not bool(m.estimate.converged.any())
+    assert all(torch.equal(bits(t), bits(b)) for t, b in zip(mapper.volume, before))
     mapper.reset()
     assert mapper.frames == 0 and bool((mapper.volume[0] == 1).all()) and bool((mapper.volume[1] == 0).all()) and torch.equal(mapper.world, eye)
     ops.check_async_errors()

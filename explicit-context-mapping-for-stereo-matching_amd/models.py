@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import color as _color
 from . import mesh as _mesh
 from . import ops
 
@@ -1417,7 +1418,20 @@ class StereoMapper:
             self.volume[1].zero_()
         self.world, self.frames = self._eye.clone(), 0
 
+    def _allocate(self, device):
+        """The empty volume on `device`."""
+        self.volume = ops.volume_new(self.dims, device)
+
+    def _integrate(self, o, extra=None):
+        """One frame (an Odometry) into the volume at the pose self.world; `extra` is what a subclass's __call__ passed on."""
+        ops.volume_integrate(*self.volume, o.disparity, self.Q, self.world, self.origin, self.voxel, self.trunc,
+                             valid=o.disparity > 0, weight=1.0 / (o.std * o.std), max_weight=self.max_weight,
+                             min_disp=self.min_disp)
+
     def __call__(self, left, right, motion=None):
+        return self._frame(left, right, motion)
+
+    def _frame(self, left, right, motion, extra=None):
         if not isinstance(left, torch.Tensor) or left.dim() != 4 or left.shape[0] != 1:
             raise ValueError(f"StereoMapper: frames {tuple(getattr(left, 'shape', ()))}: one pair at a time, [1,3,H,W]")
         first = self.frames == 0
@@ -1438,13 +1452,11 @@ class StereoMapper:
         if not (first or held):
             self.world = moved @ self.world
         if self.volume is None or self.volume[0].device != o.disparity.device:
-            self.volume = ops.volume_new(self.dims, o.disparity.device)
+            self._allocate(o.disparity.device)
         self._size = tuple(o.disparity.shape[-2:])
         if not held:
             with torch.no_grad():
-                ops.volume_integrate(*self.volume, o.disparity, self.Q, self.world, self.origin, self.voxel, self.trunc,
-                                     valid=o.disparity > 0, weight=1.0 / (o.std * o.std), max_weight=self.max_weight,
-                                     min_disp=self.min_disp)
+                self._integrate(o, extra)
             self.frames += 1
         return Mapped(*o, self.world.clone(), not held, self.frames)
 
@@ -1466,3 +1478,65 @@ class StereoMapper:
         if self.volume is None:
             raise ValueError("StereoMapper.mesh: no frame has been integrated")
         return _mesh.volume_mesh(*self.volume, self.origin, self.voxel, min_weight=min_weight, **kw)
+
+
+class ColorStereoMapper(StereoMapper):
+    """A StereoMapper whose volume also carries `channels` attribute planes: per call the frame's colours
+    -- `colors` [1,channels,H,W] fp32 of the disparity's size, or the left image as given (None; it has three channels) -- go
+    into the volume with the frame's disparity through color.volume_integrate, one launch in ops.volume_integrate's place, so
+    the Mapped it returns, tsdf and wsum are a plain StereoMapper's bit for bit.  render_colors() raycasts disparity and colour,
+    colored_mesh() extracts the mesh and samples the colour at its vertices; render() and mesh() are StereoMapper's.  The
+    attributes are averaged as they are given (a normalised image stays normalised: the caller de-normalises what it reads
+    back).  The colour band is trunc wide, a voxel reads the nearest pixel, and there is no view-angle weighting; every
+    default is untested for quality, and only synthetic scenes were used."""
+
+    def __init__(self, model, Q, origin, voxel, dims, trunc, head=2, max_weight=64.0, min_disp=1.0, channels=3, **odometry_kwargs):
+        super().__init__(model, Q, origin, voxel, dims, trunc, head, max_weight, min_disp, **odometry_kwargs)
+        self.channels = _color._channels("ColorStereoMapper", channels)
+        self.attributes = None
+
+    def reset(self):
+        """StereoMapper.reset(), and the attribute planes emptied too."""
+        super().reset()
+        if self.attributes is not None:
+            self.attributes[0].zero_()
+            self.attributes[1].zero_()
+
+    def _allocate(self, device):
+        super()._allocate(device)
+        self.attributes = _color.volume_attributes_new(self.dims, self.channels, device)
+
+    def _integrate(self, o, extra=None):
+        _color.volume_integrate(*self.volume, *self.attributes, o.disparity, extra, self.Q, self.world, self.origin, self.voxel,
+                                self.trunc, valid=o.disparity > 0, weight=1.0 / (o.std * o.std), max_weight=self.max_weight,
+                                min_disp=self.min_disp)
+
+    def __call__(self, left, right, motion=None, colors=None):
+        given = left if colors is None else colors
+        if not isinstance(given, torch.Tensor) or given.dim() != 4 or given.shape[:2] != (1, self.channels):
+            raise ValueError(f"ColorStereoMapper: colors {tuple(getattr(given, 'shape', ()))}: [1,{self.channels},H,W]"
+                             + (" (the left image: pass colors, or channels=3)" if colors is None else ""))
+        # the disparity has the left image's size: a colour image of another size is refused here, before the tracker and the pose move
+        if isinstance(left, torch.Tensor) and left.dim() == 4 and given.shape[2:] != left.shape[2:]:
+            raise ValueError(f"ColorStereoMapper: colors {tuple(given.shape)} against the frames {tuple(left.shape)}: one size H x W")
+        if isinstance(left, torch.Tensor) and given.device != left.device:
+            raise ValueError(f"ColorStereoMapper: colors on {given.device}, the frames on {left.device}: one device")
+        return self._frame(left, right, motion, given)
+
+    def render_colors(self, T=None, size=None, near_disp=None, far_disp=None, step=0.5, max_steps=None, with_weight=False, Q_out=None):
+        """color.volume_raycast with render()'s arguments and defaults: (disparity [1,1,H,W], colors [1,channels,H,W]), and
+        hit_weight behind them with with_weight=True."""
+        if self.volume is None:
+            raise ValueError("ColorStereoMapper.render_colors: no frame has been integrated")
+        size = self._size if size is None else size
+        near_disp = float(size[1]) if near_disp is None and isinstance(size, (tuple, list)) and len(size) == 2 else near_disp
+        return _color.volume_raycast(*self.volume, *self.attributes, self.Q if Q_out is None else Q_out,
+                                     self.world if T is None else T, self.origin, self.voxel, size, near_disp,
+                                     self.min_disp if far_disp is None else far_disp, step, max_steps, with_weight)
+
+    def colored_mesh(self, min_weight=0.0, **kw):
+        """(mesh(min_weight, **kw), its vertex colours [N,channels] fp32 by color.mesh_colors, in the same frame)."""
+        if self.volume is None:
+            raise ValueError("ColorStereoMapper.colored_mesh: no frame has been integrated")
+        m = self.mesh(min_weight, **kw)
+        return m, _color.mesh_colors(m, *self.attributes, self.origin, self.voxel, kw.get("T"))

@@ -172,17 +172,13 @@ extern "C" int ecmc_integrate_fwd(float* tsdf, float* wsum, float* attr, float* 
     ECM_CHECK_ARG(ecm_no_alias({tsdf, wsum, attr, asum}, {disp, valid, weight, attributes, Q, G, C}));
     ECM_CHECK_ARG(tsdf != wsum && tsdf != attr && tsdf != asum && wsum != attr && wsum != asum && attr != asum);
     if (!attributes_fit(A)) return ECM_EUNSUP;
-    if (!sizes_fit(nx, ny, nz, H, W)) return ECM_EUNSUP;
-    const bool wide = nx % 4 == 0 && ((uintptr_t)tsdf | (uintptr_t)wsum | (uintptr_t)attr | (uintptr_t)asum) % 16 == 0;
-    Bricks b;
-    if (!bricks_of(b, nx, ny, nz, wide ? 4 : 1)) return ECM_EUNSUP;
-    const Gates g = {{min_disp, max_disp}, max_weight, (double)trunc};
-    const dim3 grid((unsigned)(b.bx * b.by * b.bz));
-    return ecm_dispatch<1, 4>(wide ? 4 : 1, [&](auto vec) {
+    IntegratePlan p;
+    if (!integrate_plan(p, nx, ny, nz, H, W, trunc, max_weight, min_disp, max_disp, {tsdf, wsum, attr, asum})) return ECM_EUNSUP;
+    return ecm_dispatch<1, 4>(p.vec, [&](auto vec) {
         return ecm_dispatch<1, 2, 3, 4>(A, [&](auto planes) {
-            hipLaunchKernelGGL((integrate_color_kernel<decltype(vec)::value, decltype(planes)::value>), grid, dim3(THREADS), 0,
+            hipLaunchKernelGGL((integrate_color_kernel<decltype(vec)::value, decltype(planes)::value>), dim3(p.groups), dim3(THREADS), 0,
                                ecm_stream(stream), tsdf, wsum, attr, asum, disp, valid, weight, attributes, Q, G, C,
-                               ecm_mat_stride(m_per_view), nx, ny, nz, (int)b.bx, (int)b.by, V, H, W, g);
+                               ecm_mat_stride(m_per_view), nx, ny, nz, (int)p.bricks.bx, (int)p.bricks.by, V, H, W, p.gates);
             return ECM_LAUNCH_RESULT();
         });
     });
@@ -197,15 +193,12 @@ extern "C" int ecmc_raycast_fwd(const float* tsdf, const float* wsum, const floa
     ECM_CHECK_ARG(ecm_no_alias({out, hit_weight, colors}, {tsdf, wsum, attr, asum, R, Rinv}));
     ECM_CHECK_ARG(out != hit_weight && out != colors && hit_weight != colors);
     if (!attributes_fit(A)) return ECM_EUNSUP;
-    if (!sizes_fit(nx, ny, nz, H, W)) return ECM_EUNSUP;
-    if (max_steps > MAX_STEPS) return ECM_EUNSUP;
-    RayTiles t;
-    if (!ray_tiles_of(t, B, H, W)) return ECM_EUNSUP;
-    const March mr = {(double)near_disp, (double)far_disp, (double)step, max_steps};
+    RayPlan p;
+    if (!ray_plan(p, nx, ny, nz, B, H, W, near_disp, far_disp, step, max_steps)) return ECM_EUNSUP;
     return ecm_dispatch<1, 2, 3, 4>(A, [&](auto planes) {
-        hipLaunchKernelGGL(raycast_color_kernel<decltype(planes)::value>, dim3((unsigned)(t.per_view * B)), dim3(THREADS), 0,
-                           ecm_stream(stream), tsdf, wsum, attr, asum, R, Rinv, ecm_mat_stride(m_per_view), out, hit_weight, colors, nx,
-                           ny, nz, H, W, (int)t.x, (int)t.per_view, mr);
+        hipLaunchKernelGGL(raycast_color_kernel<decltype(planes)::value>, dim3(p.groups), dim3(THREADS), 0, ecm_stream(stream), tsdf, wsum,
+                           attr, asum, R, Rinv, ecm_mat_stride(m_per_view), out, hit_weight, colors, nx, ny, nz, H, W, (int)p.tiles.x,
+                           (int)p.tiles.per_view, p.march);
         return ECM_LAUNCH_RESULT();
     });
 }

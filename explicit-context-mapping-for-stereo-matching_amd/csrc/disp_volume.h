@@ -7,6 +7,7 @@
 #pragma once
 #include "disp_geom.h"
 #include <cstdint>
+#include <initializer_list>
 
 #pragma clang fp contract(off)
 
@@ -244,6 +245,43 @@ static inline bool voxels_fit(int nx, int ny, int nz) { return (long long)nx * n
 // the sizes a volume and an image must have for the kernels' index arithmetic
 static inline bool sizes_fit(int nx, int ny, int nz, int H, int W) {
     return (long long)nx * ny <= INT_MAX && voxels_fit(nx, ny, nz) && (long long)H * W <= INT_MAX;
+}
+
+// The launch of an integration, after the entry's own argument checks: VEC = 4 where nx % 4 == 0 and every plane the kernel updates
+// in place (`planes`) is 16-byte aligned, else 1; the bricks of that VEC, their number and the gates.  false: unsupported sizes.
+struct IntegratePlan {
+    int vec;
+    Bricks bricks;
+    Gates gates;
+    unsigned groups;
+};
+
+static inline bool integrate_plan(IntegratePlan& p, int nx, int ny, int nz, int H, int W, float trunc, float max_weight, float min_disp,
+                                  float max_disp, std::initializer_list<const void*> planes) {
+    if (!sizes_fit(nx, ny, nz, H, W)) return false;
+    uintptr_t low = 0;
+    for (const void* plane : planes) low |= (uintptr_t)plane;
+    p.vec = nx % 4 == 0 && low % 16 == 0 ? 4 : 1;
+    if (!bricks_of(p.bricks, nx, ny, nz, p.vec)) return false;
+    p.gates = {{min_disp, max_disp}, max_weight, (double)trunc};
+    p.groups = (unsigned)(p.bricks.bx * p.bricks.by * p.bricks.bz);
+    return true;
+}
+
+// The launch of a raycast, after the entry's own argument checks: the tiles of the B views and the march.  false: unsupported
+// sizes, or more steps than MAX_STEPS.
+struct RayPlan {
+    RayTiles tiles;
+    March march;
+    unsigned groups;
+};
+
+static inline bool ray_plan(RayPlan& p, int nx, int ny, int nz, int B, int H, int W, float near_disp, float far_disp, float step,
+                            int max_steps) {
+    if (!sizes_fit(nx, ny, nz, H, W) || max_steps > MAX_STEPS || !ray_tiles_of(p.tiles, B, H, W)) return false;
+    p.march = {(double)near_disp, (double)far_disp, (double)step, max_steps};
+    p.groups = (unsigned)(p.tiles.per_view * B);
+    return true;
 }
 
 }  // namespace ecm_vol

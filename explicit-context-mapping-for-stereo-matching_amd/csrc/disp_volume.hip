@@ -75,15 +75,12 @@ extern "C" int ecmv_integrate_fwd(float* tsdf, float* wsum, const float* disp, c
     ECM_CHECK_ARG(ecm_positive(trunc) && ecm_positive(max_weight));
     ECM_CHECK_ARG(ecm_disp_range_ok(min_disp, max_disp));
     ECM_CHECK_ARG(ecm_no_alias({tsdf, wsum}, {disp, valid, weight, Q, G, C}) && tsdf != wsum);
-    if (!sizes_fit(nx, ny, nz, H, W)) return ECM_EUNSUP;
-    const bool wide = nx % 4 == 0 && ((uintptr_t)tsdf | (uintptr_t)wsum) % 16 == 0;
-    Bricks b;
-    if (!bricks_of(b, nx, ny, nz, wide ? 4 : 1)) return ECM_EUNSUP;
-    const Gates g = {{min_disp, max_disp}, max_weight, (double)trunc};
-    const dim3 grid((unsigned)(b.bx * b.by * b.bz));
-    return ecm_dispatch<1, 4>(wide ? 4 : 1, [&](auto vec) {
-        hipLaunchKernelGGL(integrate_kernel<decltype(vec)::value>, grid, dim3(THREADS), 0, ecm_stream(stream), tsdf, wsum, disp, valid,
-                           weight, Q, G, C, ecm_mat_stride(m_per_view), nx, ny, nz, (int)b.bx, (int)b.by, V, H, W, g);
+    IntegratePlan p;
+    if (!integrate_plan(p, nx, ny, nz, H, W, trunc, max_weight, min_disp, max_disp, {tsdf, wsum})) return ECM_EUNSUP;
+    return ecm_dispatch<1, 4>(p.vec, [&](auto vec) {
+        hipLaunchKernelGGL(integrate_kernel<decltype(vec)::value>, dim3(p.groups), dim3(THREADS), 0, ecm_stream(stream), tsdf, wsum, disp,
+                           valid, weight, Q, G, C, ecm_mat_stride(m_per_view), nx, ny, nz, (int)p.bricks.bx, (int)p.bricks.by, V, H, W,
+                           p.gates);
         return ECM_LAUNCH_RESULT();
     });
 }
@@ -97,12 +94,9 @@ extern "C" int ecmv_raycast_fwd(const float* tsdf, const float* wsum, const doub
     ECM_CHECK_ARG(nx >= 2 && ny >= 2 && nz >= 2 && B >= 1 && H >= 1 && W >= 1 && max_steps >= 1);
     ECM_CHECK_ARG(ecm_positive(step) && ecm_positive(far_disp) && std::isfinite(near_disp) && near_disp > far_disp);
     ECM_CHECK_ARG(ecm_no_alias({out, hit_weight}, {tsdf, wsum, R, Rinv}) && out != hit_weight);
-    if (!sizes_fit(nx, ny, nz, H, W)) return ECM_EUNSUP;
-    if (max_steps > MAX_STEPS) return ECM_EUNSUP;
-    RayTiles t;
-    if (!ray_tiles_of(t, B, H, W)) return ECM_EUNSUP;
-    const March mr = {(double)near_disp, (double)far_disp, (double)step, max_steps};
-    hipLaunchKernelGGL(raycast_kernel, dim3((unsigned)(t.per_view * B)), dim3(THREADS), 0, ecm_stream(stream), tsdf, wsum, R, Rinv,
-                       ecm_mat_stride(m_per_view), out, hit_weight, nx, ny, nz, H, W, (int)t.x, (int)t.per_view, mr);
+    RayPlan p;
+    if (!ray_plan(p, nx, ny, nz, B, H, W, near_disp, far_disp, step, max_steps)) return ECM_EUNSUP;
+    hipLaunchKernelGGL(raycast_kernel, dim3(p.groups), dim3(THREADS), 0, ecm_stream(stream), tsdf, wsum, R, Rinv,
+                       ecm_mat_stride(m_per_view), out, hit_weight, nx, ny, nz, H, W, (int)p.tiles.x, (int)p.tiles.per_view, p.march);
     return ECM_LAUNCH_RESULT();
 }

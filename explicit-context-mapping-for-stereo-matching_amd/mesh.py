@@ -2,13 +2,14 @@
 the device, as an indexed mesh with shared vertices, per-vertex normals and a consistent winding, and a PLY writer for it.
 
 Forward only, and a module of its own beside ops.py: the ops here are held to ops.py's forward-only operand contract by their
-own test file (tests/test_hip_volume_mesh.py) until the table of that contract takes them in."""
+own test file (tests/test_hip_volume_mesh.py) until the table of that contract takes them in.  The one PLY writer is here
+(_write_ply): write_ply and color.write_ply are calls of it, without and with vertex colours."""
 from __future__ import annotations
 
 import collections
 import ctypes as C
-import struct
 
+import numpy as np
 import torch
 
 from . import _lib, ops
@@ -55,7 +56,7 @@ def volume_mesh(tsdf, wsum, origin, voxel, T=None, min_weight=0.0, with_normals=
     who = "volume_mesh"
     min_weight = ops._real(who, "min_weight", min_weight, ">= 0", fp32=True)
     M = mesh_matrix(origin, voxel, T)
-    nz, ny, nx = ops._volume_planes(who, tsdf, wsum, least=2)
+    nz, ny, nx = ops._volume_planes(who, least=2, tsdf=tsdf, wsum=wsum)
     need = int(_lib.query("ecms_mesh_scratch_bytes", nx, ny, nz))
     if need <= 0:
         raise RuntimeError(f"{who}: a volume of {nz} x {ny} x {nx} points: at most 2^27")
@@ -77,26 +78,45 @@ def volume_mesh(tsdf, wsum, origin, voxel, T=None, min_weight=0.0, with_normals=
     return Mesh(vertices, faces, normals, weight)
 
 
-def write_ply(path, mesh):
-    """Write `mesh` (a Mesh, on any device) to `path` as binary little-endian PLY, on the host: per vertex float x y z and, where
-    the mesh has normals, float nx ny nz; per face `list uchar int vertex_indices`."""
+def _write_ply(path, mesh, colors, who):
+    """The one PLY writer, on the host: binary little-endian; per vertex float x y z, float nx ny nz where the mesh has normals,
+    and uchar red green blue (alpha) where `colors` ([N,3] or [N,4]; None: no colour) is given; per face `list uchar int
+    vertex_indices`.  A colour c is stored as floor(clamp(c, 0, 1) * 255 + 0.5), computed in fp64 (a NaN as 0).  `who` names the
+    caller in the refusals."""
     if not isinstance(mesh, Mesh):
-        raise ValueError(f"write_ply: mesh {type(mesh).__name__}: a Mesh")
+        raise ValueError(f"{who}: mesh {type(mesh).__name__}: a Mesh")
+    if colors is not None and (not isinstance(colors, torch.Tensor) or colors.dim() != 2 or colors.shape[1] not in (3, 4)
+                               or colors.shape[0] != mesh.vertices.shape[0]):
+        raise ValueError(f"{who}: colors {tuple(getattr(colors, 'shape', ()))!r} against vertices {tuple(mesh.vertices.shape)}: [N,3] or [N,4]")
     v, f = mesh.vertices.detach().cpu().to(torch.float32), mesh.faces.detach().cpu().to(torch.int32)
     if v.dim() != 2 or v.shape[1] != 3 or f.dim() != 2 or f.shape[1] != 3:
-        raise ValueError(f"write_ply: vertices {tuple(v.shape)}, faces {tuple(f.shape)}: [N,3] and [F,3]")
+        raise ValueError(f"{who}: vertices {tuple(v.shape)}, faces {tuple(f.shape)}: [N,3] and [F,3]")
     names = ["x", "y", "z"]
     if mesh.normals is not None:
         n = mesh.normals.detach().cpu().to(torch.float32)
         if n.shape != v.shape:
-            raise ValueError(f"write_ply: normals {tuple(n.shape)} against vertices {tuple(v.shape)}")
+            raise ValueError(f"{who}: normals {tuple(n.shape)} against vertices {tuple(v.shape)}")
         v, names = torch.cat([v, n], 1), names + ["nx", "ny", "nz"]
+    fields, channels = [("f", "<f4", (v.shape[1],))], []
+    if colors is not None:
+        c = torch.nan_to_num(colors.detach().cpu().to(torch.float64), nan=0.0)
+        c = torch.floor(c.clamp(0.0, 1.0) * 255.0 + 0.5).to(torch.uint8)
+        fields, channels = fields + [("c", "u1", (c.shape[1],))], ["red", "green", "blue", "alpha"][:c.shape[1]]
     header = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}"] + [f"property float {n}" for n in names] \
-        + [f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
-    rows = bytearray()
-    for a, b, c in f.tolist():
-        rows += struct.pack("<Biii", 3, a, b, c)
+        + [f"property uchar {n}" for n in channels] + [f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
+    rows = np.empty(v.shape[0], dtype=np.dtype(fields))                    # packed: no padding
+    rows["f"] = v.numpy()
+    if colors is not None:
+        rows["c"] = c.numpy()
+    tris = np.empty(f.shape[0], dtype=np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
+    tris["n"], tris["i"] = 3, f.numpy()
     with open(path, "wb") as out:
         out.write(("\n".join(header) + "\n").encode("ascii"))
-        out.write(v.contiguous().numpy().astype("<f4").tobytes())
-        out.write(bytes(rows))
+        out.write(rows.tobytes())
+        out.write(tris.tobytes())
+
+
+def write_ply(path, mesh):
+    """Write `mesh` (a Mesh, on any device) to `path` as binary little-endian PLY, on the host: per vertex float x y z and, where
+    the mesh has normals, float nx ny nz; per face `list uchar int vertex_indices`.  color.write_ply adds vertex colours."""
+    _write_ply(path, mesh, None, "write_ply")

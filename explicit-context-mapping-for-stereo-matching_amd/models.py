@@ -1422,11 +1422,13 @@ class StereoMapper:
         """The empty volume on `device`."""
         self.volume = ops.volume_new(self.dims, device)
 
+    def _frame_kwargs(self, o):
+        """How a frame (an Odometry) counts in the volume, as keyword arguments of the integrate ops."""
+        return dict(valid=o.disparity > 0, weight=1.0 / (o.std * o.std), max_weight=self.max_weight, min_disp=self.min_disp)
+
     def _integrate(self, o, extra=None):
         """One frame (an Odometry) into the volume at the pose self.world; `extra` is what a subclass's __call__ passed on."""
-        ops.volume_integrate(*self.volume, o.disparity, self.Q, self.world, self.origin, self.voxel, self.trunc,
-                             valid=o.disparity > 0, weight=1.0 / (o.std * o.std), max_weight=self.max_weight,
-                             min_disp=self.min_disp)
+        ops.volume_integrate(*self.volume, o.disparity, self.Q, self.world, self.origin, self.voxel, self.trunc, **self._frame_kwargs(o))
 
     def __call__(self, left, right, motion=None):
         return self._frame(left, right, motion)
@@ -1464,19 +1466,25 @@ class StereoMapper:
         """ops.volume_raycast of the volume at the current pose (T None) or at T (world to camera), for the view Q_out (None: Q)
         of size (H, W) (None: the last frame's): near_disp None is W, the largest disparity a map of that width can hold, and
         far_disp None is min_disp."""
+        view = self._view("StereoMapper.render", T, size, near_disp, far_disp, Q_out)
+        return ops.volume_raycast(*self.volume, *view, step, max_steps, with_weight)
+
+    def _need_frames(self, who):
         if self.volume is None:
-            raise ValueError("StereoMapper.render: no frame has been integrated")
+            raise ValueError(f"{who}: no frame has been integrated")
+
+    def _view(self, who, T, size, near_disp, far_disp, Q_out):
+        """render()'s guard and defaults: (Q_out, T, origin, voxel, size, near_disp, far_disp) as the raycast ops take them."""
+        self._need_frames(who)
         size = self._size if size is None else size
         near_disp = float(size[1]) if near_disp is None and isinstance(size, (tuple, list)) and len(size) == 2 else near_disp
-        return ops.volume_raycast(*self.volume, self.Q if Q_out is None else Q_out, self.world if T is None else T, self.origin,
-                                  self.voxel, size, near_disp, self.min_disp if far_disp is None else far_disp, step, max_steps,
-                                  with_weight)
+        return (self.Q if Q_out is None else Q_out, self.world if T is None else T, self.origin, self.voxel, size, near_disp,
+                self.min_disp if far_disp is None else far_disp)
 
     def mesh(self, min_weight=0.0, **kw):
         """mesh.volume_mesh of the volume in the world frame (the first frame's left camera): Mesh(vertices, faces, normals,
         weight); kw: with_normals, with_weight, or T for another camera's frame."""
-        if self.volume is None:
-            raise ValueError("StereoMapper.mesh: no frame has been integrated")
+        self._need_frames("StereoMapper.mesh")
         return _mesh.volume_mesh(*self.volume, self.origin, self.voxel, min_weight=min_weight, **kw)
 
 
@@ -1508,8 +1516,7 @@ class ColorStereoMapper(StereoMapper):
 
     def _integrate(self, o, extra=None):
         _color.volume_integrate(*self.volume, *self.attributes, o.disparity, extra, self.Q, self.world, self.origin, self.voxel,
-                                self.trunc, valid=o.disparity > 0, weight=1.0 / (o.std * o.std), max_weight=self.max_weight,
-                                min_disp=self.min_disp)
+                                self.trunc, **self._frame_kwargs(o))
 
     def __call__(self, left, right, motion=None, colors=None):
         given = left if colors is None else colors
@@ -1526,17 +1533,11 @@ class ColorStereoMapper(StereoMapper):
     def render_colors(self, T=None, size=None, near_disp=None, far_disp=None, step=0.5, max_steps=None, with_weight=False, Q_out=None):
         """color.volume_raycast with render()'s arguments and defaults: (disparity [1,1,H,W], colors [1,channels,H,W]), and
         hit_weight behind them with with_weight=True."""
-        if self.volume is None:
-            raise ValueError("ColorStereoMapper.render_colors: no frame has been integrated")
-        size = self._size if size is None else size
-        near_disp = float(size[1]) if near_disp is None and isinstance(size, (tuple, list)) and len(size) == 2 else near_disp
-        return _color.volume_raycast(*self.volume, *self.attributes, self.Q if Q_out is None else Q_out,
-                                     self.world if T is None else T, self.origin, self.voxel, size, near_disp,
-                                     self.min_disp if far_disp is None else far_disp, step, max_steps, with_weight)
+        view = self._view("ColorStereoMapper.render_colors", T, size, near_disp, far_disp, Q_out)
+        return _color.volume_raycast(*self.volume, *self.attributes, *view, step, max_steps, with_weight)
 
     def colored_mesh(self, min_weight=0.0, **kw):
         """(mesh(min_weight, **kw), its vertex colours [N,channels] fp32 by color.mesh_colors, in the same frame)."""
-        if self.volume is None:
-            raise ValueError("ColorStereoMapper.colored_mesh: no frame has been integrated")
+        self._need_frames("ColorStereoMapper.colored_mesh")
         m = self.mesh(min_weight, **kw)
         return m, _color.mesh_colors(m, *self.attributes, self.origin, self.voxel, kw.get("T"))

@@ -1417,26 +1417,95 @@ def volume_new(dims, device):
     return tsdf, torch.zeros(dims, dtype=torch.float32, device=device)
 
 
-def _volume_planes(who, tsdf, wsum, least=1):
-    """The two planes of a volume after their refusals: fp32 on the device, [nz,ny,nx], contiguous (they are used in place), of
-    one shape, neither requiring grad."""
-    for name, t in (("tsdf", tsdf), ("wsum", wsum)):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{who}: {name} {type(t).__name__}: a tensor")
-        if t.requires_grad:
-            raise ValueError(f"{who}: {name} requires grad: the volume ops are forward only")
-    _chk(tsdf, wsum)
-    _need(tsdf.dim() == 3 and tsdf.shape == wsum.shape and all(n >= least for n in tsdf.shape),
-          lambda: f"{who}: tsdf {tuple(tsdf.shape)}, wsum {tuple(wsum.shape)}: one shape [nz,ny,nx], every dim >= {least}")
-    _need(tsdf.is_contiguous() and wsum.is_contiguous(), lambda: f"{who}: tsdf and wsum must be contiguous")
-    _need(tsdf.data_ptr() != wsum.data_ptr(), lambda: f"{who}: tsdf and wsum are one tensor")
-    return tuple(int(n) for n in tsdf.shape)
-
-
 def _no_grad_operands(who, **ts):
     for name, t in ts.items():
         if isinstance(t, torch.Tensor) and t.requires_grad:
             raise ValueError(f"{who}: {name} requires grad: the volume ops are forward only")
+
+
+def _volume_planes(who, least=1, most_attributes=None, **planes):
+    """The planes of a volume, by name, after their refusals: tsdf and wsum [nz,ny,nx], and / or attr [A,nz,ny,nx] (A in
+    1..most_attributes, the caller's rule) and asum [nz,ny,nx] of the same shape; each a tensor that does not require grad, fp32 on
+    the device, contiguous (they are used in place), every dim >= least, and no two sharing a byte.  Returns (nz, ny, nx)."""
+    dims, spans = None, []
+    for first, second in (("tsdf", "wsum"), ("attr", "asum")):
+        if first not in planes:
+            continue
+        a, b = planes[first], planes[second]
+        for name, t in ((first, a), (second, b)):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{who}: {name} {type(t).__name__}: a tensor")
+            _no_grad_operands(who, **{name: t})
+        _chk(a, b)
+        if first == "tsdf":
+            _need(a.dim() == 3 and a.shape == b.shape and all(n >= least for n in a.shape),
+                  lambda: f"{who}: tsdf {tuple(a.shape)}, wsum {tuple(b.shape)}: one shape [nz,ny,nx], every dim >= {least}")
+        else:
+            _need(b.dim() == 3 and a.dim() == 4 and a.shape[1:] == b.shape and all(n >= least for n in b.shape) and dims in (None, tuple(b.shape)),
+                  lambda: f"{who}: attr {tuple(a.shape)}, asum {tuple(b.shape)}: [A,nz,ny,nx] and [nz,ny,nx]"
+                  + (f" of the volume's shape {dims}" if dims is not None else f", every dim >= {least}"))
+            _need(1 <= a.shape[0] <= most_attributes, lambda: f"{who}: attr {tuple(a.shape)}: A in 1..{most_attributes}")
+        _need(a.is_contiguous() and b.is_contiguous(), lambda: f"{who}: {first} and {second} must be contiguous")
+        dims = tuple(int(n) for n in b.shape)
+        for name, t in ((first, a), (second, b)):
+            lo, hi = t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()
+            for other, lo2, hi2 in spans:
+                _need(hi <= lo2 or hi2 <= lo, lambda: f"{who}: tsdf and wsum are one tensor" if (other, name, lo2) == ("tsdf", "wsum", lo)
+                      else f"{who}: {name} and {other} share memory")
+            spans.append((name, lo, hi))
+    return dims
+
+
+def _one_device(who, **ts):
+    """Every tensor given (None: not passed) lies on the device of the first: the library takes pointers of one device."""
+    first = None
+    for name, t in ts.items():
+        if t is None:
+            continue
+        if first is None:
+            first = (name, t.device)
+        _need(t.device == first[1], lambda: f"{who}: {name} is on {t.device}, {first[0]} on {first[1]}: one device")
+
+
+def _packed_matrices(device, *ms):
+    """float64 CPU matrices as one buffer on `device` (one host-to-device copy) and the address of each in it: (buffer, pointers).
+    The caller keeps the buffer until its launch is queued."""
+    buffer = torch.cat([m.reshape(-1) for m in ms]).to(device)
+    sizes = [m.numel() * m.element_size() for m in ms]
+    return buffer, [C.c_void_p(buffer.data_ptr() + sum(sizes[:k])) for k in range(len(ms))]
+
+
+def _integrate_operands(who, planes, disp, Q, T, origin, voxel, trunc, valid, weight, max_weight, min_disp, max_disp, most_attributes=None,
+                        **more):
+    """What ops.volume_integrate and color.volume_integrate share up to the library call: parameters and matrices before any
+    tensor is looked at, then `planes` (by name, for _volume_planes), disp, valid and weight; `more`: the caller's further operands,
+    which must not require grad either.  Returns (d, v, w), the entry's (Q, G, C, m_per_view) behind the buffer that holds them,
+    (nx, ny, nz), (V, H, W) and (trunc, max_weight, lo, hi).  _one_device is left to the caller, who has every operand."""
+    gates = check_volume_parameters(trunc, max_weight, min_disp, max_disp, who)
+    m = volume_matrices(Q, T, origin, voxel)
+    _no_grad_operands(who, disp=disp, valid=valid, weight=weight, **more)
+    nz, ny, nx = _volume_planes(who, most_attributes=most_attributes, **planes)
+    d, v = _filter_planes(who, disp, valid)
+    if m.G.dim() == 3 and m.G.shape[0] != d.shape[0]:
+        raise ValueError(f"{who}: T {tuple(T.shape)} against disp {tuple(d.shape)}: one matrix, or one per view")
+    w = None if weight is None else _c(_plane_like(who, "weight", weight, d, ((torch.float32,)), "fp32"))
+    mats, pointers = _packed_matrices(d.device, Q.detach(), m.G, m.C)
+    return (d, v, w), (mats, *pointers, int(m.G.dim() == 3)), (nx, ny, nz), tuple(d.shape), gates
+
+
+def _raycast_operands(who, planes, Q_out, T, origin, voxel, size, near_disp, far_disp, step, max_steps, with_weight, most_attributes=None):
+    """What ops.volume_raycast and color.volume_raycast share up to the library call.  Returns the entry's (R, Rinv, m_per_view)
+    behind the buffer that holds them, (out, hit) -- hit None without with_weight --, (nx, ny, nz), (B, H, W) and the march."""
+    (H, W), *march = check_raycast_parameters(size, near_disp, far_disp, step, max_steps, who)
+    m = volume_matrices(Q_out, T, origin, voxel)
+    nz, ny, nx = _volume_planes(who, least=2, most_attributes=most_attributes, **planes)
+    _one_device(who, **planes)
+    B = m.R.shape[0] if m.R.dim() == 3 else 1
+    dev = planes["tsdf"].device
+    mats, pointers = _packed_matrices(dev, m.R, m.Rinv)
+    out = torch.empty(B, 1, H, W, device=dev, dtype=torch.float32)
+    hit = torch.empty(B, 1, H, W, device=dev, dtype=torch.float32) if with_weight else None
+    return (mats, *pointers, int(m.R.dim() == 3)), (out, hit), (nx, ny, nz), (B, H, W), march
 
 
 @torch.no_grad()
@@ -1452,20 +1521,10 @@ def volume_integrate(tsdf, wsum, disp, Q, T, origin, voxel, trunc, valid=None, w
     one thread per voxel, no atomics: bit-reproducible; a voxel no view sees keeps its bits.  include/ecm_volume.h states every
     operation.  A static-scene model; every default is untested for quality."""
     who = "volume_integrate"
-    trunc, max_weight, lo, hi = check_volume_parameters(trunc, max_weight, min_disp, max_disp)
-    m = volume_matrices(Q, T, origin, voxel)
-    _no_grad_operands(who, disp=disp, valid=valid, weight=weight)
-    nz, ny, nx = _volume_planes(who, tsdf, wsum)
-    d, v = _filter_planes(who, disp, valid)
-    V, H, W = d.shape
-    if m.G.dim() == 3 and m.G.shape[0] != V:
-        raise ValueError(f"{who}: T {tuple(T.shape)} against disp {tuple(d.shape)}: one matrix, or one per view")
-    w = None if weight is None else _c(_plane_like(who, "weight", weight, d, ((torch.float32,)), "fp32"))
-    n = m.G.numel()
-    mats = torch.cat([Q.detach().reshape(-1), m.G.reshape(-1), m.C.reshape(-1)]).to(d.device)        # one host-to-device copy
-    at = mats.data_ptr()
-    _lib.call("ecmv_integrate_fwd", _p(tsdf), _p(wsum), _p(d), _p(v), _p(w), C.c_void_p(at), C.c_void_p(at + 128),
-              C.c_void_p(at + 128 + 8 * n), int(m.G.dim() == 3), nx, ny, nz, V, H, W, trunc, max_weight, lo, hi, _stream())
+    (d, v, w), (held, *mats), dims, views, gates = _integrate_operands(who, dict(tsdf=tsdf, wsum=wsum), disp, Q, T, origin, voxel, trunc, valid,
+                                                                    weight, max_weight, min_disp, max_disp)
+    _one_device(who, tsdf=tsdf, wsum=wsum, disp=d, valid=v, weight=w)
+    _lib.call("ecmv_integrate_fwd", _p(tsdf), _p(wsum), _p(d), _p(v), _p(w), *mats, *dims, *views, *gates, _stream())
     return tsdf, wsum
 
 
@@ -1479,18 +1538,9 @@ def volume_raycast(tsdf, wsum, Q_out, T, origin, voxel, size, near_disp, far_dis
     tsdf between two consecutive samples that count, found by linear interpolation, is mapped back to a disparity; a back-face
     crossing met first ends the ray.  Holes are +0.0.  with_weight=True returns (out, hit_weight), the trilinear wsum at the
     crossing.  One launch, one thread per pixel: bit-reproducible.  include/ecm_volume.h states every operation."""
-    who = "volume_raycast"
-    (H, W), near_disp, far_disp, step, max_steps = check_raycast_parameters(size, near_disp, far_disp, step, max_steps)
-    m = volume_matrices(Q_out, T, origin, voxel)
-    nz, ny, nx = _volume_planes(who, tsdf, wsum, least=2)
-    B = m.R.shape[0] if m.R.dim() == 3 else 1
-    n = m.R.numel()
-    mats = torch.cat([m.R.reshape(-1), m.Rinv.reshape(-1)]).to(tsdf.device)
-    at = mats.data_ptr()
-    out = torch.empty(B, 1, H, W, device=tsdf.device, dtype=torch.float32)
-    hit = torch.empty(B, 1, H, W, device=tsdf.device, dtype=torch.float32) if with_weight else None
-    _lib.call("ecmv_raycast_fwd", _p(tsdf), _p(wsum), C.c_void_p(at), C.c_void_p(at + 8 * n), int(m.R.dim() == 3), _p(out), _p(hit),
-              nx, ny, nz, B, H, W, near_disp, far_disp, step, max_steps, _stream())
+    (held, *mats), (out, hit), dims, views, march = _raycast_operands("volume_raycast", dict(tsdf=tsdf, wsum=wsum), Q_out, T, origin, voxel, size,
+                                                                   near_disp, far_disp, step, max_steps, with_weight)
+    _lib.call("ecmv_raycast_fwd", _p(tsdf), _p(wsum), *mats, _p(out), _p(hit), *dims, *views, *march, _stream())
     return (out, hit) if with_weight else out
 
 

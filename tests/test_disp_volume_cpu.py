@@ -57,8 +57,10 @@ def _view(M, v):
     return M[v] if M.dim() == 3 else M
 
 
-def integrate_t(tsdf, wsum, disp, Q, G, Cm, trunc, valid=None, weight=None, max_weight=64.0, min_disp=0.0, max_disp=None):
-    """include/ecm_volume.h's integration on CPU tensors: (tsdf, wsum, touched), new tensors; touched: some view updated the voxel."""
+def integrate_t(tsdf, wsum, disp, Q, G, Cm, trunc, valid=None, weight=None, max_weight=64.0, min_disp=0.0, max_disp=None, seen=None):
+    """include/ecm_volume.h's integration on CPU tensors: (tsdf, wsum, touched), new tensors; touched: some view updated the voxel.
+    After the tsdf step of view v, seen(v, ok, (yi, xi), w, s) is called with the voxels the view updated, the pixel each voxel
+    reads, its weight and s = z_meas - z_vox (include/ecm_color.h's attribute step hangs there); it changes nothing here."""
     nz, ny, nx = tsdf.shape
     V, H, W = disp.shape
     lo, hi = f32(min_disp), f32(FLT_MAX if max_disp is None else min(max_disp, FLT_MAX))
@@ -94,6 +96,8 @@ def integrate_t(tsdf, wsum, disp, Q, G, Cm, trunc, valid=None, weight=None, max_
         Nn = torch.minimum(Wn, mw)
         X, N = torch.where(ok, Xn, X), torch.where(ok, Nn, N)
         touched |= ok
+        if seen is not None:
+            seen(v, ok, (yi, xi), w, s)
     return X, N, touched
 
 
@@ -105,8 +109,11 @@ def _blend(plane, cell, q):
     return e[0] + q[2] * (e[1] - e[0])
 
 
-def raycast_t(tsdf, wsum, R, Rinv, size, near_disp, far_disp, step=0.5, max_steps=MAX_STEPS):
-    """include/ecm_volume.h's raycast on CPU tensors: a dict of out and hit_weight [B,H,W] fp32, hit (bool) and n (fp64)."""
+def raycast_t(tsdf, wsum, R, Rinv, size, near_disp, far_disp, step=0.5, max_steps=MAX_STEPS, at_hit=None):
+    """include/ecm_volume.h's raycast on CPU tensors: a dict of out and hit_weight [B,H,W] fp32, hit (bool) and n (fp64).  Where
+    rays of view b hit, at_hit(b, hit, cell, q) is called with the mask, the clamped cell about each crossing ([x, y, z], long; 0
+    off the mask) and the crossing's position within it, the operands of hit_weight's blend (include/ecm_color.h's blend of the
+    attributes hangs there); it changes nothing here."""
     nz, ny, nx = tsdf.shape
     dims = (nx, ny, nz)
     H, W = size
@@ -115,7 +122,7 @@ def raycast_t(tsdf, wsum, R, Rinv, size, near_disp, far_disp, step=0.5, max_step
     ys, xs = (t.to(F64) for t in torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij"))
     zero = torch.zeros_like(xs)
     outs, weights, hits, ns = [], [], [], []
-    for Rm, Ri in zip(Rb, Rib):
+    for b, (Rm, Ri) in enumerate(zip(Rb, Rib)):
         hn, hf = [_row(Rm[r], xs, ys, near) for r in range(4)], [_row(Rm[r], xs, ys, far) for r in range(4)]
         gn, gf = [hn[a] / hn[3] for a in range(3)], [hf[a] / hf[3] for a in range(3)]
         dr = [gf[a] - gn[a] for a in range(3)]
@@ -154,7 +161,10 @@ def raycast_t(tsdf, wsum, R, Rinv, size, near_disp, far_disp, step=0.5, max_step
             val = (_row(Ri[2], ps[0], ps[1], ps[2]) / _row(Ri[3], ps[0], ps[1], ps[2])).to(F32)
             res = torch.where(hit, val, res)
             wc = [torch.where(hit, torch.floor(ps[a]).clamp(0, dims[a] - 2), zero) for a in range(3)]
-            hw = torch.where(hit, _blend(wsum, [t.long() for t in wc], [ps[a] - wc[a] for a in range(3)]).to(F32), hw)
+            at, within = [t.long() for t in wc], [ps[a] - wc[a] for a in range(3)]
+            hw = torch.where(hit, _blend(wsum, at, within).to(F32), hw)
+            if at_hit is not None and bool(hit.any()):
+                at_hit(b, hit, at, within)
             hit_any |= hit
             done = done | hit | back
             before, f0, p0 = ok, f, p
@@ -595,6 +605,16 @@ def test_volume_op_refusals():
     for kw, match in (({"valid": z}, "valid"), ({"weight": fake(1, 4, 9)}, "weight"), ({"weight": fake(1, 4, 8, dtype=F64)}, "weight")):
         with pytest.raises(RuntimeError, match=match):
             integ(**kw)
+    # every operand on one device, in the colour ops' words: a foreign pointer never reaches a kernel
+    elsewhere = lambda *shape: torch.zeros(*shape, device="meta").as_subclass(type(z))           # noqa: E731  (a tensor of another device)
+    for call in (lambda: integ(disp=elsewhere(1, 4, 8)), lambda: integ(weight=elsewhere(1, 4, 8)),
+                 lambda: integ(valid=elsewhere(1, 4, 8).to(torch.uint8)), lambda: integ(fake(3, 4, 5), elsewhere(3, 4, 5)),
+                 lambda: cast(fake(3, 4, 5), elsewhere(3, 4, 5))):
+        with pytest.raises(RuntimeError, match="is on .*: one device"):
+            call()
+    big = fake(4, 4, 5)
+    with pytest.raises(RuntimeError, match="share memory"):                # one alias rule, by byte span, for every pair of planes
+        integ(big[:3], big[1:])
     assert ops.check_volume_parameters(0.5) == (0.5, 64.0, 0.0, FLT_MAX)
     assert ops.check_raycast_parameters((4, 8), 8, 2) == ((4, 8), 8.0, 2.0, 0.5, MAX_STEPS)
 

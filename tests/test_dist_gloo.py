@@ -5,6 +5,7 @@ import os
 import sys
 import tempfile
 
+import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp

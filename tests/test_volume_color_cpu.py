@@ -22,9 +22,9 @@ import torch
 import abi_refusal_child as child
 from test_abi_refusals import EINVAL, EUNSUP, HIDE, Row, _report, calls_of, classify
 from test_abi_types import INCLUDE, _strip, compare, lib_mod, package_entry_names, parse_header  # noqa: F401  (lib_mod: a fixture)
-from test_disp_volume_cpu import (DIMS, F32, F64, FAR, FIFTH, FLT_MAX, H0, HIT_SHARE, MAPPER_HELD_OUT, MAPPER_MIN_DISP, MAPPER_STD, MAX_STEPS, NEAR, ORIGIN,
-                                  TRUNC, VIEWS, VOXEL, W0, _blend, _row, _view, closed_loop, empty, f32, integrate_t, mapper_loop, mapper_poses, raycast_t,
-                                  scene_views, unit_setup)
+from test_disp_volume_cpu import (DIMS, F32, F64, FAR, FIFTH, H0, HIT_SHARE, MAPPER_HELD_OUT, MAPPER_MIN_DISP, MAPPER_STD, MAX_STEPS, NEAR, ORIGIN, TRUNC,
+                                  VIEWS, VOXEL, W0, _row, closed_loop, empty, f32, integrate_t, mapper_loop, mapper_poses, raycast_t, scene_views,
+                                  unit_setup)
 from test_disp_warp_cpu import bits
 from test_motion_align_cpu import PLANES, fake, render, scene_q
 from test_volume_mesh_cpu import mesh_t, read_ply
@@ -45,52 +45,23 @@ def ecm():
 def integrate_color_t(tsdf, wsum, attr, asum, disp, attributes, Q, G, Cm, trunc, valid=None, weight=None, max_weight=64.0, min_disp=0.0,
                       max_disp=None):
     """include/ecm_color.h's integration on CPU tensors: (tsdf, wsum, attr, asum, touched, coloured), new tensors; touched: some
-    view updated the voxel's tsdf, coloured: some view updated its attributes.  The geometry step is integrate_t's, line by line."""
-    nz, ny, nx = tsdf.shape
-    V, H, W = disp.shape
-    A = attr.shape[0]
-    lo, hi = f32(min_disp), f32(FLT_MAX if max_disp is None else min(max_disp, FLT_MAX))
+    view updated the voxel's tsdf, coloured: some view updated its attributes.  The geometry step is integrate_t itself; the
+    attribute step is the hook it calls after each view's tsdf step."""
     tr, mw = float(f32(trunc)), f32(max_weight)
-    kk, jj, ii = (t.to(F64) for t in torch.meshgrid(torch.arange(nz), torch.arange(ny), torch.arange(nx), indexing="ij"))
-    X, N, Y, Na = tsdf.clone(), wsum.clone(), attr.clone(), asum.clone()
-    touched = torch.zeros(nz, ny, nx, dtype=torch.bool)
-    coloured = torch.zeros(nz, ny, nx, dtype=torch.bool)
-    zero = torch.zeros_like(ii)
-    for v in range(V):
-        Gv, Cv = _view(G, v), _view(Cm, v)
-        h = [_row(Gv[r], ii, jj, kk) for r in range(4)]
-        u, vv, dv = h[0] / h[3], h[1] / h[3], h[2] / h[3]
-        ok = torch.isfinite(u) & torch.isfinite(vv) & torch.isfinite(dv) & (dv > 0)
-        px, py = torch.floor(u + 0.5), torch.floor(vv + 0.5)
-        ok = ok & (px >= 0) & (px <= W - 1) & (py >= 0) & (py <= H - 1)
-        px, py = torch.where(ok, px, zero), torch.where(ok, py, zero)
-        xi, yi = px.long(), py.long()
-        d = disp[v][yi, xi]
-        val = torch.ones_like(ok) if valid is None else valid[v][yi, xi] != 0
-        w = torch.ones_like(d) if weight is None else weight[v][yi, xi]
-        ok = ok & torch.isfinite(d) & val & (d > lo) & (d <= hi) & torch.isfinite(w) & (w > 0)
-        fd = d.to(F64)
-        P3 = _row(Q[3], px, py, fd)
-        ok = ok & torch.isfinite(P3) & (P3 != 0)
-        z_meas = _row(Q[2], px, py, fd) / P3
-        z_vox = _row(Cv[2], ii, jj, kk)
-        ok = ok & torch.isfinite(z_meas) & (z_meas > 0) & torch.isfinite(z_vox) & (z_vox > 0)
-        s = z_meas - z_vox
-        ok = ok & ~(s < -tr)
-        t = torch.clamp(s / tr, max=1.0).to(F32)
-        Wn = N + w
-        Xn = (X * N + t * w) / Wn
-        Nn = torch.minimum(Wn, mw)
-        X, N = torch.where(ok, Xn, X), torch.where(ok, Nn, N)
-        touched |= ok
-        # the attribute step
-        c = attributes[v][:, yi, xi]                                        # [A,nz,ny,nx]
+    Y, Na = attr.clone(), asum.clone()
+    coloured = torch.zeros(tsdf.shape, dtype=torch.bool)
+
+    def attribute_step(v, ok, pixel, w, s):
+        nonlocal Y, Na, coloured
+        c = attributes[v][:, pixel[0], pixel[1]]                            # [A,nz,ny,nx]
         paint = ok & (s <= tr) & torch.isfinite(c).all(0)
         An = Na + w
         Yn = (Y * Na + c * w) / An
         Y, Na = torch.where(paint, Yn, Y), torch.where(paint, torch.minimum(An, mw), Na)
         coloured |= paint
-    assert Y.shape == (A, nz, ny, nx)
+
+    X, N, touched = integrate_t(tsdf, wsum, disp, Q, G, Cm, trunc, valid, weight, max_weight, min_disp, max_disp, seen=attribute_step)
+    assert Y.shape == attr.shape
     return X, N, Y, Na, touched, coloured
 
 
@@ -115,66 +86,17 @@ def _sample(attr, asum, cell, q):
 
 
 def raycast_color_t(tsdf, wsum, attr, asum, R, Rinv, size, near_disp, far_disp, step=0.5, max_steps=MAX_STEPS):
-    """include/ecm_color.h's raycast on CPU tensors: raycast_t's dict (its march, line by line) plus colors [B,A,H,W] fp32."""
-    nz, ny, nx = tsdf.shape
-    dims = (nx, ny, nz)
-    A = attr.shape[0]
-    H, W = size
-    Rb, Rib = (R, Rinv) if R.dim() == 3 else (R[None], Rinv[None])
-    near, far, st = float(f32(near_disp)), float(f32(far_disp)), float(f32(step))
-    ys, xs = (t.to(F64) for t in torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij"))
-    zero = torch.zeros_like(xs)
-    outs, weights, hits, ns, cols = [], [], [], [], []
-    for Rm, Ri in zip(Rb, Rib):
-        hn, hf = [_row(Rm[r], xs, ys, near) for r in range(4)], [_row(Rm[r], xs, ys, far) for r in range(4)]
-        gn, gf = [hn[a] / hn[3] for a in range(3)], [hf[a] / hf[3] for a in range(3)]
-        dr = [gf[a] - gn[a] for a in range(3)]
-        ln = torch.sqrt((dr[0] * dr[0] + dr[1] * dr[1]) + dr[2] * dr[2])
-        nd = torch.ceil(ln / st)
-        live = (nd >= 1) & (nd <= max_steps)
-        for t in gn + gf:
-            live = live & torch.isfinite(t)
-        ndc = torch.where(live, nd, torch.ones_like(nd))
-        done = ~live
-        before = torch.zeros_like(live)
-        f0, p0 = zero, [zero, zero, zero]
-        res, hw, hit_any = torch.zeros(H, W, dtype=F32), torch.zeros(H, W, dtype=F32), torch.zeros_like(live)
-        col = torch.zeros(A, H, W, dtype=F32)
-        for m in range(int(ndc.max()) + 1):
-            act = ~done & (m <= ndc)
-            if not bool(act.any()):
-                break
-            s = m / ndc
-            p = [gn[a] + dr[a] * s for a in range(3)]
-            c = [torch.floor(p[a]) for a in range(3)]
-            ok = act
-            for a in range(3):
-                ok = ok & (c[a] >= 0) & (c[a] <= dims[a] - 2)
-            cell = [torch.where(ok, c[a], zero).long() for a in range(3)]
-            q = [p[a] - c[a] for a in range(3)]
-            for dz in (0, 1):
-                for dy in (0, 1):
-                    for dx in (0, 1):
-                        ok = ok & (wsum[cell[2] + dz, cell[1] + dy, cell[0] + dx] > 0)
-            f = _blend(tsdf, cell, q)
-            pair = ok & before
-            hit = pair & (f0 > 0) & (f <= 0)
-            back = pair & (f0 < 0) & (f > 0)
-            al = f0 / (f0 - f)
-            ps = [p0[a] + (p[a] - p0[a]) * al for a in range(3)]
-            val = (_row(Ri[2], ps[0], ps[1], ps[2]) / _row(Ri[3], ps[0], ps[1], ps[2])).to(F32)
-            res = torch.where(hit, val, res)
-            wc = [torch.where(hit, torch.floor(ps[a]).clamp(0, dims[a] - 2), zero) for a in range(3)]
-            hw = torch.where(hit, _blend(wsum, [t.long() for t in wc], [ps[a] - wc[a] for a in range(3)]).to(F32), hw)
-            if bool(hit.any()):
-                qs = [torch.where(hit, ps[a] - wc[a], zero) for a in range(3)]
-                col = torch.where(hit, _sample(attr, asum, [t.long() for t in wc], qs), col)
-            hit_any |= hit
-            done = done | hit | back
-            before, f0, p0 = ok, f, p
-        outs.append(res), weights.append(hw), hits.append(hit_any), ns.append(nd), cols.append(col)
-    return {"out": torch.stack(outs), "hit_weight": torch.stack(weights), "hit": torch.stack(hits), "n": torch.stack(ns),
-            "colors": torch.stack(cols)}
+    """include/ecm_color.h's raycast on CPU tensors: raycast_t's dict (the march is raycast_t itself) plus colors [B,A,H,W] fp32,
+    blended by the hook it calls at the hits."""
+    B = R.shape[0] if R.dim() == 3 else 1
+    cols = [torch.zeros((attr.shape[0],) + tuple(size), dtype=F32) for _ in range(B)]
+
+    def blend_attributes(b, hit, cell, q):
+        zero = torch.zeros_like(q[0])
+        cols[b] = torch.where(hit, _sample(attr, asum, cell, [torch.where(hit, q[a], zero) for a in range(3)]), cols[b])
+
+    cast = raycast_t(tsdf, wsum, R, Rinv, size, near_disp, far_disp, step, max_steps, at_hit=blend_attributes)
+    return {**cast, "colors": torch.stack(cols)}
 
 
 def sample_t(attr, asum, Minv, points):

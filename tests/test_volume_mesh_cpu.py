@@ -538,16 +538,18 @@ def test_write_ply_reads_back_byte_for_byte(tmp_path):
     props, v, f, body = read_ply(path)
     assert props == ["x", "y", "z", "nx", "ny", "nz"]
     assert v.tobytes() == torch.cat([res.vertices, res.normals], 1).numpy().tobytes() and f.tobytes() == res.faces.numpy().tobytes()
-    want = v.tobytes() + b"".join(struct.pack("<Biii", 3, *row) for row in res.faces.tolist())
-    assert body == want
+    # the face block against the packing the writer once had, restated here: one struct.pack per face
+    face_block = lambda faces: b"".join(struct.pack("<Biii", 3, a, b, c) for a, b, c in faces.tolist())   # noqa: E731
+    assert body[len(v.tobytes()):] == face_block(res.faces) and body == v.tobytes() + face_block(res.faces)
     bare = str(tmp_path / "bare.ply")
     mesh.write_ply(bare, mesh.Mesh(res.vertices, res.faces, None, None))
-    props, v, f, _ = read_ply(bare)
+    props, v, f, body = read_ply(bare)
     assert props == ["x", "y", "z"] and v.tobytes() == res.vertices.numpy().tobytes() and f.tobytes() == res.faces.numpy().tobytes()
+    assert body[12 * len(res.vertices):] == face_block(res.faces) and len(res.faces) > 0
     empty = str(tmp_path / "empty.ply")
     mesh.write_ply(empty, mesh.Mesh(torch.zeros(0, 3), torch.zeros(0, 3, dtype=torch.int32), torch.zeros(0, 3), None))
     props, v, f, body = read_ply(empty)
-    assert len(v) == 0 and len(f) == 0 and body == b""
+    assert len(v) == 0 and len(f) == 0 and body == b"" == face_block(torch.zeros(0, 3, dtype=torch.int32))
     for bad in ((res.vertices, res.faces), "mesh", None):
         with pytest.raises(ValueError, match="a Mesh"):
             mesh.write_ply(path, bad)

@@ -1,6 +1,6 @@
 """ctypes binding of libecm_hip.so (the C ABI declared in include/ecm_hip.h and, for the geometry, rectification, temporal and
-motion, volume, mesh and colour entries, include/ecm_geometry.h, include/ecm_rectify.h, include/ecm_temporal.h,
-include/ecm_motion.h, include/ecm_volume.h, include/ecm_mesh.h and include/ecm_color.h).
+motion, volume, mesh, colour and augmentation entries, include/ecm_geometry.h, include/ecm_rectify.h, include/ecm_temporal.h,
+include/ecm_motion.h, include/ecm_volume.h, include/ecm_mesh.h, include/ecm_color.h and include/ecm_augment.h).
 
 The product path has NO fallback: if the library is missing or a call fails, a RuntimeError is
 raised.  Each table below mirrors its header one to one: tests/test_abi_types.py parses every header of TABLES and compares
@@ -284,6 +284,30 @@ def _each_table():
     return _every_table() + [row for registry in NEWEST_REGISTRIES for table, _ in registry.values() for row in table.items()]
 
 
+# The augmentation entries (include/ecm_augment.h, prefix ecma_): the KITTI training transform in the frame decode, and its colour
+# jitter on resident uint8 images.
+AUGMENT_PROTOTYPES = {
+    "ecma_jitter_tile": (_I, []),
+    "ecma_jitter_scratch_bytes": (_LL, [_I, _I, _I]),
+    "ecma_color_jitter_fwd": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _LL, _P]),
+    "ecma_frame_prep_jitter_fwd": (_I, [_P, _P, _I] + [_P] * 4 + [_I, _I, _I, _P, _P, _I, _I] + [_P] * 7 + [_LL, _P]),
+}
+
+AUGMENT_TABLES = {
+    "ecm_augment.h": (AUGMENT_PROTOTYPES, "ecma_"),
+}
+
+# tests/test_volume_color_cpu.py pins NEWEST_REGISTRIES == (COLOR_TABLES,) and the row count of _each_table(), so a ninth header can
+# be a row of neither without an edit of that file.  One more tuple of registries of the same form: load() and missing_symbols()
+# walk _each_table() and then these, so call() and query() serve them alike, and the new header's own test file holds it to the
+# same census.
+LATEST_REGISTRIES = (AUGMENT_TABLES,)
+
+
+def _whole_table():
+    return _each_table() + [row for registry in LATEST_REGISTRIES for table, _ in registry.values() for row in table.items()]
+
+
 _lib = None
 
 
@@ -296,7 +320,7 @@ def load():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or `make -C explicit-context-mapping-for-stereo-matching_amd/csrc`). There is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in _each_table():
+        for name, (res, args) in _whole_table():
             fn = getattr(lib, name, None)
             if fn is None:
                 continue            # reported by missing_symbols()/tests; calling it raises below
@@ -307,7 +331,7 @@ def load():
 
 def missing_symbols():
     lib = load()
-    return [n for n, _ in _each_table() if not hasattr(lib, n)]
+    return [n for n, _ in _whole_table() if not hasattr(lib, n)]
 
 
 # Optional per-launch timing (bench.py's roofline leg): name -> list of (start_event, end_event, int_args).

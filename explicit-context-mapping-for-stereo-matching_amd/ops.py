@@ -9,9 +9,11 @@ from __future__ import annotations
 import collections
 import contextlib as _contextlib
 import ctypes as C
+import dataclasses
 import math
 import numbers
 import os as _os
+import random
 
 import torch
 
@@ -2536,6 +2538,168 @@ def _frame_prep(frames, crop_y0, crop_x0, th, tw, split, tail, mean, std, want_i
     else:
         _lib.call("ecm_frame_prep", _p(frames), _p(left), _p(right), _p(disp), _p(image), B, H, W, ys, xs, int(th), int(tw),
                   split, int(tail), m3, s3, _stream())
+    return (left, right, disp, image) if want_image else (left, right, disp)
+
+
+# ------------------------------------------------------------------------------------ the KITTI training transform
+# DESIGN.md section 37; include/ecm_augment.h states every operation.  KITTI.transform's train branch (cmf/loader/KITTI.py:144-191)
+# per view: ColorJitter(0.4, 0.4, 0.4, 0.4) on the PIL image, the PCA "lighting" shift, clamp to 0..1, normalise.  The jitter is
+# Pillow's arithmetic on uint8, byte for byte (tests/golden/g13_jitter.npz); what torchvision 0.2 adds around it -- the ranges
+# drawn, the shuffle, adjust_hue's uint8 wrap -- is restated from its source, not executed.  Forward only.
+KITTI_JITTER = dict(brightness=0.4, contrast=0.4, saturation=0.4, hue=0.4, alphastd=0.1)                  # KITTI.py:20,164
+JITTER_BRIGHTNESS, JITTER_CONTRAST, JITTER_SATURATION, JITTER_HUE = 0, 1, 2, 3                             # the codes of an order
+_PCA_EIGVAL = (0.2175, 0.0188, 0.0045)                                                                    # KITTI.py:21
+_PCA_EIGVEC = ((-0.5675, 0.7192, 0.4009), (-0.5808, -0.0045, -0.8140), (-0.5836, -0.6948, 0.4203))        # KITTI.py:22-26
+_JITTER_MAX_PIXELS = 1 << 24
+
+
+@dataclasses.dataclass
+class JitterParams:
+    """The drawn parameters of a batch, CPU tensors, view 0 = left and 1 = right: factors [B,2,3] fp32 (brightness, contrast,
+    saturation), order [B,2,4] int32 (the codes of the operations present, in the order they run, then -1), hue_shift [B,2]
+    int32 in 0..255, pca [B,2,3] fp32 (the shift added to the 0..1 image per channel)."""
+    factors: torch.Tensor
+    order: torch.Tensor
+    hue_shift: torch.Tensor
+    pca: torch.Tensor
+
+
+def jitter_params(batch, rng, gen, brightness=0.4, contrast=0.4, saturation=0.4, hue=0.4, alphastd=0.1):
+    """Draw KITTI.transform's parameters for `batch` samples, the left view and then the right one of each, as torchvision 0.2's
+    ColorJitter.get_params and KITTI.py's Lighting do: uniform(max(0, 1 - x), 1 + x) for brightness, contrast and saturation,
+    uniform(-hue, hue) for the hue (stored as adjust_hue's uint8 wrap, trunc(h * 255) mod 256), a shuffle of the operations
+    present (a strength of 0 omits its operation), and alpha ~ N(0, alphastd) three times for the PCA shift, formed by the
+    loader's own torch statements.  rng is a random.Random, gen a CPU torch.Generator: the caller's, so the draws repeat with
+    their seeds (the reference draws from global generators inside DataLoader workers; its stream is not matched)."""
+    who = "jitter_params"
+    batch = _integer(who, "batch", batch, 1, None)
+    strengths = [_real(who, n, v, ">= 0") for n, v in (("brightness", brightness), ("contrast", contrast), ("saturation", saturation))]
+    hue, alphastd = _real(who, "hue", hue, ">= 0"), _real(who, "alphastd", alphastd, ">= 0")
+    if hue > 0.5:
+        raise ValueError(f"{who}: hue {hue}: at most 0.5, as torchvision's")
+    if not isinstance(rng, random.Random) or not isinstance(gen, torch.Generator):
+        raise ValueError(f"{who}: rng {type(rng).__name__}, gen {type(gen).__name__}: a random.Random and a torch.Generator")
+    factors, order = torch.ones(batch, 2, 3, dtype=torch.float32), torch.full((batch, 2, 4), -1, dtype=torch.int32)
+    shift, pca = torch.zeros(batch, 2, dtype=torch.int32), torch.zeros(batch, 2, 3, dtype=torch.float32)
+    eigval, eigvec = torch.Tensor(_PCA_EIGVAL), torch.Tensor(_PCA_EIGVEC)
+    for b in range(batch):
+        for view in range(2):
+            present = []
+            for code, x in enumerate(strengths):
+                if x > 0:
+                    factors[b, view, code] = rng.uniform(max(0, 1 - x), 1 + x)
+                    present.append(code)
+            if hue > 0:
+                shift[b, view] = int(rng.uniform(-hue, hue) * 255) % 256
+                present.append(JITTER_HUE)
+            rng.shuffle(present)
+            order[b, view, :len(present)] = torch.tensor(present, dtype=torch.int32)
+            if alphastd > 0:                                               # KITTI.py:29-36
+                alpha = torch.empty(3).normal_(0, alphastd, generator=gen)
+                pca[b, view] = eigvec.clone().mul(alpha.view(1, 3).expand(3, 3)).mul(eigval.view(1, 3).expand(3, 3)).sum(1).squeeze()
+    return JitterParams(factors, order, shift, pca)
+
+
+def jitter_tile():
+    """The pixels of one tile of the contrast reduction (a query of the library: no GPU needed)."""
+    return int(_lib.query("ecma_jitter_tile"))
+
+
+def _jitter_views(who, views, factors, order, hue_shift, pca=None):
+    """The per-view parameters as flat host lists, refused with ValueError where the library would refuse them."""
+    def flat(name, v, shape, dtype):
+        t = torch.as_tensor(v).detach().cpu()
+        if tuple(t.shape) != shape or (t.is_floating_point() and not dtype.is_floating_point) or t.dtype == torch.bool or t.is_complex():
+            raise ValueError(f"{who}: {name} {tuple(t.shape)} {t.dtype}: want {shape} of {'floats' if dtype.is_floating_point else 'integers'}")
+        return t.to(torch.float64 if dtype.is_floating_point else torch.int64).reshape(views, -1)
+    f = flat("factors", factors, (views, 3), torch.float32)
+    o, h = flat("order", order, (views, 4), torch.int32), flat("hue_shift", hue_shift, (views,), torch.int32)
+    if not bool(torch.isfinite(f).all()) or bool((f < 0).any()) or bool((f > _FLT_MAX).any()):
+        raise ValueError(f"{who}: factors: finite fp32 values >= 0")
+    for v, row in enumerate(o.tolist()):
+        codes = [c for c in row if c != -1]
+        if row[len(codes):] != [-1] * (4 - len(codes)) or any(c < 0 or c > 3 for c in codes) or len(set(codes)) != len(codes):
+            raise ValueError(f"{who}: order {row} of view {v}: distinct codes 0..3, then -1")
+    if bool((h < 0).any()) or bool((h > 255).any()):
+        raise ValueError(f"{who}: hue_shift: 0..255")
+    out = [_host(C.c_float, f.reshape(-1).tolist()), _host(C.c_int, o.reshape(-1).tolist()), _host(C.c_int, h.reshape(-1).tolist())]
+    if pca is not None:
+        p = flat("pca", pca, (views, 3), torch.float32)
+        if not bool(torch.isfinite(p).all()) or bool((p.abs() > _FLT_MAX).any()):
+            raise ValueError(f"{who}: pca: finite fp32 values")
+        out.append(_host(C.c_float, p.reshape(-1).tolist()))
+    return out
+
+
+def _jitter_scratch(who, views, rows, cols, dev):
+    if rows > 65535 or rows * cols > _JITTER_MAX_PIXELS:
+        raise RuntimeError(f"{who}: views of {rows} x {cols}: at most 65535 rows and 2^24 pixels")
+    nbytes = int(_lib.query("ecma_jitter_scratch_bytes", views, rows, cols))
+    _need(nbytes > 0, lambda: f"{who}: no scratch size for {views} views of {rows} x {cols}")
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev), C.c_longlong(nbytes)
+
+
+def color_jitter(images_u8, factors, order, hue_shift):
+    """torchvision's ColorJitter with given parameters on resident images: images_u8 uint8 [N,H,W,3] -> uint8 [N,H,W,3], Pillow's
+    result byte for byte.  Per image: factors [N,3] (brightness, contrast, saturation; read where the operation is present), order
+    [N,4] (codes 0 brightness, 1 contrast, 2 saturation, 3 hue in the order they run, then -1) and hue_shift [N] in 0..255, host
+    values.  Each operation works on the uint8 result of the one before; contrast blends with the rounded mean gray of the image
+    as it then stands.  Two launches where an image has contrast, else one; integer sums only: bit-reproducible."""
+    who = "color_jitter"
+    if not isinstance(images_u8, torch.Tensor):
+        raise ValueError(f"{who}: images_u8 {type(images_u8).__name__}: a tensor")
+    _on_device(images_u8)
+    _need(images_u8.dtype == torch.uint8 and images_u8.dim() == 4 and images_u8.shape[3] == 3 and images_u8.numel() > 0,
+          lambda: f"{who}: images_u8 {images_u8.dtype} {tuple(images_u8.shape)}: want uint8 [N,H,W,3], none of them 0")
+    N, H, W, _ = images_u8.shape
+    fh, oh, hh = _jitter_views(who, N, factors, order, hue_shift)
+    scratch, nbytes = _jitter_scratch(who, N, H, W, images_u8.device)
+    src = images_u8.contiguous()
+    out = torch.empty_like(src)
+    _lib.call("ecma_color_jitter_fwd", _p(src), _p(out), N, H, W, fh, oh, hh, _p(scratch), nbytes, _stream())
+    return out
+
+
+def frame_prep_jitter(frames, crop_y0, crop_x0, th, tw, params, mean=FLYING3D_MEAN, std=FLYING3D_STD, want_image=False):
+    """frame_prep's window decode of a packed shard with KITTI.transform's training augmentation in it (KITTI.py:144-191): frames
+    = (rgb6 uint8 [B,H,W,6], disparity fp16|fp32 [B,H,W]), windows of th x tw at crop_y0/crop_x0, params a JitterParams of B
+    samples (jitter_params) -> left, right [B,3,th,tw], disparity [B,th,tw] (and, with want_image, the left view clamped to 0..1
+    as KITTI.py:189 returns it -- not frame_prep's raw 0..255 plane).  Per view: color_jitter's operations on the window, then in
+    fp32 u / 255 + pca, clamp to 0..1, (x - mean) / std.  float32 [B,H,W,7] frames are not taken."""
+    who = "frame_prep_jitter"
+    if not isinstance(frames, (tuple, list)) or len(frames) != 2 or not all(isinstance(t, torch.Tensor) for t in frames):
+        raise ValueError(f"{who}: frames: a packed shard (uint8 [B,H,W,6], fp16|fp32 [B,H,W])")
+    if not isinstance(params, JitterParams):
+        raise ValueError(f"{who}: params {type(params).__name__}: a JitterParams (jitter_params)")
+    rgb, dsp = frames
+    _on_device(rgb, dsp)
+    _need(rgb.dtype == torch.uint8 and dsp.dtype in (torch.float16, torch.float32) and rgb.dim() == 4 and rgb.shape[-1] == 6
+          and tuple(rgb.shape[:3]) == tuple(dsp.shape) and rgb.numel() > 0 and rgb.device == dsp.device,
+          lambda: f"{who}: packed shard must be (uint8 [B,H,W,6], fp16|fp32 [B,H,W]) on one device, got {rgb.dtype} {tuple(rgb.shape)} / "
+                  f"{dsp.dtype} {tuple(dsp.shape)}")
+    B, H, W = dsp.shape
+    th, tw = _integer(who, "th", th, 1, None), _integer(who, "tw", tw, 1, None)
+    ys, xs = [int(v) for v in crop_y0], [int(v) for v in crop_x0]
+    if len(ys) != B or len(xs) != B or any(y < 0 or y + th > H for y in ys) or any(x < 0 or x + tw > W for x in xs):
+        raise ValueError(f"{who}: windows of {th} x {tw} at {ys} / {xs}: one per sample, inside the {H} x {W} frame")
+    fields = dict(factors=(B, 2, 3), order=(B, 2, 4), hue_shift=(B, 2), pca=(B, 2, 3))
+    for name, shape in fields.items():
+        t = getattr(params, name)
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
+            raise ValueError(f"{who}: params.{name}: a tensor of {shape} for {B} samples")
+    fh, oh, hh, ph = _jitter_views(who, 2 * B, *(getattr(params, name).reshape((2 * B,) + shape[2:]) for name, shape in fields.items()))
+    m3, s3 = [float(v) for v in mean], [float(v) for v in std]
+    if len(m3) != 3 or len(s3) != 3:
+        raise ValueError(f"{who}: mean {m3}, std {s3}: three values each")
+    scratch, nbytes = _jitter_scratch(who, 2 * B, th, tw, rgb.device)
+    rgb, dsp = rgb.contiguous(), dsp.contiguous()
+    left = torch.empty(B, 3, th, tw, device=rgb.device, dtype=torch.float32)
+    right = torch.empty_like(left)
+    disp = torch.empty(B, th, tw, device=rgb.device, dtype=torch.float32)
+    image = torch.empty_like(left) if want_image else None
+    _lib.call("ecma_frame_prep_jitter_fwd", _p(rgb), _p(dsp), int(dsp.dtype == torch.float16), _p(left), _p(right), _p(disp), _p(image), B,
+              H, W, _host(C.c_int, ys), _host(C.c_int, xs), th, tw, fh, oh, hh, ph, _host(C.c_float, m3), _host(C.c_float, s3),
+              _p(scratch), nbytes, _stream())
     return (left, right, disp, image) if want_image else (left, right, disp)
 
 

@@ -182,12 +182,24 @@ class ShardFeeder:
     box of the valid disparities, KITTI.py:84-97), "test" (Flying3d's 540 -> 576 tail padding, Flying3d.py:66-72) or
     "kitti_test" (top / left padding to 384x1248, KITTI.py:98-108; batch 1 or equal-sized frames).
     Data parallel: rank r of `world` takes every world-th batch of the epoch's order (no two ranks see the same frame in an
-    epoch).  The order is a seeded permutation per epoch (the reference shuffles with the DataLoader's default generator)."""
+    epoch).  The order is a seeded permutation per epoch (the reference shuffles with the DataLoader's default generator).
+    jitter: None, or the strengths of KITTI.transform's photometric augmentation (KITTI.py:144-191) as a dict of brightness,
+    contrast, saturation, hue and alphastd (`ops.KITTI_JITTER` is the reference's set): the "train" split then decodes with
+    ops.frame_prep_jitter, its parameters drawn per batch from generators seeded like the windows' (the windows themselves are
+    those of jitter=None), `last_jitter` holds the JitterParams of the batch just delivered, and want_image gives the left view
+    clamped to 0..1 (KITTI.py:189) instead of frame_prep's raw plane."""
 
     def __init__(self, reader, batch, split="train", device="cuda", rank=0, world=1, seed=0, prefetch=2, shuffle=None,
-                 kitti=False, crop=(256, 512), want_image=False):
+                 kitti=False, crop=(256, 512), want_image=False, jitter=None):
         from . import ops
         self.ops = ops
+        if jitter is not None:
+            if not isinstance(jitter, dict) or set(jitter) != set(ops.KITTI_JITTER):
+                raise ValueError(f"ShardFeeder: jitter {jitter!r}: None or a dict of {sorted(ops.KITTI_JITTER)}")
+            if split != "train":
+                raise ValueError(f"ShardFeeder: jitter is the training transform: split {split!r} does not take it")
+            ops.jitter_params(1, random.Random(0), torch.Generator(), **jitter)    # refuses bad strengths here, not in the thread
+        self.jitter, self.last_jitter = jitter, None
         self.reader, self.batch, self.split, self.kitti = reader, int(batch), split, bool(kitti)
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -244,6 +256,9 @@ class ShardFeeder:
         try:                                                                # whatever goes wrong reaches the consumer
             torch.cuda.set_device(self.device)
             rng = random.Random(self.seed * 7919 + epoch * 104729 + self.rank)
+            if self.jitter is not None:                                     # generators of their own: the windows stay jitter=None's
+                jrng = random.Random(f"jitter/{self.seed}/{epoch}/{self.rank}")
+                jgen = torch.Generator().manual_seed((self.seed * 7919 + epoch * 104729 + self.rank) * 2 + 1)
             k = 0
             for idx in self._order(epoch):
                 if self._stop.is_set():
@@ -275,7 +290,12 @@ class ShardFeeder:
                     slot["h2d_done"] = torch.cuda.Event()
                     slot["h2d_done"].record(self._copy)
                     frames = (slot["dev"]["rgb"], slot["dev"]["dsp"])
-                    if self.split == "train":
+                    params = None
+                    if self.split == "train" and self.jitter is not None:
+                        params = self.ops.jitter_params(self.batch, jrng, jgen, **self.jitter)
+                        out = self.ops.frame_prep_jitter(frames, [0] * self.batch, [0] * self.batch, H, W, params,
+                                                         want_image=self.want_image)
+                    elif self.split == "train":
                         out = self.ops.frame_prep(frames, [0] * self.batch, [0] * self.batch, H, W, want_image=self.want_image)
                     elif self.split == "test":                             # 540 rows + the last 36 again (Flying3d.py:66-72)
                         out = self.ops.frame_prep(frames, [0] * self.batch, [0] * self.batch, min(H, 540) + 36, min(W, 960),
@@ -286,7 +306,7 @@ class ShardFeeder:
                         raise ValueError(f"unknown split {self.split!r}")
                     ready = torch.cuda.Event()
                     ready.record(self._copy)
-                self._q.put((out, ready, idx, wins))
+                self._q.put((out, ready, idx, wins, params))
                 k += 1
             self._q.put(None)
         except BaseException as e:                                          # surfaced by the consumer
@@ -317,13 +337,13 @@ class ShardFeeder:
             if self._err is not None:
                 raise self._err
             raise StopIteration
-        out, ready, idx, wins = item
+        out, ready, idx, wins, params = item
         cur = torch.cuda.current_stream(self.device)
         cur.wait_event(ready)
         for t in out:
             if t is not None:
                 t.record_stream(cur)
-        self.last_indices, self.last_windows = idx, wins
+        self.last_indices, self.last_windows, self.last_jitter = idx, wins, params
         return out
 
     def close(self):

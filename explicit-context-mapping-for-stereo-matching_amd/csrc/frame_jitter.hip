@@ -15,20 +15,17 @@
 // a product and a sum inlined from there are fused all the same (that changed 84 bytes of a 37x53 contrast at factor 0.6).
 #include "common.h"
 #include "../../include/ecm_augment.h"
-#include <hip/hip_fp16.h>
+#include "frame_io.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int FP_MAXB = 32;                   // samples per launch chunk, as in frame_prep.hip
-constexpr int JT_MAXV = 2 * FP_MAXB;          // views per launch chunk
+constexpr int JT_MAXV = 2 * FP_MAXB;          // views per launch chunk: both views of frame_io.h's FP_MAXB samples
 constexpr int JT_THREADS = 256, JT_PPT = 8, JT_TILE = JT_THREADS * JT_PPT;
 constexpr long long JT_MAX_PIXELS = 1ll << 24;        // S <= 255 * 2^24 < 2^32, and PIL's int(mean + 0.5) is exact up to here
 constexpr int OP_BRIGHTNESS = 0, OP_CONTRAST = 1, OP_SATURATION = 2, OP_HUE = 3, OP_NONE = 15;
 
-struct FrameCrops { int y0[FP_MAXB], x0[FP_MAXB]; };
-struct FrameNorm { float mean[3], stdv[3]; };
 // ops: four nibbles (the codes in order, OP_NONE behind them), the hue shift in bits 16..23, bit 24 set where contrast is present
 struct JitterViews { float f[JT_MAXV][3]; float pca[JT_MAXV][3]; int ops[JT_MAXV]; };
 constexpr int HAS_CONTRAST = 1 << 24;
@@ -127,9 +124,9 @@ struct SrcFrame {                     // packed frames: uint8 [B,H,W,6] (view 2b
         return ((size_t)(gv >> 1) * H + (crops.y0[bl] + r)) * W + (crops.x0[bl] + x);
     }
     __device__ __forceinline__ RGB load(size_t pix, int gv) const {
-        const unsigned short* q = reinterpret_cast<const unsigned short*>(rgb + pix * 6);      // 6 B per pixel: 2-B aligned
-        const int a = q[0], b = q[1], e = q[2];
-        return (gv & 1) ? RGB{b >> 8, e & 0xff, e >> 8} : RGB{a & 0xff, a >> 8, b & 0xff};
+        int c[3];
+        frame_unpack3(rgb, pix, gv & 1, c);
+        return RGB{c[0], c[1], c[2]};
     }
 };
 struct SrcU8 {                        // resident views: uint8 [N,H,W,3]
@@ -162,8 +159,7 @@ struct SinkFrame {                    // KITTI.py:171-191 behind the jitter: NCH
             if (!side && image) image[o + k * plane] = x;                                       // KITTI.py:189: the clamped left view
             dst[o + k * plane] = div_rn(sub_rn(x, nrm.mean[k]), nrm.stdv[k]);
         }
-        if (!side)
-            disp[(size_t)b * plane + p] = HALF ? __half2float(static_cast<const __half*>(disp_in)[pix]) : static_cast<const float*>(disp_in)[pix];
+        if (!side) disp[(size_t)b * plane + p] = frame_disp<HALF>(disp_in, pix);
     }
 };
 struct SinkU8 {
@@ -276,19 +272,6 @@ int jitter_launch(MakeSrc make_src, Sink sink, int views, int per_sample, long l
     return ECM_LAUNCH_RESULT();
 }
 
-template <bool HALF>
-int frame_jitter(const unsigned char* rgb6, const void* disp_in, float* left, float* right, float* disp, float* image, int B, int H,
-                 int W, const int* crop_y0, const int* crop_x0, int th, int tw, const float* factors, const int* order,
-                 const int* hue_shift, const float* pca, const FrameNorm& nrm, unsigned* partial, hipStream_t st) {
-    const SinkFrame<HALF> sink{left, right, disp, image, disp_in, nrm, (size_t)th * tw};
-    auto make_src = [=](int v0, int nv) {
-        SrcFrame src{rgb6, FrameCrops{}, H, W, tw};
-        for (int i = 0; i < nv / 2; ++i) { src.crops.y0[i] = crop_y0[v0 / 2 + i]; src.crops.x0[i] = crop_x0[v0 / 2 + i]; }
-        return src;
-    };
-    return jitter_launch(make_src, sink, 2 * B, 2, (long long)th * tw, factors, order, hue_shift, pca, partial, st);
-}
-
 }  // namespace
 
 extern "C" int ecma_jitter_tile(void) { return JT_TILE; }
@@ -313,16 +296,12 @@ extern "C" int ecma_frame_prep_jitter_fwd(const unsigned char* rgb6, const void*
     ECM_CHECK_ARG(rgb6 && disp_in && left && right && disp && crop_y0 && crop_x0 && factors && order && hue_shift && pca && mean3 &&
                   std3 && scratch && B > 0 && H > 0 && W > 0 && th > 0 && tw > 0);
     if (th > 65535 || (long long)th * tw > JT_MAX_PIXELS || B > (1 << 29)) return ECM_EUNSUP;
-    for (int b = 0; b < B; ++b)                 // the windows lie inside the frame (the loader's randint bounds)
-        if (!(crop_y0[b] >= 0 && crop_x0[b] >= 0 && (long long)crop_y0[b] + th <= H && (long long)crop_x0[b] + tw <= W)) return ECM_EINVAL;
+    if (!frame_windows_inside(crop_y0, crop_x0, B, th, tw, H, W)) return ECM_EINVAL;
     if (scratch_bytes < scratch_bytes_of(2 * B, th, tw)) return ECM_ESCRATCH;
-    FrameNorm nrm;
-    for (int c = 0; c < 3; ++c) { nrm.mean[c] = mean3[c]; nrm.stdv[c] = std3[c]; }
-    hipStream_t st = ecm_stream(stream);
-    unsigned* partial = static_cast<unsigned*>(scratch);
-    if (disp_is_half)
-        return frame_jitter<true>(rgb6, disp_in, left, right, disp, image, B, H, W, crop_y0, crop_x0, th, tw, factors, order, hue_shift,
-                                  pca, nrm, partial, st);
-    return frame_jitter<false>(rgb6, disp_in, left, right, disp, image, B, H, W, crop_y0, crop_x0, th, tw, factors, order, hue_shift,
-                               pca, nrm, partial, st);
+    auto make_src = [=](int v0, int nv) { return SrcFrame{rgb6, frame_crops(crop_y0, crop_x0, v0 / 2, nv / 2), H, W, tw}; };
+    return frame_by_disp(disp_is_half, [&](auto half) {
+        const SinkFrame<decltype(half)::value> sink{left, right, disp, image, disp_in, frame_norm(mean3, std3), (size_t)th * tw};
+        return jitter_launch(make_src, sink, 2 * B, 2, (long long)th * tw, factors, order, hue_shift, pca, static_cast<unsigned*>(scratch),
+                             ecm_stream(stream));
+    });
 }

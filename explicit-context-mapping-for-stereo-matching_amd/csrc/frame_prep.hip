@@ -13,13 +13,9 @@
 //     outputs are bit-identical to the float32-frame path; an fp16 disparity is the fp32 value rounded to fp16.
 // Arithmetic is the loader's, operation for operation in fp32 -- (v/255 - mean)/std with IEEE division.
 #include "common.h"
-#include <hip/hip_fp16.h>
+#include "frame_io.h"
 
 namespace {
-
-constexpr int FP_MAXB = 32;
-struct FrameCrops { int y0[FP_MAXB], x0[FP_MAXB]; };
-struct FrameNorm { float mean[3], stdv[3]; };
 
 struct SrcF32 {                       // float32 [B,H,W,7]
     const float* frames;
@@ -35,11 +31,8 @@ struct SrcPacked {                    // uint8 [B,H,W,6] + fp16|fp32 [B,H,W]
     const unsigned char* rgb;
     const void* disp;
     __device__ __forceinline__ void load(size_t pix, float (&c)[6], float& d) const {
-        const unsigned short* p = reinterpret_cast<const unsigned short*>(rgb + pix * 6);      // 6 B per pixel: 2-B aligned
-        const unsigned a = p[0], b = p[1], e = p[2];
-        c[0] = (float)(a & 0xff); c[1] = (float)(a >> 8); c[2] = (float)(b & 0xff);
-        c[3] = (float)(b >> 8);   c[4] = (float)(e & 0xff); c[5] = (float)(e >> 8);
-        d = HALF ? __half2float(static_cast<const __half*>(disp)[pix]) : static_cast<const float*>(disp)[pix];
+        frame_unpack3(rgb, pix, false, c), frame_unpack3(rgb, pix, true, c + 3);
+        d = frame_disp<HALF>(disp, pix);
     }
 };
 
@@ -86,29 +79,21 @@ int frame_prep_launch(Src src, float* left, float* right, float* disp, float* im
                       int mode, hipStream_t st) {
     if (!(left && right && disp && mean3 && std3 && B > 0 && H > 0 && W > 0 && th > 0 && tw > 0)) return ECM_EINVAL;
     if (th > 65535) return ECM_EUNSUP;
-    FrameNorm nrm;
-    for (int c = 0; c < 3; ++c) { nrm.mean[c] = mean3[c]; nrm.stdv[c] = std3[c]; }
     if (mode == 0) {
         if (!(crop_y0 && crop_x0 && split >= 0 && split <= th && tail >= 0 && th - split <= tail && tail <= H)) return ECM_EINVAL;
-        for (int b = 0; b < B; ++b)             // crop windows must lie inside the frame (the loader's randint bounds)
-            if (!(crop_y0[b] >= 0 && crop_x0[b] >= 0 && crop_y0[b] + split <= H && crop_x0[b] + tw <= W)) return ECM_EINVAL;
+        if (!frame_windows_inside(crop_y0, crop_x0, B, split, tw, H, W)) return ECM_EINVAL;
     } else if (mode == 1) {
         if (!(th >= H && tw >= W && th - H <= H && tw - W <= W)) return ECM_EINVAL;      // the pad repeats existing rows / columns
     } else {
         return ECM_EUNSUP;
     }
+    const auto kernel = mode == 0 ? frame_prep_kernel<0, Src> : frame_prep_kernel<1, Src>;
     for (int b0 = 0; b0 < B; b0 += FP_MAXB) {
         const int nb = B - b0 < FP_MAXB ? B - b0 : FP_MAXB;
-        FrameCrops crops{};
-        if (mode == 0)
-            for (int i = 0; i < nb; ++i) { crops.y0[i] = crop_y0[b0 + i]; crops.x0[i] = crop_x0[b0 + i]; }
+        const FrameCrops crops = mode == 0 ? frame_crops(crop_y0, crop_x0, b0, nb) : FrameCrops{};
         const dim3 grid((tw + 255) / 256, th, nb), block(256);
-        if (mode == 0)
-            hipLaunchKernelGGL((frame_prep_kernel<0, Src>), grid, block, 0, st, src, left, right, disp, image, crops, nrm, H, W, th,
-                               tw, split, tail, b0);
-        else
-            hipLaunchKernelGGL((frame_prep_kernel<1, Src>), grid, block, 0, st, src, left, right, disp, image, crops, nrm, H, W, th,
-                               tw, split, tail, b0);
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, src, left, right, disp, image, crops, frame_norm(mean3, std3), H, W, th, tw, split,
+                           tail, b0);
     }
     return ECM_LAUNCH_RESULT();
 }
@@ -135,10 +120,8 @@ extern "C" int ecm_frame_prep_packed(const unsigned char* rgb6, const void* disp
                                      const int* crop_x0, int th, int tw, int split, int tail, const float* mean3,
                                      const float* std3, int mode, void* stream) {
     ECM_CHECK_ARG(rgb6 && disp_in);
-    hipStream_t st = ecm_stream(stream);
-    if (disp_is_half)
-        return frame_prep_launch(SrcPacked<true>{rgb6, disp_in}, left, right, disp, image, B, H, W, crop_y0, crop_x0, th, tw,
-                                 split, tail, mean3, std3, mode, st);
-    return frame_prep_launch(SrcPacked<false>{rgb6, disp_in}, left, right, disp, image, B, H, W, crop_y0, crop_x0, th, tw,
-                             split, tail, mean3, std3, mode, st);
+    return frame_by_disp(disp_is_half, [&](auto half) {
+        return frame_prep_launch(SrcPacked<decltype(half)::value>{rgb6, disp_in}, left, right, disp, image, B, H, W, crop_y0, crop_x0, th,
+                                 tw, split, tail, mean3, std3, mode, ecm_stream(stream));
+    });
 }

@@ -10,6 +10,7 @@
 //                 word; otherwise every pixel is loaded and stored on its own.
 // No atomics, no LDS, no scratch memory; plane offsets are 64-bit.
 #include "common.h"
+#include "frame_io.h"
 #include "../../include/ecm_rectify.h"
 #include <climits>
 #include <cmath>
@@ -52,7 +53,7 @@ struct RemapArgs {
     unsigned char *mask_l, *mask_r;
     size_t map_stride;                        // floats between the maps of two images: 0 where the batch shares one
     int H, W, Ho, Wo;
-    float mean[3], stdv[3], border;
+    FrameNorm nrm; float border;
 };
 
 template <bool U8>
@@ -125,7 +126,7 @@ __global__ __launch_bounds__(TX * TY) void remap_pair(RemapArgs a) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             img[c][k] = s[c] / 255.0f;
-            net[c][k] = (img[c][k] - a.mean[c]) / a.stdv[c];
+            net[c][k] = (img[c][k] - a.nrm.mean[c]) / a.nrm.stdv[c];
         }
     }
     if (VEC) {
@@ -201,8 +202,7 @@ extern "C" int ecmr_remap_pair_fwd(const void* left_raw, const void* right_raw, 
     a.src_l = left_raw; a.src_r = right_raw; a.map_l = map_left; a.map_r = map_right;
     a.out_l = left; a.out_r = right; a.image = image; a.mask_l = mask_left; a.mask_r = mask_right;
     a.map_stride = map_per_image ? (size_t)2 * plane : 0;
-    a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.border = border;
-    for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; }
+    a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.border = border; a.nrm = frame_norm(mean3, std3);
     const bool vec = Wo % PX == 0 && aligned16(map_left) && aligned16(map_right) && aligned16(left) && aligned16(right) &&
                      aligned16(image) && aligned16(mask_left) && aligned16(mask_right);
     const dim3 grid((Wo + TILE_W - 1) / TILE_W, (Ho + TY - 1) / TY, 2 * B), block(TX, TY);

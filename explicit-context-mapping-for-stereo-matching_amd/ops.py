@@ -2484,6 +2484,7 @@ def classifier_tail(x, gamma, beta, w):
 
 
 FLYING3D_MEAN, FLYING3D_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)          # cmf/loader/Flying3d.py:26-27
+_NORM3_OWN = {id(v): _host(C.c_float, v) for v in (FLYING3D_MEAN, FLYING3D_STD)}    # the defaults' host arrays: built and checked once
 
 
 def frame_prep(frames, crop_y0, crop_x0, th, tw, split=None, tail=0, mean=FLYING3D_MEAN, std=FLYING3D_STD, want_image=False):
@@ -2502,43 +2503,65 @@ def frame_prep_kitti_eval(frames, th=384, tw=1248, mean=FLYING3D_MEAN, std=FLYIN
     return _frame_prep(frames, None, None, th, tw, None, 0, mean, std, want_image, 1)
 
 
+# ---- the operands of the frame decodes, stated once: the library reads B origins and 3 floats whatever a list holds
+def _packed_shard(who, frames):                               # -> rgb6, disparity (contiguous), B, H, W of a shard that is not empty and on one device
+    rgb, dsp = frames
+    _on_device(rgb, dsp)
+    _need(rgb.dtype == torch.uint8 and dsp.dtype in (torch.float16, torch.float32) and rgb.dim() == 4 and rgb.shape[-1] == 6
+          and tuple(rgb.shape[:3]) == tuple(dsp.shape) and rgb.numel() > 0 and rgb.device == dsp.device,
+          lambda: f"{who}: packed shard must be (uint8 [B,H,W,6], fp16|fp32 [B,H,W]) on one device, got {rgb.dtype} {tuple(rgb.shape)} "
+                  f"on {rgb.device} / {dsp.dtype} {tuple(dsp.shape)} on {dsp.device}")
+    return (rgb.contiguous(), dsp.contiguous(), *dsp.shape)
+
+
+def _window_origins(who, crop_y0, crop_x0, B):
+    ys, xs = [int(v) for v in (() if crop_y0 is None else crop_y0)], [int(v) for v in (() if crop_x0 is None else crop_x0)]
+    if len(ys) != B or len(xs) != B:
+        raise ValueError(f"{who}: crop_y0 {ys} / crop_x0 {xs}: one window origin per sample, {B} of each")
+    return ys, xs
+
+
+def _norm3(who, name, values, nonzero=False):                 # mean or std, any sequence of three finite numbers, as the host array an entry reads
+    if id(values) in _NORM3_OWN:                               # the module's own constants, finite and non-zero: no check per batch
+        return _NORM3_OWN[id(values)]
+    vals = values.tolist() if hasattr(values, "tolist") else values
+    if not isinstance(vals, (tuple, list)) or len(vals) != 3 or not all(_is_real(v) and not (nonzero and v == 0) for v in vals):
+        raise ValueError(f"{who}: {name} {values!r}: three finite numbers" + (", none zero" if nonzero else ""))
+    return _host(C.c_float, vals)
+
+
+def _decode_outputs(B, rows, cols, dev, want_image, with_disp=True):
+    left = torch.empty(B, 3, rows, cols, device=dev, dtype=torch.float32)
+    disp = torch.empty(B, rows, cols, device=dev, dtype=torch.float32) if with_disp else None
+    return left, torch.empty_like(left), disp, torch.empty_like(left) if want_image else None
+
+
+def _decoded(left, right, disp, image):
+    return (left, right, disp) if image is None else (left, right, disp, image)
+
+
 def _frame_prep(frames, crop_y0, crop_x0, th, tw, split, tail, mean, std, want_image, mode):
-    packed = isinstance(frames, (tuple, list))
+    who, packed = "frame_prep", isinstance(frames, (tuple, list))
     if packed:
-        rgb, dsp = frames
-        _on_device(rgb, dsp)
-        if rgb.dtype != torch.uint8 or dsp.dtype not in (torch.float16, torch.float32) or rgb.shape[-1] != 6 \
-                or tuple(rgb.shape[:3]) != tuple(dsp.shape):
-            raise RuntimeError(f"packed shard must be (uint8 [B,H,W,6], fp16|fp32 [B,H,W]), got {rgb.dtype} {tuple(rgb.shape)} / "
-                               f"{dsp.dtype} {tuple(dsp.shape)}")
-        rgb, dsp = rgb.contiguous(), dsp.contiguous()
-        B, H, W = dsp.shape
-        dev = rgb.device
+        rgb, dsp, B, H, W = _packed_shard(who, frames)
     else:
         _chk(frames)
         frames = _c(frames)
         B, H, W, ch = frames.shape
         if ch != 7:
             raise RuntimeError(f"frame_prep expects [B,H,W,7] frames (left RGB, right RGB, disparity), got {tuple(frames.shape)}")
-        dev = frames.device
     split = th if split is None else int(split)
-    ys = _host(C.c_int, [int(v) for v in crop_y0] if crop_y0 is not None else None)
-    xs = _host(C.c_int, [int(v) for v in crop_x0] if crop_x0 is not None else None)
-    m3, s3 = _host(C.c_float, mean), _host(C.c_float, std)
-    left = torch.empty(B, 3, th, tw, device=dev, dtype=torch.float32)
-    right = torch.empty_like(left)
-    disp = torch.empty(B, th, tw, device=dev, dtype=torch.float32)
-    image = torch.empty_like(left) if want_image else None
+    ys, xs = map(_host, (C.c_int, C.c_int), _window_origins(who, crop_y0, crop_x0, B)) if mode == 0 else (None, None)
+    m3, s3 = _norm3(who, "mean", mean), _norm3(who, "std", std)
+    left, right, disp, image = _decode_outputs(B, th, tw, rgb.device if packed else frames.device, want_image)
+    outs = (_p(left), _p(right), _p(disp), _p(image), B, H, W)
     if packed:
-        _lib.call("ecm_frame_prep_packed", _p(rgb), _p(dsp), int(dsp.dtype == torch.float16), _p(left), _p(right), _p(disp),
-                  _p(image), B, H, W, ys, xs, int(th), int(tw), split, int(tail), m3, s3, mode, _stream())
+        _lib.call("ecm_frame_prep_packed", _p(rgb), _p(dsp), int(dsp.dtype == torch.float16), *outs, ys, xs, int(th), int(tw), split, int(tail), m3, s3, mode, _stream())
     elif mode == 1:
-        _lib.call("ecm_frame_prep_kitti_eval", _p(frames), _p(left), _p(right), _p(disp), _p(image), B, H, W, int(th), int(tw),
-                  m3, s3, _stream())
+        _lib.call("ecm_frame_prep_kitti_eval", _p(frames), *outs, int(th), int(tw), m3, s3, _stream())
     else:
-        _lib.call("ecm_frame_prep", _p(frames), _p(left), _p(right), _p(disp), _p(image), B, H, W, ys, xs, int(th), int(tw),
-                  split, int(tail), m3, s3, _stream())
-    return (left, right, disp, image) if want_image else (left, right, disp)
+        _lib.call("ecm_frame_prep", _p(frames), *outs, ys, xs, int(th), int(tw), split, int(tail), m3, s3, _stream())
+    return _decoded(left, right, disp, image)
 
 
 # ------------------------------------------------------------------------------------ the KITTI training transform
@@ -2671,36 +2694,23 @@ def frame_prep_jitter(frames, crop_y0, crop_x0, th, tw, params, mean=FLYING3D_ME
         raise ValueError(f"{who}: frames: a packed shard (uint8 [B,H,W,6], fp16|fp32 [B,H,W])")
     if not isinstance(params, JitterParams):
         raise ValueError(f"{who}: params {type(params).__name__}: a JitterParams (jitter_params)")
-    rgb, dsp = frames
-    _on_device(rgb, dsp)
-    _need(rgb.dtype == torch.uint8 and dsp.dtype in (torch.float16, torch.float32) and rgb.dim() == 4 and rgb.shape[-1] == 6
-          and tuple(rgb.shape[:3]) == tuple(dsp.shape) and rgb.numel() > 0 and rgb.device == dsp.device,
-          lambda: f"{who}: packed shard must be (uint8 [B,H,W,6], fp16|fp32 [B,H,W]) on one device, got {rgb.dtype} {tuple(rgb.shape)} / "
-                  f"{dsp.dtype} {tuple(dsp.shape)}")
-    B, H, W = dsp.shape
+    rgb, dsp, B, H, W = _packed_shard(who, frames)
     th, tw = _integer(who, "th", th, 1, None), _integer(who, "tw", tw, 1, None)
-    ys, xs = [int(v) for v in crop_y0], [int(v) for v in crop_x0]
-    if len(ys) != B or len(xs) != B or any(y < 0 or y + th > H for y in ys) or any(x < 0 or x + tw > W for x in xs):
-        raise ValueError(f"{who}: windows of {th} x {tw} at {ys} / {xs}: one per sample, inside the {H} x {W} frame")
+    ys, xs = _window_origins(who, crop_y0, crop_x0, B)
+    if any(y < 0 or y + th > H for y in ys) or any(x < 0 or x + tw > W for x in xs):
+        raise ValueError(f"{who}: windows of {th} x {tw} at {ys} / {xs}: inside the {H} x {W} frame")
     fields = dict(factors=(B, 2, 3), order=(B, 2, 4), hue_shift=(B, 2), pca=(B, 2, 3))
     for name, shape in fields.items():
         t = getattr(params, name)
         if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
             raise ValueError(f"{who}: params.{name}: a tensor of {shape} for {B} samples")
     fh, oh, hh, ph = _jitter_views(who, 2 * B, *(getattr(params, name).reshape((2 * B,) + shape[2:]) for name, shape in fields.items()))
-    m3, s3 = [float(v) for v in mean], [float(v) for v in std]
-    if len(m3) != 3 or len(s3) != 3:
-        raise ValueError(f"{who}: mean {m3}, std {s3}: three values each")
+    m3, s3 = _norm3(who, "mean", mean), _norm3(who, "std", std)
     scratch, nbytes = _jitter_scratch(who, 2 * B, th, tw, rgb.device)
-    rgb, dsp = rgb.contiguous(), dsp.contiguous()
-    left = torch.empty(B, 3, th, tw, device=rgb.device, dtype=torch.float32)
-    right = torch.empty_like(left)
-    disp = torch.empty(B, th, tw, device=rgb.device, dtype=torch.float32)
-    image = torch.empty_like(left) if want_image else None
+    left, right, disp, image = _decode_outputs(B, th, tw, rgb.device, want_image)
     _lib.call("ecma_frame_prep_jitter_fwd", _p(rgb), _p(dsp), int(dsp.dtype == torch.float16), _p(left), _p(right), _p(disp), _p(image), B,
-              H, W, _host(C.c_int, ys), _host(C.c_int, xs), th, tw, fh, oh, hh, ph, _host(C.c_float, m3), _host(C.c_float, s3),
-              _p(scratch), nbytes, _stream())
-    return (left, right, disp, image) if want_image else (left, right, disp)
+              H, W, _host(C.c_int, ys), _host(C.c_int, xs), th, tw, fh, oh, hh, ph, m3, s3, _p(scratch), nbytes, _stream())
+    return _decoded(left, right, disp, image)
 
 
 # ------------------------------------------------------------------------------------ stereo rectification
@@ -2873,12 +2883,6 @@ def rectify_map(K, D, R, P, new_size, device):
     return out
 
 
-def _norm3(who, name, values, nonzero):
-    if not isinstance(values, (tuple, list)) or len(values) != 3 or not all(_is_real(v) and not (nonzero and v == 0) for v in values):
-        raise ValueError(f"{who}: {name} {values!r}: three finite numbers" + (", none zero" if nonzero else ""))
-    return [float(v) for v in values]
-
-
 @torch.no_grad()
 def remap_pair(left_raw, right_raw, map_left, map_right, mean=FLYING3D_MEAN, std=FLYING3D_STD, border=0.0, want_image=False,
                with_mask=False):
@@ -2907,20 +2911,16 @@ def remap_pair(left_raw, right_raw, map_left, map_right, mean=FLYING3D_MEAN, std
           lambda: f"{who}: map_left {map_left.dtype} {tuple(map_left.shape)}: want float32 [2,Ho,Wo] or [{B},2,Ho,Wo]")
     _need(map_right.dtype == torch.float32 and map_right.shape == map_left.shape,
           lambda: f"{who}: map_right {map_right.dtype} {tuple(map_right.shape)} against map_left {tuple(map_left.shape)}")
-    m3, s3 = _norm3(who, "mean", mean, False), _norm3(who, "std", std, True)
+    m3, s3 = _norm3(who, "mean", mean), _norm3(who, "std", std, nonzero=True)
     _real(who, "border", border, fp32=True)
     Ho, Wo = map_left.shape[-2:]
     lr, rr, ml, mr = left_raw.detach().contiguous(), right_raw.detach().contiguous(), _c(map_left.detach()), _c(map_right.detach())
-    dev = lr.device
-    left = torch.empty(B, 3, Ho, Wo, device=dev, dtype=torch.float32)
-    right = torch.empty_like(left)
-    image = torch.empty_like(left) if want_image else None
-    mask_l = torch.empty(B, Ho, Wo, device=dev, dtype=torch.uint8) if with_mask else None
+    left, right, _, image = _decode_outputs(B, Ho, Wo, lr.device, want_image, with_disp=False)
+    mask_l = torch.empty(B, Ho, Wo, device=lr.device, dtype=torch.uint8) if with_mask else None
     mask_r = torch.empty_like(mask_l) if with_mask else None
     # B * max(H * W, Ho * Wo) >= 2^31 is refused by the library before any launch (ECM_EUNSUP -> RuntimeError)
     _lib.call("ecmr_remap_pair_fwd", _p(lr), _p(rr), int(u8), _p(ml), _p(mr), int(map_left.dim() == 4), _p(left), _p(right),
-              _p(image), _p(mask_l), _p(mask_r), B, H, W, Ho, Wo, _host(C.c_float, m3), _host(C.c_float, s3), float(border),
-              _stream())
+              _p(image), _p(mask_l), _p(mask_r), B, H, W, Ho, Wo, m3, s3, float(border), _stream())
     out = (left, right) + ((image,) if want_image else ())
     return out + ((mask_l.view(torch.bool), mask_r.view(torch.bool)) if with_mask else ())
 

@@ -252,13 +252,27 @@ class ShardFeeder:
                    dsp=torch.empty(self.batch, H, W, dtype=pin["dsp"].dtype, device=self.device))
         return dict(pin=pin, dev=dev, shape=(H, W), h2d_done=None)
 
+    def _decode(self, frames, H, W, jgens):
+        """(out, params) of the split's decode of resident packed frames of H x W, whole: params is its JitterParams or None."""
+        ops, zeros, want = self.ops, [0] * self.batch, self.want_image
+        if self.split == "train" and self.jitter is not None:
+            params = ops.jitter_params(self.batch, *jgens, **self.jitter)
+            return ops.frame_prep_jitter(frames, zeros, zeros, H, W, params, want_image=want), params
+        if self.split == "train":
+            return ops.frame_prep(frames, zeros, zeros, H, W, want_image=want), None
+        if self.split == "test":                                            # 540 rows + the last 36 again (Flying3d.py:66-72)
+            return ops.frame_prep(frames, zeros, zeros, min(H, 540) + 36, min(W, 960), split=min(H, 540), tail=36, want_image=want), None
+        if self.split == "kitti_test":
+            return ops.frame_prep_kitti_eval(frames, want_image=want), None
+        raise ValueError(f"unknown split {self.split!r}")
+
     def _produce(self, epoch):
         try:                                                                # whatever goes wrong reaches the consumer
             torch.cuda.set_device(self.device)
             rng = random.Random(self.seed * 7919 + epoch * 104729 + self.rank)
-            if self.jitter is not None:                                     # generators of their own: the windows stay jitter=None's
-                jrng = random.Random(f"jitter/{self.seed}/{epoch}/{self.rank}")
-                jgen = torch.Generator().manual_seed((self.seed * 7919 + epoch * 104729 + self.rank) * 2 + 1)
+            # the jitter's generators are its own (the windows stay jitter=None's), and are made only for it
+            jgens = None if self.jitter is None else (random.Random(f"jitter/{self.seed}/{epoch}/{self.rank}"),
+                                                      torch.Generator().manual_seed((self.seed * 7919 + epoch * 104729 + self.rank) * 2 + 1))
             k = 0
             for idx in self._order(epoch):
                 if self._stop.is_set():
@@ -289,21 +303,7 @@ class ShardFeeder:
                     slot["dev"]["dsp"].copy_(slot["pin"]["dsp"], non_blocking=True)
                     slot["h2d_done"] = torch.cuda.Event()
                     slot["h2d_done"].record(self._copy)
-                    frames = (slot["dev"]["rgb"], slot["dev"]["dsp"])
-                    params = None
-                    if self.split == "train" and self.jitter is not None:
-                        params = self.ops.jitter_params(self.batch, jrng, jgen, **self.jitter)
-                        out = self.ops.frame_prep_jitter(frames, [0] * self.batch, [0] * self.batch, H, W, params,
-                                                         want_image=self.want_image)
-                    elif self.split == "train":
-                        out = self.ops.frame_prep(frames, [0] * self.batch, [0] * self.batch, H, W, want_image=self.want_image)
-                    elif self.split == "test":                             # 540 rows + the last 36 again (Flying3d.py:66-72)
-                        out = self.ops.frame_prep(frames, [0] * self.batch, [0] * self.batch, min(H, 540) + 36, min(W, 960),
-                                                  split=min(H, 540), tail=36, want_image=self.want_image)
-                    elif self.split == "kitti_test":
-                        out = self.ops.frame_prep_kitti_eval(frames, want_image=self.want_image)
-                    else:
-                        raise ValueError(f"unknown split {self.split!r}")
+                    out, params = self._decode((slot["dev"]["rgb"], slot["dev"]["dsp"]), H, W, jgens)
                     ready = torch.cuda.Event()
                     ready.record(self._copy)
                 self._q.put((out, ready, idx, wins, params))

@@ -102,7 +102,8 @@ def jitter(img, factors, order, shift):
 
 
 def finish(u8, pca, mean, std):
-    """KITTI.py:171-191 behind the jitter, in fp32: (image [3,H,W] clamped to 0..1, the normalised view [3,H,W])."""
+    """KITTI.py:171-191 behind the jitter, in fp32: (image [3,H,W] clamped to 0..1, the normalised view [3,H,W]).  The tests' reference is
+    frame_fixtures.loader_statements; tests/test_color_jitter_cpu.py holds the two to each other."""
     x = u8.astype(F32).transpose(2, 0, 1) / F32(255)
     x = x + np.asarray(pca, F32).reshape(3, 1, 1)
     x = np.minimum(np.maximum(x, F32(0)), F32(1))

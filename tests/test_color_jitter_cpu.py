@@ -209,6 +209,20 @@ def test_hue_shift_is_the_uint8_wrap():
         assert R.hue_shift_of(h) == want == int(h * 255) % 256, h
 
 
+def test_the_two_statements_of_the_loader_agree():
+    """The numpy statement behind the jitter and the torch one that the decodes' tests compare against (tests/frame_fixtures.py),
+    once, bit for bit: all 256 bytes in every channel, both clamps binding, and no shift at all against the statement without one."""
+    from frame_fixtures import MEAN, STD, loader_statements
+    u8 = torch.stack([torch.arange(256), torch.arange(255, -1, -1), (torch.arange(256) * 7) % 256], -1).to(torch.uint8).reshape(16, 16, 3)
+    for pca in ((0.9, -0.9, 0.02), (0.0, 0.0, 0.0)):
+        image, view = loader_statements(u8, torch.tensor(pca))
+        rimage, rview = R.finish(u8.numpy(), pca, MEAN, STD)
+        assert np.array_equal(image.numpy(), rimage) and np.array_equal(view.numpy(), rview)
+    assert float(image.min()) >= 0 and float(loader_statements(u8, torch.tensor((0.9, -0.9, 0.02)))[0].max()) == 1.0
+    plain = loader_statements(u8)
+    assert torch.equal(plain[0], image) and torch.equal(plain[1], view)          # a zero shift and a clamp that never binds: Flying3d's
+
+
 def test_python_refusals():
     ops = ecm().ops
     rng, gen = random.Random(0), torch.Generator()

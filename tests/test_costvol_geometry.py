@@ -35,7 +35,7 @@ NCP, NCQ = 15, 6                                   # costvol_conv.hip: classes o
 LDS_MAX = 64 * 1024                                # costvol_conv.hip: both row-staged gates
 LT = ET = 256                                      # loss.hip / eval.hip: threads of a reduction workgroup
 PER_THREAD, MAX_BLOCKS, FINAL_LANES = 8, 1024, 64  # elements per thread below the cap, the cap, lanes of stereo_loss_final
-CHUNK = 32                                         # eval.hip U16_MAXB / frame_prep.hip FP_MAXB: samples per launch
+CHUNK = 32                                         # eval.hip U16_MAXB / frame_io.h FP_MAXB: samples per launch
 UNREACHABLE_P = (9, 12)
 MAXDISP = 192.0
 
@@ -555,7 +555,7 @@ def test_assembly_constants_are_those_of_the_source():
 
 
 def test_reduction_constants_are_those_of_the_sources():
-    loss, ev, prep = _source("loss.hip"), _source("eval.hip"), _source("frame_prep.hip")
+    loss, ev, prep = _source("loss.hip"), _source("eval.hip"), _source("frame_io.h")
     assert int(_one(loss, r"^constexpr int LT = (\d+);", "LT")) == LT and int(_one(ev, r"^constexpr int ET = (\d+);", "ET")) == ET
     assert int(_one(loss, r"^constexpr int LOSS_MAX_BLOCKS = (\d+);", "cap")) == MAX_BLOCKS
     assert int(_one(ev, r"^constexpr int EVAL_MAX_BLOCKS = (\d+);", "cap")) == MAX_BLOCKS

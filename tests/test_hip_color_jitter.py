@@ -15,11 +15,11 @@ import torch
 
 import jitter_restatement as R
 from conftest import GOLDEN
+from frame_fixtures import MEAN, STD, loader_statements, packed_shard as packed
 
 pytestmark = pytest.mark.gpu
 
 S = importlib.import_module("explicit-context-mapping-for-stereo-matching_amd.shards")
-MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 ESCRATCH = -3
 
 
@@ -115,23 +115,6 @@ def test_contrast_mean_rounds_half_up_across_tiles(ops, prefix):
 
 
 # ---- (d), (e) the decode --------------------------------------------------------------------------------------------------------------------
-def packed(B, H, W, half, seed):
-    g = torch.Generator().manual_seed(seed)
-    rgb = torch.randint(0, 256, (B, H, W, 6), dtype=torch.uint8, generator=g)
-    dsp = torch.rand(B, H, W, generator=g) * 200
-    return rgb, (dsp.half() if half else dsp)
-
-
-def loader_statements(u8, pca):
-    """KITTI.py:171-191 on one jittered uint8 view [H,W,3], on the CPU in fp32: (image, normalised view)."""
-    x = u8.permute(2, 0, 1).float() / 255
-    x = x + pca.view(3, 1, 1)
-    x = x.clamp(min=0, max=1)
-    image = x + 0
-    x = (x - torch.tensor(MEAN).view(3, 1, 1)) / torch.tensor(STD).view(3, 1, 1)
-    return image, x
-
-
 @pytest.mark.parametrize("half", [True, False])
 def test_frame_prep_jitter_is_color_jitter_then_the_loader_statements(ops, half):
     B, H, W, th, tw = 3, 75, 140, 70, 131
@@ -149,8 +132,6 @@ def test_frame_prep_jitter_is_color_jitter_then_the_loader_statements(ops, half)
             assert torch.equal(got[b].cpu(), want), (b, v, (got[b].cpu() - want).abs().max())
             if v == 0:
                 assert torch.equal(image[b].cpu(), img) and 0 <= float(img.min()) and float(img.max()) <= 1
-            rimg, rwant = R.finish(u8[2 * b + v].numpy(), p.pca[b, v].numpy(), MEAN, STD)       # the restatement says the same
-            assert np.array_equal(want.numpy(), rwant) and np.array_equal(img.numpy(), rimg)
         assert torch.equal(disp[b].cpu(), dsp[b, ys[b]:ys[b] + th, xs[b]:xs[b] + tw].float())
     assert float(image[0, 0].max()) == 1.0 and float(image[0, 1].min()) == 0.0
     three = ops.frame_prep_jitter((rgb.cuda(), dsp.cuda()), ys, xs, th, tw, p)

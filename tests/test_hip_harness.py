@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN
+from frame_fixtures import float_frames
 from oracle import ecm_oracle as O
 from oracle.weights import eval_harness_inputs
 
@@ -78,21 +79,13 @@ def test_kitti_uint16_ragged_batch_vs_oracle(ecm):
         assert not img[b, hs[b]:].any() and not img[b, :, ws[b]:].any()
 
 
-def _frames(B, H, W, seed):
-    rs = np.random.RandomState(seed)
-    rgb = rs.randint(0, 256, size=(B, H, W, 6)).astype(np.uint8)
-    disp = (rs.rand(B, H, W) * 250.0).astype(np.float32)
-    frames = np.concatenate([rgb.astype(np.float32), disp[..., None]], 3)           # flying3ddata.py:34-39
-    return rgb, disp, frames
-
-
 @pytest.mark.parametrize("half", [False, True])
 def test_packed_shard_train_crop_bit_exact(ecm, half):
-    rgb, disp, frames = _frames(3, 300, 600, 5)
+    rgb, disp, frames = float_frames(3, 300, 600, 5)
     ys, xs = [0, 44, 13], [88, 0, 61]
-    a = ecm.ops.frame_prep(torch.from_numpy(frames).cuda(), ys, xs, 256, 512, want_image=True)
-    d_in = torch.from_numpy(disp).cuda()
-    b = ecm.ops.frame_prep((torch.from_numpy(rgb).cuda(), d_in.half() if half else d_in), ys, xs, 256, 512, want_image=True)
+    a = ecm.ops.frame_prep(frames.cuda(), ys, xs, 256, 512, want_image=True)
+    d_in = disp.cuda()
+    b = ecm.ops.frame_prep((rgb.cuda(), d_in.half() if half else d_in), ys, xs, 256, 512, want_image=True)
     for k in (0, 1, 3):
         assert torch.equal(a[k], b[k]), k                  # colour outputs: bit-identical
     want_d = a[2].half().float() if half else a[2]          # fp16 shard: the fp32 disparity rounded to fp16
@@ -100,11 +93,10 @@ def test_packed_shard_train_crop_bit_exact(ecm, half):
 
 
 def test_packed_shard_eval_pad_bit_exact_vs_oracle(ecm):
-    rgb, disp, frames = _frames(2, 540, 960, 6)
-    got = ecm.ops.frame_prep((torch.from_numpy(rgb).cuda(), torch.from_numpy(disp).cuda()), [0, 0], [0, 0], 576, 960, split=540,
-                             tail=36)
+    rgb, disp, frames = float_frames(2, 540, 960, 6)
+    got = ecm.ops.frame_prep((rgb.cuda(), disp.cuda()), [0, 0], [0, 0], 576, 960, split=540, tail=36)
     for b in range(2):
-        l, r, d, _ = O.flying3d_sample(frames[b], "test")
+        l, r, d, _ = O.flying3d_sample(frames[b].numpy(), "test")
         assert torch.equal(got[0][b].cpu(), l) and torch.equal(got[1][b].cpu(), r) and torch.equal(got[2][b].cpu(), d)
 
 
@@ -132,10 +124,9 @@ def test_eval_step_reproduces_test_py(ecm):
     """One evaluation step as test.py:63-94 runs it -- eval-pad the frames, forward under no_grad, crop [:540,:960],
     EPE of output3 -- on the HIP path end to end (frame prep, model, metric), finite and consistent with torch's own
     masked mean on the device."""
-    rgb, disp, _ = _frames(1, 540, 960, 8)
+    rgb, disp, _ = float_frames(1, 540, 960, 8)
     disp = disp * 0.7
-    left, right, gt = ecm.ops.frame_prep((torch.from_numpy(rgb).cuda(), torch.from_numpy(disp).cuda()), [0], [0], 576, 960,
-                                         split=540, tail=36)
+    left, right, gt = ecm.ops.frame_prep((rgb.cuda(), disp.cuda()), [0], [0], 576, 960, split=540, tail=36)
     torch.manual_seed(0)
     model = ecm.get_model("cmfsm").cuda().eval()
     with torch.no_grad():

@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import load_golden
+from frame_fixtures import float_frames
 from oracle import ecm_oracle as O
 from oracle.weights import seeded
 
@@ -467,10 +468,7 @@ def test_stereo_loss3(ecm, B, H, W):
 
 
 def _frames(B, H, W, seed):
-    g = torch.Generator().manual_seed(seed)
-    rgb = torch.randint(0, 256, (B, H, W, 6), generator=g).float()          # uint8 images promoted to float32
-    disp = torch.rand(B, H, W, 1, generator=g) * 300.0
-    return torch.cat([rgb, disp], -1).contiguous()
+    return float_frames(B, H, W, seed)[2]
 
 
 def test_frame_prep_train_crop_bit_exact(ecm):

@@ -17,11 +17,11 @@ import math
 import pytest
 import torch
 
+from frame_fixtures import MEAN, STD, loader_statements, raw_views as frames
 from test_abi_types import header_prototypes, lib_mod  # noqa: F401  (lib_mod: a fixture)
 
 ENTRIES = ("ecmr_rectify_map_fwd", "ecmr_rectify_map_params", "ecmr_remap_pair_fwd", "ecmr_tile_width")
 NAN, INF = float("nan"), float("inf")
-MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 F64 = torch.float64
 
 
@@ -94,22 +94,10 @@ def remap_t(raw, mp, mean=MEAN, std=STD, border=0.0, dtype=F64):
     return (image - mean_t) / std_t, image, fin & k00 & k01 & k10 & k11
 
 
-def frame_prep_t(raw):
-    """ops.frame_prep's planes of a uint8 [B,H,W,3] frame, in fp32: (v / 255 - mean) / std."""
-    v = raw.permute(0, 3, 1, 2).to(torch.float32)
-    return (v / 255.0 - torch.tensor(MEAN).view(1, 3, 1, 1)) / torch.tensor(STD).view(1, 3, 1, 1)
-
-
 def integer_map(Ho, Wo, dx=0, dy=0):
     x = torch.arange(Wo, dtype=torch.float32).view(1, Wo).expand(Ho, Wo) + dx
     y = torch.arange(Ho, dtype=torch.float32).view(Ho, 1).expand(Ho, Wo) + dy
     return torch.stack([x, y]).contiguous()
-
-
-def frames(B, H, W, seed, kind="u8"):
-    g = torch.Generator().manual_seed(seed)
-    raw = torch.randint(0, 256, (B, H, W, 3), generator=g, dtype=torch.uint8)
-    return raw if kind == "u8" else raw.permute(0, 3, 1, 2).to(torch.float32).contiguous()
 
 
 # ---- the rig of the tests -----------------------------------------------------------------------------------------------------------
@@ -249,7 +237,7 @@ def test_map_parameters_are_the_restatements_numbers(lib_mod):
 def test_identity_map_is_the_normalised_input(kind):
     raw = frames(2, 5, 7, 3, kind)
     out, image, mask = remap_t(raw, integer_map(4, 6))                                     # the last row and column need outside taps
-    want = frame_prep_t(frames(2, 5, 7, 3))
+    want = loader_statements(frames(2, 5, 7, 3))[1]                                        # ops.frame_prep's planes
     assert float((out - want[:, :, :4, :6].to(F64)).abs().max()) < 1e-6
     assert torch.equal(remap_t(raw, integer_map(4, 6), dtype=torch.float32)[0], want[:, :, :4, :6])
     assert bool(mask.all()) and mask.shape == (2, 4, 6) and mask.dtype == torch.bool
@@ -261,7 +249,7 @@ def test_identity_map_is_the_normalised_input(kind):
 def test_integer_shift_moves_the_image():
     raw = frames(1, 5, 9, 4)
     out, _, mask = remap_t(raw, integer_map(5, 9, dx=-2), border=37.0, dtype=torch.float32)
-    want = frame_prep_t(raw)
+    want = loader_statements(raw)[1]
     edge = ((torch.tensor(37.0) / 255.0 - torch.tensor(MEAN)) / torch.tensor(STD)).view(1, 3, 1, 1)
     assert torch.equal(out[..., 2:], want[..., :-2]) and torch.equal(out[..., :2], edge.expand(1, 3, 5, 2))
     assert not bool(mask[..., :2].any()) and bool(mask[:, :4, 2:].all()) and not bool(mask[:, 4].any())
